@@ -1,8 +1,14 @@
 #!/usr/bin/env python3
 """bench.py -- training images/sec of the AirNet hot path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dtype bf16|fp32] [--no-graph] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] [--dtype bf16|fp32] [--no-graph] [--dump-outputs DIR]
+                    [--full [--no-cpu-baseline] [--no-profile]]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
+
+A plain run sets up, warms up, times K steps and prints the result line (images/sec, ms_per_step, losses, step_mfma_fraction).
+--full adds the measurements that take runs of their own: the PCIe-inclusive rate, the per-launch GEMM / window-attention
+roofline (`roofline`, `wmsa`) and the CPU-oracle baseline (`cpu_baseline`).  --dump-outputs DIR writes what the last timed step
+returned (its loss vector) as float32 .npy (see dump_outputs).
 
 One "step" = one phase-2 training step of train.py:80-96 on one synthetic batch: zero grads, AirNet forward
 (query encoder, key-encoder EMA + forward, MoCo logits, decoder with learned frequency selection), L1 + 0.6 * CE,
@@ -422,6 +428,17 @@ def cpu_baseline(threads):
                       f'(denoise 15/25/50, derain, dehaze), 128x128, fp32, after {warm} warm-up step'}
 
 
+def dump_outputs(out, path):
+    """What the last timed step handed back to its caller, as float32 .npy under `path`: TrainEngine.step returns the loss
+    vector [total, l1, contrast] of the step (the updated weights stay inside the engine's flat buffers).  Inputs and initial
+    weights are identical in every run, but the backward's float atomics are unordered and Adam carries their rounding over
+    the steps: two runs drift apart, more so the more steps they take."""
+    os.makedirs(path, exist_ok=True)
+    loss = np.ascontiguousarray(out.detach().float().cpu().numpy(), dtype=np.float32)
+    np.save(os.path.join(path, 'loss.npy'), loss)
+    log(f'outputs of the last timed step -> {path}: loss {loss.shape}')
+
+
 def log(msg):
     print(f'[bench] {msg}', file=sys.stderr, flush=True)
 
@@ -481,8 +498,11 @@ def main():
     ap.add_argument('--encoder', default='Uformer', choices=['Uformer', 'ViT'], help='ViT = BASELINE configs[4] (with --patch-size 256)')
     ap.add_argument('--tasks', default='denoise', choices=['denoise', 'allinone'], help='allinone = BASELINE configs[2]/[3]: 5 tasks cycled over the batch')
     ap.add_argument('--no-graph', action='store_true')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-profile', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure the PCIe-inclusive rate, the GEMM / attention roofline and the CPU-oracle baseline (off by default)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU-oracle baseline')
+    ap.add_argument('--no-profile', action='store_true', help='with --full: skip the per-launch GEMM / attention roofline')
+    ap.add_argument('--dump-outputs', metavar='DIR', help='write what the last timed step returned (its loss vector) as DIR/loss.npy (float32)')
     args = ap.parse_args()
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         launch_ranks(args.gpus)                               # never returns
@@ -537,15 +557,8 @@ def main():
     loss = [float(v) for v in out]
     ips = args.batch * world * args.steps / dt
     log(f'{ips:.1f} images/sec, {dt / args.steps * 1e3:.1f} ms/step')
-    # what the rate would be if every step also took its batch over PCIe (pinned host -> HBM, not overlapped): reported, never `value`
-    host = [t.cpu().pin_memory() for t in (xq, xk, clean)]
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    for _ in range(5):
-        for h, d in zip(host, (xq, xk, clean)):
-            d.copy_(h, non_blocking=True)
-    torch.cuda.synchronize()
-    h2d = (time.perf_counter() - t1) / 5
+    if args.dump_outputs and rank == 0:
+        dump_outputs(out, args.dump_outputs)
 
     res = {
         'metric': f'training images/sec @{args.patch_size}x{args.patch_size}', 'value': round(ips, 2), 'unit': 'images/sec', 'n_gpus': world,
@@ -558,11 +571,22 @@ def main():
                                 + f'{args.patch_size}x{args.patch_size}, phase-2 train step (fwd+bwd+Adam, DropPath on)'), 'per_gpu_batch': args.batch,
                    'global_batch': args.batch * world, 'parallelism': f'dp{world}', 'hip_graph': graph_ok},
         'loss': {'total': loss[0], 'l1': loss[1], 'contrast': loss[2]},
-        'pcie_inclusive_value': round(args.batch * world / (dt / args.steps + h2d), 2), 'h2d_ms_per_step': round(h2d * 1e3, 3),
     }
+    if args.full:
+        # what the rate would be if every step also took its batch over PCIe (pinned host -> HBM, not overlapped): reported, never `value`
+        host = [t.cpu().pin_memory() for t in (xq, xk, clean)]
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        for _ in range(5):
+            for h, d in zip(host, (xq, xk, clean)):
+                d.copy_(h, non_blocking=True)
+        torch.cuda.synchronize()
+        h2d = (time.perf_counter() - t1) / 5
+        res['pcie_inclusive_value'] = round(args.batch * world / (dt / args.steps + h2d), 2)
+        res['h2d_ms_per_step'] = round(h2d * 1e3, 3)
     peak = PEAK_BF16 if args.dtype == 'bf16' else PEAK_F32_MFMA
     res['step_mfma_fraction'] = round(ips / world * flop_per_image_step(args.encoder, args.patch_size) / peak, 5)
-    if rank == 0 and world == 1 and not args.no_profile:
+    if args.full and rank == 0 and world == 1 and not args.no_profile:
         log('timing every distinct GEMM launch of the step (HIP events around captured replays) ...')
         agg, launches = gemm_profile(eng, data)
         dom = max(agg.items(), key=lambda kv: kv[1][1])
@@ -599,7 +623,7 @@ def main():
                 for kind, way, sig, cnt_, fl_, by_, t_ in sorted(arows, key=lambda r: -r[3] * r[6]):
                     f.write(f'{kind},{way},{sig[1]},{sig[2]},{sig[3]},{sig[4]},{sig[6]},{sig[7]},{sig[8]},{sig[9]},{sig[10]},{sig[11]},{sig[12]},'
                             f'{cnt_},{t_ * 1e6:.1f},{fl_ / t_ / 1e12:.1f},{by_ / t_ / 1e9:.0f}\n')
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         res['cpu_baseline'] = cpu_baseline(host_threads())
     if rank == 0:
         print(json.dumps(res))
