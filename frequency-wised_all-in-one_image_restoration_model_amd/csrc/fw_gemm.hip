@@ -39,7 +39,7 @@ struct GemmArgs {
     const float* rowscale; int rows_per_scale;
     const float* residual; long ldr;    // f32 [M][ldr]
     int out_f32;                        // C is float (else T)
-    int accumulate;                     // 0 store, 1 atomicAdd (f32 C only)
+    int accumulate;                     // 0 store; f32 C only: 1 add (read-modify-write when splitk == 1, else atomicAdd), 2 atomicAdd
     int splitk; int kper;               // K range per z-slice (multiple of the K step)
     char* C2; long ldc2;                // optional second output GELU(v), type T
     float* xsum;                        // optional: xsum[m] += sum_k X(m,k) (x_trans only; the bias gradient of a dW GEMM)
@@ -127,10 +127,10 @@ FW_DEV void epi_apply(const GemmArgs& a, const f32x4& bias, const uint4& ext, co
     if (a.out_f32) {
         float* cp = reinterpret_cast<float*>(a.C) + (long)z * a.c_zstride + (long)m * a.ldc + n0;
         if (a.accumulate && a.c_zstride == 0) {
-            if (a.splitk == 1) {                        // every element has exactly one producer in this launch: plain 16-byte read-modify-write
+            if (a.accumulate == 1 && a.splitk == 1) {   // the caller vouches that no other workgroup of this launch writes the element: plain 16-byte read-modify-write
                 const f32x4 old = *reinterpret_cast<const f32x4*>(cp);
                 *reinterpret_cast<f32x4*>(cp) = f32x4{old[0] + v[0], old[1] + v[1], old[2] + v[2], old[3] + v[3]};
-            } else {
+            } else {                                    // split-K slices, or (accumulate == 2) several products of a grouped launch adding into one gradient
 #pragma unroll
                 for (int r = 0; r < 4; ++r) atomicAdd(cp + r, v[r]);
             }
@@ -1053,7 +1053,7 @@ __global__ __launch_bounds__(256, 3) void gemm_wgrad_group_kernel(const GemmArgs
     if (it.x < 0) return;                                  // padding of an XCD's work list
     const GemmArgs a = probs[it.x];
     if (a.c_zstride > 0) tr_ring_tile<true, 32, 3, true>(a, it.y, it.z, it.w, smem);      // a slice's partial tile: plain store into its slab
-    else tr_ring_tile<true, 32, 3, false>(a, it.y, it.z, it.w, smem);                     // the whole reduction: dW += tile (f32 read-modify-write)
+    else tr_ring_tile<true, 32, 3, false>(a, it.y, it.z, it.w, smem);                     // the whole reduction: dW += tile (f32 read-modify-write, or atomicAdd for a shared gradient)
 }
 
 // The same product on 256 x 256 tiles (8 waves, wave tile 128 x 64, 32-token steps, 3 stages of 32 KB): half the operand bytes per
@@ -2014,8 +2014,10 @@ extern "C" int fw_gemm_last_kernel(char* buf, int n) {
 //   {X (dY, bf16 [tokens][ldx]), W (x, bf16 [tokens][ldw]), C (f32), ldx, ldw, ldc, M (rows of dW), N (columns), K (tokens), kper (tokens
 //    per slice, multiple of 32), splitk, xsum (f32 or 0), c_zstride, xsum_zstride, accumulate, 0};
 // probs: device scratch of nprob * fw_wgrad_group_prob_bytes() bytes the kernel's argument blocks are built in;
-// items: device int32 [nitems][4] = {problem, m tile, n tile, slice}.  splitk == 1: the tile ADDS into C (accumulate = 1) or stores;
-// splitk > 1: slice z stores its partial tile at C + z * c_zstride (the caller folds the slabs, fw_slab_reduce_multi).
+// items: device int32 [nitems][4] = {problem, m tile, n tile, slice}.  splitk == 1: the tile STORES into C (c_zstride = 1, accumulate = 0:
+// the sole writer of a zeroed gradient), ADDS by read-modify-write (accumulate = 1: no other product of the launch writes C) or by
+// atomicAdd (accumulate = 2: another product of the launch writes into the same range); splitk > 1: slice z stores its partial tile at
+// C + z * c_zstride (the caller folds the slabs, fw_slab_reduce_multi).  xsum is always added (atomicAdd) unless xsum_zstride > 0.
 extern "C" int fw_wgrad_group_prob_bytes(void) { return (int)sizeof(GemmArgs); }
 namespace {
 __global__ void wgrad_group_fill_kernel(const long long* __restrict__ tab, GemmArgs* __restrict__ probs, int nprob) {

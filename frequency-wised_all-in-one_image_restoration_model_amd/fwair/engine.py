@@ -347,6 +347,7 @@ class TrainEngine:
 
     def _fwd_bwd(self, xq, xk, clean):
         self.flat_g.zero_()
+        ops.mark_zeroed(self.flat_g)                         # grouped weight gradients may store into it (ops.wgrad)
         restored, logits, labels = self.net(x_query=xq, x_key=xk)
         total, l1, contrast = train_loss(restored, clean, torch.stack(logits, 0), self.w, 1.0 / self.allreduce.world)
         if self.freq_l1 is not None:
@@ -361,6 +362,7 @@ class TrainEngine:
     def _split_a(self, xq, xk, clean):
         """zero grads, forward, L1 loss, backward of the DECODER (incl. the lambda heads) down to the encoder's output stack."""
         self.flat_g.zero_()
+        ops.mark_zeroed(self.flat_g)                         # grouped weight gradients may store into it (ops.wgrad)
         Fn.droppath_begin(xq.device, 'airnet')
         _, logits, _, inter = self.net.E(xq, xk, True)
         stack = inter[0]._fw_stack
@@ -432,6 +434,7 @@ class TrainEngine:
     # ---- phase 1 (train.py:82-86): encoder only, contrastive loss only -------------------------------------------------
     def _fwd_bwd_p1(self, xq, xk):
         self.flat_g[:self.n_enc].zero_()
+        ops.mark_zeroed(self.flat_g[:self.n_enc])
         _, logits, _, _ = self.net.E(x_query=xq, x_key=xk)
         loss = ContrastLossFn.apply(torch.stack(logits, 0), 1.0 / self.allreduce.world)
         loss.backward()

@@ -1,6 +1,8 @@
 """Tensor-level wrappers over the C ABI (include/fwair.h).  They only allocate outputs with the PyTorch
 caching allocator, check shapes on the host and forward raw pointers; all arithmetic happens in
 libfwair_hip.so.  Activations are 2-D [tokens, channels] tensors whose row stride is their `ld`."""
+import bisect
+
 import torch
 
 from . import lfs as _lfs
@@ -24,6 +26,10 @@ def gemm(x, w, M, N, K, *, x_trans=False, w_trans=False, x_op=0, w_op=0, out=Non
     assert x.dtype == w.dtype
     if out is None:
         out = torch.empty((M, N), dtype=out_dtype or x.dtype, device=x.device)
+    if accumulate:
+        _note_write(out)
+    if xsum is not None and not xsum_zstride:
+        _note_write(xsum)
     out_f32 = int(out.dtype == torch.float32)
     call('fw_gemm', dt(x.dtype), x, _ld(x), int(x_trans), x_op, w, _ld(w), int(w_trans), w_op, out, _ld(out), out_f32,
          int(accumulate), M, N, K, float(alpha), bias, act, float(slope), aux, _ld(aux) if aux is not None else 0,
@@ -47,6 +53,92 @@ def pick_splitk(M, N, K, dtype):
     while sk > 1 and sk * M * N * 4 > (256 << 20):          # keep the partial-tile slab under 256 MB
         sk //= 2
     return int(sk)
+
+
+# ---- gradient buffers known to be zero -------------------------------------------------------------------------
+# A grouped weight gradient may STORE its tiles instead of adding them only into memory that is provably zero: the caller zeroes a
+# buffer and marks it (mark_zeroed); every write through these wrappers into a marked range -- and, after each grouped launch, every
+# range that launch wrote -- takes that range out of the marked set again.  Ranges are byte spans [lo, hi), not data_ptr()s:
+# overlapping views that start at different addresses (the fused [3C, K] QKV gradient and its [2C, K] tail) are seen as overlapping.
+_zeroed = []             # sorted, disjoint [lo, hi) spans that hold zeros and that nothing has written since they were marked
+_zeroed_bufs = {}        # data_ptr -> the marked tensors: a marked range is never handed to another tensor by the allocator
+
+
+def _span(t):
+    """[lo, hi) bytes a (strided) tensor covers, padding between its rows included."""
+    lo = t.data_ptr()
+    if t.numel() == 0:
+        return lo, lo
+    return lo, lo + t.element_size() * (1 + sum((n - 1) * st for n, st in zip(t.shape, t.stride())))
+
+
+def _clusters(spans):
+    """Union of the spans as sorted disjoint [lo, hi), and for every input span whether it overlaps another input span."""
+    order = sorted(range(len(spans)), key=lambda i: spans[i][0])
+    union, shared, first = [], [False] * len(spans), 0
+    for i in order:
+        lo, hi = spans[i]
+        if lo >= hi:
+            continue
+        if union and lo < union[-1][1]:
+            union[-1][1] = max(union[-1][1], hi)
+            shared[first] = shared[i] = True
+        else:
+            union.append([lo, hi])
+            first = i
+    return union, shared
+
+
+def mark_zeroed(t):
+    """The caller has just zeroed `t` (a contiguous gradient buffer, e.g. the engine's flat .grad) on the current stream: grouped
+    weight gradients that are the only writers of a range inside it may store instead of read-modify-write, until a write lands there."""
+    assert t.is_contiguous()
+    lo, hi = _span(t)
+    _unmark([(lo, hi)])
+    _zeroed.append((lo, hi))
+    _zeroed.sort()
+    _zeroed_bufs[lo] = t
+    for p in [p for p, b in _zeroed_bufs.items() if not any(z[0] < _span(b)[1] and _span(b)[0] < z[1] for z in _zeroed)]:
+        del _zeroed_bufs[p]
+
+
+def clear_marks():
+    """Forget every zeroed mark: from here on every grouped weight gradient adds."""
+    _zeroed.clear()
+    _zeroed_bufs.clear()
+
+
+def _unmark(spans):
+    """Take the spans out of the marked set (one sweep over both sorted lists)."""
+    if not _zeroed or not spans:
+        return
+    cut, out, j = _clusters(spans)[0], [], 0
+    for lo, hi in _zeroed:
+        while j < len(cut) and cut[j][1] <= lo:
+            j += 1
+        cur, k = lo, j
+        while k < len(cut) and cut[k][0] < hi:
+            if cut[k][0] > cur:
+                out.append((cur, cut[k][0]))
+            cur = max(cur, cut[k][1])
+            k += 1
+        if cur < hi:
+            out.append((cur, hi))
+    _zeroed[:] = out
+
+
+def _note_write(t):
+    """A kernel is about to write (add into) `t`: it no longer holds zeros."""
+    if _zeroed and t is not None:
+        lo, hi = _span(t)
+        i = bisect.bisect_left(_zeroed, (hi,))
+        if i and _zeroed[i - 1][1] > lo:
+            _unmark([(lo, hi)])
+
+
+def _is_zero(span):
+    i = bisect.bisect_right(_zeroed, (span[0], float('inf')))
+    return i > 0 and _zeroed[i - 1][0] <= span[0] and span[1] <= _zeroed[i - 1][1]
 
 
 # ---- deferred reduction of split partials -------------------------------------------------------------------
@@ -96,6 +188,8 @@ def _in_backward():
 def slab_reduce(slab, nz, n, zstride, dst, dst2=None, off2=0, n2=0, defer=False):
     """dst[0:n] += sum_z slab[z][0:n];  dst2[0:n2] += sum_z slab[z][off2:off2+n2].  With defer (the destinations are persistent
     gradient buffers, not tensors handed back to autograd) the fold waits for the end of the running backward pass."""
+    _note_write(dst)
+    _note_write(dst2)
     if not defer or not _in_backward():
         call('fw_slab_reduce', slab, nz, n, zstride, dst, 1, dst2, off2, n2 if dst2 is not None else 0)
         return
@@ -105,10 +199,15 @@ def slab_reduce(slab, nz, n, zstride, dst, dst2=None, off2=0, n2=0, defer=False)
 
 def flush_slabs():
     """End-of-backward-pass callback: the grouped weight gradients first (they queue the slabs of their sliced reductions), then ONE
-    fold of every slab of the pass."""
+    fold of every slab of the pass.  If either raises, the queues of the pass and the zeroed marks are dropped: nothing of it
+    lingers into the next pass, and no later product stores into a buffer whose content is no longer known."""
     _flush_registered[0] = None
-    _flush_wgrads()
-    _fold_slabs()
+    try:
+        _flush_wgrads()
+        _fold_slabs()
+    except BaseException:
+        _pending.clear(); _pending_w.clear(); clear_marks()
+        raise
 
 
 def _fold_slabs():
@@ -121,19 +220,21 @@ def _fold_slabs():
     host = _host_table(num * 12 + num + 1)
     tab, prefix = host[:num * 12].view(num, 12), host[num * 12:]
     rows, offs, total = [], [0], 0
-    seen = {}
-    for it in items:                                           # destinations written by more than one entry need atomics
-        for t in (it[4], it[5]):
-            if t is not None:
-                seen[t.data_ptr()] = seen.get(t.data_ptr(), 0) + 1
-    for slab, nz, n, zstride, dst, dst2, off2, n2 in items:
+    spans, owner = [], []                                      # destinations that overlap another entry's need atomics
+    for i, it in enumerate(items):
+        spans.append(_span(it[4])); owner.append(i)
+        if it[5] is not None:
+            spans.append(_span(it[5])); owner.append(i)
+    shared_item = [False] * num
+    for i, sh in zip(owner, _clusters(spans)[1]):
+        shared_item[i] |= sh
+    for (slab, nz, n, zstride, dst, dst2, off2, n2), shared in zip(items, shared_item):
         end = off2 + n2 if dst2 is not None else n
         nchunks = ((end + 3) // 4 + 63) // 64                  # 64 lanes x 16 bytes
         zper = min(nz, 64)
         splits = (nz + zper - 1) // zper
         upw = max(1, 32 // zper)                               # units per wave: >= ~32 KB moved by every wave
         blocks = (nchunks * splits + 4 * upw - 1) // (4 * upw)
-        shared = seen[dst.data_ptr()] > 1 or (dst2 is not None and seen[dst2.data_ptr()] > 1)
         unaligned = dst.data_ptr() % 16 or (dst2 is not None and dst2.data_ptr() % 16)
         rows.append((slab.data_ptr(), dst.data_ptr(), dst2.data_ptr() if dst2 is not None else 0, n, zstride, off2, n2, nz, zper,
                      nchunks, upw, int(splits > 1 or shared or bool(unaligned))))
@@ -155,18 +256,17 @@ def _fold_slabs():
 _GROUP = int(_os.environ.get('FW_WGRAD_GROUP', '1'))                # 0: one launch per product (round-2 behaviour)
 _GROUP_CHUNK = int(_os.environ.get('FW_WGRAD_CHUNK', '4096'))       # tokens per work item: longer reductions are cut into slices (sweep on MI355X: 1024: 298.6, 2048: 307.5, 4096: 305.6-308.7, 8192: 302.3, 16384: 281.3 images/s)
 _GROUP_BIG_MIN = int(_os.environ.get('FW_WGRAD_BIG_MIN', '224'))  # smallest output side that takes the 256 x 256 tile form
-_GROUP_PLAIN = int(_os.environ.get('FW_WGRAD_PLAIN', '1'))        # sole writer of a (pre-zeroed) gradient: plain store instead of accumulate
+_GROUP_PLAIN = int(_os.environ.get('FW_WGRAD_PLAIN', '1'))        # sole writer of a gradient range marked zero (mark_zeroed): plain store instead of accumulate
 _GROUP_UNIT_BX = int(_os.environ.get('FW_WGRAD_UNIT_BX', '1'))    # dY column blocks per work unit (see _launch_group)
 _pending_w = []          # (g, x, n, k, m, dw, db)
-_shared_dw = set()
-_fresh_dw = set()        # gradients the caller vouches are ZERO when the pass starts (engine mode) and that ONE product writes: plain store
+_dw_mode = {}            # _span(dw) -> epilogue of an unsliced product of the last flush: 0 plain store, 1 read-modify-write, 2 atomicAdd
 
 
 def _register_flush():
     task = torch._C._current_graph_task_id()
     if _flush_registered[0] != task:                       # a new backward pass (an earlier one may have died before its callback ran)
         if _flush_registered[0] is not None:
-            _pending.clear(); _pending_w.clear(); _fresh_dw.clear()      # work of a pass that never finished: its gradients are void anyway
+            _pending.clear(); _pending_w.clear()      # work of a pass that never finished: its gradients are void anyway
         _flush_registered[0] = task
         torch.autograd.Variable._execution_engine.queue_callback(flush_slabs)
 
@@ -185,12 +285,16 @@ def _flush_wgrads():
         return
     work = list(_pending_w)
     _pending_w.clear()
-    seen = set()
-    _shared_dw.clear()
-    for w_ in work:                                          # gradients that several products of this pass add into keep the accumulate form
-        (_shared_dw if w_[5].data_ptr() in seen else seen).add(w_[5].data_ptr())
-    _shared_dw.update(seen - _fresh_dw)                      # ... and so does everything nobody declared fresh
-    _fresh_dw.clear()
+    # A product STORES its tiles only if its dW range is marked zero and no other product of the pass writes into it.  Products
+    # whose dW ranges overlap add with atomics: their tiles run in the same launch, on different XCDs whose L2s are not coherent.
+    spans = [_span(w_[5]) for w_ in work]
+    shared = _clusters(spans)[1]
+    unsliced = [i for i, w_ in enumerate(work) if w_[4] <= _GROUP_CHUNK]
+    racing = _clusters([spans[i] for i in unsliced])[1]
+    _dw_mode.clear()
+    for i, r in zip(unsliced, racing):
+        _dw_mode[spans[i]] = 2 if r else 1 if shared[i] or not _GROUP_PLAIN or not _is_zero(spans[i]) else 0
+    _unmark(spans + [_span(w_[6]) for w_ in work if w_[6] is not None])
     # outputs of at least _GROUP_BIG_MIN rows and columns run on 256 x 256 tiles (8 waves), the others on 128 x 128 (4 waves)
     big = [w for w in work if min(w[2], w[3]) >= _GROUP_BIG_MIN]
     small = [w for w in work if min(w[2], w[3]) < _GROUP_BIG_MIN]
@@ -214,9 +318,9 @@ def _launch_group(work, tile=128):
         kper = -(-(-(-m // sk)) // 32) * 32                   # tokens per slice, whole 32-token steps
         sk = -(-m // kper)
         if sk == 1:
-            sole = dw.data_ptr() not in _shared_dw                      # fresh, and the only product of the pass that writes it
+            mode = _dw_mode.get(_span(dw), 2)                               # see _flush_wgrads; unknown: atomicAdd, right in every case
             rows.append((g.data_ptr(), x.data_ptr(), dw.data_ptr(), g.stride(0), x.stride(0), dw.stride(0), n, k, m, kper, 1,
-                         db.data_ptr() if db is not None else 0, 1 if sole else 0, 0, 0 if sole else 1, 0))   # c_zstride > 0 selects the plain-store tile
+                         db.data_ptr() if db is not None else 0, 1 if mode == 0 else 0, 0, mode, 0))   # c_zstride > 0 selects the plain-store tile
         else:
             nk = (n * k + 3) // 4 * 4
             S = nk + (n + 3) // 4 * 4
@@ -263,19 +367,19 @@ def _launch_group(work, tile=128):
     # `work` (the operands) dies here: the allocator reuses them stream-ordered, i.e. after the kernel above
 
 
-def wgrad(g, x, n, k, m, dw, db=None, defer=False, fresh=False):
+def wgrad(g, x, n, k, m, dw, db=None, defer=False):
     """dw[n][k] += sum_m g[m][n] x[m][k];  db[n] += sum_m g[m][n].  With defer (dw / db are persistent gradient buffers nobody reads
     before the optimizer step) inside a backward pass the product is QUEUED and runs in the pass's grouped launch (_flush_wgrads).
-    fresh: the caller vouches that dw / db are ZERO when the pass starts (the engine's flat gradient buffer): if this is the only queued
-    product of the pass that writes them, its tiles are STORED instead of read-modified-written.
+    A queued product always ADDS, with one exception: when dw lies in a range marked zero (mark_zeroed) that nothing has written
+    since, and no other write of the pass -- queued or immediate -- touches that range, its tiles are STORED.
     Otherwise: large reductions are split over K into a slab of partial tiles (plain stores) that a slab reduce folds -- no
     same-address atomics."""
     if defer and _in_backward() and _groupable(g, x, n, k, m, dw, db):
         _register_flush()
         _pending_w.append((g, x, n, k, m, dw, db))
-        if fresh and _GROUP_PLAIN:
-            _fresh_dw.add(dw.data_ptr())
         return
+    _note_write(dw)
+    _note_write(db)
     sk = pick_splitk(n, k, m, g.dtype)
     if sk == 1:
         gemm(g, x, n, k, m, x_trans=True, w_trans=True, out=dw, accumulate=True, xsum=db)
@@ -354,6 +458,8 @@ def attn_bwd(qkv, out, dout, lse, C, B, H, W, heads, L, mode, shift, bias, dbias
     nkt = 1 if mode == 0 else L - 1
     dqkv = torch.empty_like(qkv)
     d2 = torch.empty_like(qkv) if nkt == 2 else None          # second key-gradient slot, same layout as dqkv
+    _note_write(dbias_dense)
+    _note_write(dcoef)
     tab = _lfs.device_table(qkv.dtype, qkv.device) if lfs == 2 else None
     call('fw_attn_bwd', dt(qkv.dtype), D, nkt, lfs, qkv, qkv[:, C:], qkv[:, 2 * C:], _ld(qkv), out, _ld(out), dout, _ld(dout),
          lse, bias, coef, tab, dqkv, dqkv[:, C:], dqkv[:, 2 * C:], d2[:, C:] if d2 is not None else None,
@@ -386,6 +492,8 @@ def dwconv_fwd(src, w, bias, B, H, W, in_gelu=False):
 def dwconv_bwd(dh2, g1, h1, w, dw, dbias, B, H, W):
     """g1 may be None: the weight gradient then evaluates GELU(h1) itself."""
     dh1 = torch.empty_like(h1)
+    _note_write(dw)
+    _note_write(dbias)
     call('fw_dwconv_bwd', dt(h1.dtype), dh2, _ld(dh2), g1, h1, _ld(h1), w, dh1, _ld(dh1), dw, dbias, B, H, W, h1.shape[1])
     return dh1
 
@@ -416,6 +524,7 @@ def pixel_unshuffle(dout, B, H, W, Cout, dtype):
 
 
 def colsum(x, out):
+    _note_write(out)
     call('fw_colsum', 1 if x.dtype == torch.bfloat16 else 0, x, _ld(x), out, x.shape[0], x.shape[1])
 
 
@@ -426,11 +535,15 @@ def cast_rows(src, dtype, rowscale=None, rows_per_scale=1):
 
 
 def copy_rows(src, dst, accumulate=False):
+    if accumulate:
+        _note_write(dst)
     call('fw_copy_rows', src, _ld(src), dst, _ld(dst), src.shape[0], src.shape[1], int(accumulate))
 
 
 def permute3(src, dst, dims, out_strides, accumulate=False):
     ind = 1 if src.dtype == torch.bfloat16 else 0
     outd = 1 if dst.dtype == torch.bfloat16 else 0
+    if accumulate:
+        _note_write(dst)
     call('fw_permute3', ind, outd, src, dst, dims[0], dims[1], dims[2], out_strides[0], out_strides[1], out_strides[2],
          int(accumulate))
