@@ -13,7 +13,8 @@
 // lanes), so that the C/D layout's 4-consecutive-rows-per-lane is written back to LDS with one 8/16-byte store as the
 // k-contiguous operand of the next product, and V / dO / Q / K are read along their token axis with ds_read_b64_tr_b16.
 // Dropout masks are counter-based (fw_common.h: fw_keep): the backward pass re-derives them, nothing is stored.
-// The band re-weighting (N = 64 only: the reference sizes its masks dim_head x dim_head, encoder_ViT.py:56,60) is a full 64x64
+// The band re-weighting at N = 64 (the reference sizes its masks dim_head x dim_head, encoder_ViT.py:56,60; N = 256 with N x N masks:
+// the V_* variants and the bands_* passes further down) is a full 64x64
 // 2-D DFT on the f32 MFMA (exact f32 products): A' = A + Re F^-1( W . F(A) ), W[u][v] = lamb[band(u, v)], with the cos / sin
 // panels read as ready-made fragments from L2; it is self-adjoint (real radial W), so the backward pass runs the same routine on
 // the incoming gradient and gets d(lamb) from the two spectra.
@@ -40,6 +41,10 @@ struct GAttnArgs {
     float* dvec;                                                // [B][heads][N] rowsum(dO . O)
     char* dq; char* dk; char* dv; long ldd;
     float* dlamb;                                               // same layout as lamb, accumulated with atomics
+    // N = 256 with <n>_bands on the N x N grid: the map leaves the workgroup (f32 [B][heads][N][N])
+    float* map;                                                 // fwd: P, then A' = P + filter(P);  bwd: the saved A'
+    float* map2;                                                // bwd: G = dropout'(dO V^T), then dA = G + filter(G)
+    float* pmap;                                                // bwd: P rebuilt from lse (the spectrum of P gives d lamb)
 };
 
 constexpr int NTH = 256;
@@ -193,9 +198,23 @@ FW_DEV void lamb_weights(const GAttnArgs& a, int b, int h, f32x4 (&wv)[4]) {
         }
 }
 
+// 'DC' with N x N masks at N = 256 (band 0 = the bin (0, 0), band 1 = the rest) needs no transform: every softmax row sums to 1,
+// so the mean of the map is exactly 1 / N and  A' = A + lamb0 mean + lamb1 (A - mean) = (1 + lamb1) A + (lamb0 - lamb1) / N.
+FW_DEV void dc_coef(const GAttnArgs& a, int b, int h, float& gain, float& offs) {
+    const float* lam = a.lamb + (long)(a.lamb_batch > 1 ? b : 0) * a.heads + h;
+    const float l0 = lam[0], l1 = lam[(long)a.lamb_batch * a.heads];
+    gain = 1.0f + l1;
+    offs = (l0 - l1) / (float)a.N;
+}
+
 // ================================================================================================================ forward
-template <typename T, int NT, bool LAMB>
-__global__ __launch_bounds__(NTH) void gattn_fwd_kernel(GAttnArgs a) {
+// Variants at N = 256 (NT = 4) with N x N band masks; the kernels below wrap this body.
+//   V_DC: the affine form above.   <n>_bands: the 256x256 map does not fit a workgroup, so the filter runs between two launches:
+//   V_PROBS writes the softmax strip P (f32) and lse and stops; V_APPLY reads A' = P + filter(P) back, applies Dropout, and does A'' V.
+enum { V_NONE = 0, V_DC = 1, V_PROBS = 2, V_APPLY = 3, V_MAPS = 4 };
+template <typename T, int NT, bool LAMB, int VAR>
+FW_DEV void gattn_fwd_body(const GAttnArgs& a) {
+    constexpr bool DC = VAR == V_DC;
     using G = GG<T>;
     constexpr int SZ = G::SZ, LDR = G::LDR, KC = G::KC, N = 64 * NT, MT = N / 16;
     constexpr int LDP = N * SZ + 16, JC = N * SZ / 64;
@@ -209,13 +228,21 @@ __global__ __launch_bounds__(NTH) void gattn_fwd_kernel(GAttnArgs a) {
     const int qt = item % NT; item /= NT;
     const int h = item % a.heads, b = item / a.heads;
     const long ldb = a.ld * SZ;
-    load_tile<T, 64>(Qs, a.q + ((long)(b * N + qt * 64) * a.ld + h * 64) * SZ, ldb);
-    load_tile<T, N>(Ks, a.k + ((long)b * N * a.ld + h * 64) * SZ, ldb);
-    load_tile<T, N>(Vs, a.v + ((long)b * N * a.ld + h * 64) * SZ, ldb);
+    if constexpr (VAR != V_APPLY) {
+        load_tile<T, 64>(Qs, a.q + ((long)(b * N + qt * 64) * a.ld + h * 64) * SZ, ldb);
+        load_tile<T, N>(Ks, a.k + ((long)b * N * a.ld + h * 64) * SZ, ldb);
+    }
+    if constexpr (VAR != V_PROBS) load_tile<T, N>(Vs, a.v + ((long)b * N * a.ld + h * 64) * SZ, ldb);
     __syncthreads();
     // S^T strip: s[mt][r] = score(query 16 w + (l & 15), key 16 mt + 4 (l >> 4) + r)
     f32x4 s[MT];
-    {
+    const int iq = qt * 64 + 16 * w + (l & 15);                        // the lane's query
+    float* maprow = nullptr;                                           // the lane's 4-key groups of the f32 map
+    if constexpr (VAR == V_PROBS || VAR == V_APPLY) maprow = a.map + ((long)(b * a.heads + h) * N + iq) * N + 4 * (l >> 4);
+    if constexpr (VAR == V_APPLY) {
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) s[mt] = *reinterpret_cast<const f32x4*>(maprow + 16 * mt);
+    } else {
         uint4 qf[KC];
 #pragma unroll
         for (int c = 0; c < KC; ++c) qf[c] = frag_kc(Qs, LDR, 16 * w, c);
@@ -225,7 +252,6 @@ __global__ __launch_bounds__(NTH) void gattn_fwd_kernel(GAttnArgs a) {
 #pragma unroll
             for (int c = 0; c < KC; ++c) mma_chunk<T>(s[mt], frag_kc(Ks, LDR, 16 * mt, c), qf[c]);
         }
-    }
     float mx = -3.0e38f;
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt)
@@ -241,14 +267,25 @@ __global__ __launch_bounds__(NTH) void gattn_fwd_kernel(GAttnArgs a) {
     const float inv = 1.0f / sum;
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt) s[mt] *= inv;
-    const int iq = qt * 64 + 16 * w + (l & 15);                        // the lane's query
     if ((l >> 4) == 0) a.lse[(long)(b * a.heads + h) * N + iq] = mx + __logf(sum);
+    }
+    if constexpr (VAR == V_PROBS) {
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) *reinterpret_cast<f32x4*>(maprow + 16 * mt) = s[mt];
+        return;
+    }
     if constexpr (LAMB) {
         f32x4 wv[4], fo[4], xr[4], xi[4];
         lamb_weights(a, b, h, wv);
         spectral_filter(s, fo, wv, xr, xi, arena, a.panels, a.panels + 4096);
 #pragma unroll
         for (int mt = 0; mt < 4; ++mt) s[mt] += fo[mt];
+    }
+    if constexpr (DC) {
+        float gain, offs;
+        dc_coef(a, b, h, gain, offs);
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt) s[mt] = s[mt] * gain + offs;
     }
     if (a.thresh) {
         const unsigned key = fw_site_key(a.seed[0], a.site);
@@ -280,6 +317,14 @@ __global__ __launch_bounds__(NTH) void gattn_fwd_kernel(GAttnArgs a) {
     wave_fence();
     store_rows16<T>(Os, a.out + ((long)(b * N + qt * 64 + 16 * w) * a.ldo + h * 64) * SZ, a.ldo * SZ);
 }
+template <typename T, int NT, bool LAMB>
+__global__ __launch_bounds__(NTH) void gattn_fwd_kernel(GAttnArgs a) { gattn_fwd_body<T, NT, LAMB, V_NONE>(a); }
+template <typename T>
+__global__ __launch_bounds__(NTH) void gattn_dc_fwd_kernel(GAttnArgs a) { gattn_fwd_body<T, 4, false, V_DC>(a); }
+template <typename T>
+__global__ __launch_bounds__(NTH) void gattn_probs_kernel(GAttnArgs a) { gattn_fwd_body<T, 4, false, V_PROBS>(a); }
+template <typename T>
+__global__ __launch_bounds__(NTH) void gattn_apply_kernel(GAttnArgs a) { gattn_fwd_body<T, 4, false, V_APPLY>(a); }
 
 // ================================================================================================================ backward
 // dvec[b][h][i] = sum_d dO[i][d] O[i][d]
@@ -308,9 +353,14 @@ __global__ void gattn_dvec_kernel(GAttnArgs a) {
 // One (query tile, key tile) pair: from the LDS tiles Qs / dOs (queries) and Ks / Vs (keys) to the strips
 //   p2[mt][r] = P''^T  (what multiplies V: after re-weighting and dropout)      ds[mt][r] = scale * dS^T
 // rows = key 16 mt + 4 (l >> 4) + r of the key tile, column = query 16 w + (l & 15) of the query tile.
-template <typename T, int NT, bool LAMB>
+// DC (N = 256, dc_coef): p2 = gain P + offs; the constant drops out of the softmax gradient (rowsum(P) = 1), so
+// ds = scale gain P (G - rowsum(P G)) with G = dropout'(dO V^T) and rowsum(P G) in dvec (gattn_dc_rows_kernel).
+// MAPS (N = 256, <n>_bands): the filter ran between launches; p2 = dropout(A') from the saved map, dP = G + filter(G) from map2
+// (Dropout' is already inside G), rowsum(P dP) in dvec (gattn_rowdot_kernel).
+template <typename T, int NT, bool LAMB, int VAR = V_NONE>
 FW_DEV void pair_grads(const GAttnArgs& a, int b, int h, int qi, int kj, const char* Qs, const char* dOs, const char* Ks, const char* Vs,
                        char* arena, f32x4 (&p2)[4], f32x4 (&ds)[4]) {
+    constexpr bool DC = VAR == V_DC, MAPS = VAR == V_MAPS;
     using G = GG<T>;
     constexpr int LDR = G::LDR, KC = G::KC, N = 64 * NT;
     const int w = wave_id(), l = lane_id();
@@ -343,6 +393,15 @@ FW_DEV void pair_grads(const GAttnArgs& a, int b, int h, int qi, int kj, const c
         spectral_filter(p, fo, wv, xr, xi, arena, a.panels, a.panels + 4096);
 #pragma unroll
         for (int mt = 0; mt < 4; ++mt) p2[mt] = p[mt] + fo[mt];
+    } else if constexpr (DC) {
+        float gain, offs;
+        dc_coef(a, b, h, gain, offs);
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt) { p2[mt] = p[mt] * gain + offs; p[mt] *= gain; }         // p enters ds only: gain P (G - rowsum(P G))
+    } else if constexpr (MAPS) {
+        const long off = rowid * N + kj * 64 + 4 * (l >> 4);
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt) p2[mt] = *reinterpret_cast<const f32x4*>(a.map + off + 16 * mt);
     } else {
 #pragma unroll
         for (int mt = 0; mt < 4; ++mt) p2[mt] = p[mt];
@@ -358,6 +417,11 @@ FW_DEV void pair_grads(const GAttnArgs& a, int b, int h, int qi, int kj, const c
                 p2[mt][r] = keep ? p2[mt][r] * a.inv_keep : 0.f;
                 dp[mt][r] = keep ? dp[mt][r] * a.inv_keep : 0.f;
             }
+    }
+    if constexpr (MAPS) {                                             // replaces the product above (the compiler drops it)
+        const long off = rowid * N + kj * 64 + 4 * (l >> 4);
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt) dp[mt] = *reinterpret_cast<const f32x4*>(a.map2 + off + 16 * mt);
     }
     float dsum;
     if constexpr (LAMB) {
@@ -392,11 +456,12 @@ FW_DEV void pair_grads(const GAttnArgs& a, int b, int h, int qi, int kj, const c
         for (int r = 0; r < 4; ++r) ds[mt][r] = p[mt][r] * (dp[mt][r] - dsum) * a.scale;
 }
 
-template <typename T, int NT, bool LAMB>
-__global__ __launch_bounds__(NTH) void gattn_bwd_kernel(GAttnArgs a) {
+template <typename T, int NT, bool LAMB, int DC>                        // DC: V_NONE | V_DC | V_MAPS, handed to pair_grads
+FW_DEV void gattn_bwd_body(const GAttnArgs& a) {
     using G = GG<T>;
     constexpr int SZ = G::SZ, LDR = G::LDR, KC = G::KC, N = 64 * NT, TILE = G::TILE;
-    static_assert(!LAMB || NT == 1, "the band re-weighting is defined for N = 64 only");
+    static_assert(!LAMB || NT == 1, "the 64x64 transform is defined for N = 64 only");
+    static_assert(DC == V_NONE || (NT == 4 && !LAMB), "the N x N band grid has kernels at N = 256 only");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* Qs = smem;
     char* dOs = Qs + TILE;
@@ -423,7 +488,7 @@ __global__ __launch_bounds__(NTH) void gattn_bwd_kernel(GAttnArgs a) {
         load_tile<T, 64>(Ks, rows(a.k, ldb, kj), ldb);
         load_tile<T, 64>(Vs, rows(a.v, ldb, kj), ldb);
         __syncthreads();
-        pair_grads<T, NT, LAMB>(a, b, h, t, kj, Qs, dOs, Ks, Vs, arena, p2, ds);
+        pair_grads<T, NT, LAMB, DC>(a, b, h, t, kj, Qs, dOs, Ks, Vs, arena, p2, ds);
         char* myS = dSs + 16 * w * LDR;
 #pragma unroll
         for (int mt = 0; mt < 4; ++mt) store_acc_T<T>(myS, LDR, 16 * mt, 0, ds[mt]);             // dSs[i][j], j contiguous
@@ -482,7 +547,7 @@ __global__ __launch_bounds__(NTH) void gattn_bwd_kernel(GAttnArgs a) {
             load_tile<T, 64>(Qs, rows(a.q, ldb, qi), ldb);
             load_tile<T, 64>(dOs, rows(a.dout, lddob, qi), lddob);
             __syncthreads();
-            pair_grads<T, NT, LAMB>(a, b, h, qi, t, Qs, dOs, Ks, Vs, arena, p2, ds);
+            pair_grads<T, NT, LAMB, DC>(a, b, h, qi, t, Qs, dOs, Ks, Vs, arena, p2, ds);
 #pragma unroll
             for (int mt = 0; mt < 4; ++mt) {
                 store_acc_T<T>(Ps + 16 * w * LDR, LDR, 16 * mt, 0, p2[mt]);
@@ -510,6 +575,82 @@ __global__ __launch_bounds__(NTH) void gattn_bwd_kernel(GAttnArgs a) {
         store_rows16<T>(Vs + 16 * w * LDR, const_cast<char*>(rows(a.dv, lddb, t)) + (long)16 * w * lddb, lddb);
     }
 }
+template <typename T, int NT, bool LAMB>
+__global__ __launch_bounds__(NTH) void gattn_bwd_kernel(GAttnArgs a) { gattn_bwd_body<T, NT, LAMB, V_NONE>(a); }
+template <typename T>
+__global__ __launch_bounds__(NTH) void gattn_dc_bwd_kernel(GAttnArgs a) { gattn_bwd_body<T, 4, false, V_DC>(a); }
+template <typename T>
+__global__ __launch_bounds__(NTH) void gattn_maps_bwd_kernel(GAttnArgs a) { gattn_bwd_body<T, 4, false, V_MAPS>(a); }
+
+// 'DC' at N = 256, ahead of gattn_dc_bwd_kernel: one workgroup per (image, head, 64-query tile) walks all keys and leaves
+//   dvec[i] = sum_j P[i][j] G[i][j],  G = dropout'(dO V^T);     d lamb0 += sum(G) / N;     d lamb1 += sum(G . P) - sum(G) / N
+// MAPS (<n>_bands): the same walk writes P -> pmap and G -> map2 (f32) for the filter passes instead of reducing them
+template <typename T, bool MAPS>
+__global__ __launch_bounds__(NTH) void gattn_dc_rows_kernel(GAttnArgs a) {
+    using G = GG<T>;
+    constexpr int SZ = G::SZ, LDR = G::LDR, KC = G::KC, N = 256, TILE = G::TILE;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    char* Qs = smem;
+    char* dOs = Qs + TILE;
+    char* Ks = dOs + TILE;
+    char* Vs = Ks + TILE;
+    const int w = wave_id(), l = lane_id();
+    int item = blockIdx.x;
+    const int t = item % 4; item /= 4;
+    const int h = item % a.heads, b = item / a.heads;
+    const long ldb = a.ld * SZ, lddob = a.lddo * SZ;
+    const long col = (long)h * 64 * SZ;
+    auto rows = [&](const char* base, long ldbytes, int tile) { return base + (long)(b * N + tile * 64) * ldbytes + col; };
+    load_tile<T, 64>(Qs, rows(a.q, ldb, t), ldb);
+    load_tile<T, 64>(dOs, rows(a.dout, lddob, t), lddob);
+    const long rowid = (long)(b * a.heads + h) * N + t * 64 + 16 * w + (l & 15);
+    const float lse = a.lse[rowid];
+    const unsigned key = a.thresh ? fw_site_key(a.seed[0], a.site) : 0u;
+    float spg = 0.f, sg = 0.f;
+    for (int kj = 0; kj < 4; ++kj) {
+        load_tile<T, 64>(Ks, rows(a.k, ldb, kj), ldb);
+        load_tile<T, 64>(Vs, rows(a.v, ldb, kj), ldb);
+        __syncthreads();
+        uint4 qf[KC], df[KC];
+#pragma unroll
+        for (int c = 0; c < KC; ++c) { qf[c] = frag_kc(Qs, LDR, 16 * w, c); df[c] = frag_kc(dOs, LDR, 16 * w, c); }
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt) {
+            f32x4 p = zero4(), dp = zero4();
+#pragma unroll
+            for (int c = 0; c < KC; ++c) {
+                mma_chunk<T>(p, frag_kc(Ks, LDR, 16 * mt, c), qf[c]);
+                mma_chunk<T>(dp, frag_kc(Vs, LDR, 16 * mt, c), df[c]);
+            }
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                float g = dp[r];
+                if (a.thresh)
+                    g = fw_keep(key, (unsigned long long)rowid * N + kj * 64 + 16 * mt + 4 * (l >> 4) + r, a.thresh) ? g * a.inv_keep : 0.f;
+                p[r] = __expf(p[r] * a.scale - lse);
+                dp[r] = g;
+                spg += p[r] * g;
+                sg += g;
+            }
+            if constexpr (MAPS) {
+                const long off = rowid * N + kj * 64 + 16 * mt + 4 * (l >> 4);
+                *reinterpret_cast<f32x4*>(a.pmap + off) = p;
+                *reinterpret_cast<f32x4*>(a.map2 + off) = dp;
+            }
+        }
+        __syncthreads();
+    }
+    if constexpr (MAPS) return;
+    spg = col_sum(spg); sg = col_sum(sg);                              // every lane of a query now holds its row sums
+    const bool own = (l >> 4) == 0;
+    if (own) a.dvec[rowid] = spg;
+    const float tpg = wave_sum(own ? spg : 0.f), tg = wave_sum(own ? sg : 0.f);
+    if (l == 0) {
+        float* dl = a.dlamb + (long)(a.lamb_batch > 1 ? b : 0) * a.heads + h;
+        atomicAdd(dl, tg * (1.0f / N));
+        atomicAdd(dl + (long)a.lamb_batch * a.heads, tpg - tg * (1.0f / N));
+    }
+}
 
 template <typename T> static size_t fwd_lds(int NT, bool lamb) {
     return (size_t)(64 + 2 * 64 * NT) * GG<T>::LDR + (lamb ? 4 * SLOT : 0);
@@ -530,23 +671,305 @@ template <typename T, int NT, bool LAMB> static void launch_bwd(const GAttnArgs&
     FW_SET_LDS_ONCE((gattn_bwd_kernel<T, NT, LAMB>), lds);
     hipLaunchKernelGGL((gattn_bwd_kernel<T, NT, LAMB>), dim3(a.B * a.heads * NT), dim3(NTH), lds, st, a);
 }
+// 'DC' at N = 256: the flash-form kernels with the affine re-weighting, no tables and no scratch
+template <typename T> static void launch_dc_fwd(const GAttnArgs& a, hipStream_t st) {
+    const size_t lds = fwd_lds<T>(4, false);
+    FW_SET_LDS_ONCE((gattn_dc_fwd_kernel<T>), lds);
+    hipLaunchKernelGGL((gattn_dc_fwd_kernel<T>), dim3(a.B * a.heads * 4), dim3(NTH), lds, st, a);
+}
+template <typename T> static void launch_dc_bwd(const GAttnArgs& a, hipStream_t st) {
+    const size_t lds_rows = (size_t)4 * GG<T>::TILE, lds = bwd_lds<T>(false);
+    FW_SET_LDS_ONCE((gattn_dc_rows_kernel<T, false>), lds_rows);
+    hipLaunchKernelGGL((gattn_dc_rows_kernel<T, false>), dim3(a.B * a.heads * 4), dim3(NTH), lds_rows, st, a);
+    FW_SET_LDS_ONCE((gattn_dc_bwd_kernel<T>), lds);
+    hipLaunchKernelGGL((gattn_dc_bwd_kernel<T>), dim3(a.B * a.heads * 4), dim3(NTH), lds, st, a);
+}
+
+// ================================================================================ <n>_bands on the 256x256 map: the filter passes
+// map += Re IDFT2( W . DFT2(map) ), W[u][v] = lamb[band(u, v)], batched over maps = B * heads, all products on the f32 MFMA with the
+// cos / sin panels ([2][256][256] f32, L2-resident) read as ready-made fragments.  One map is 256 KiB of f32, more than a CU's LDS:
+//   row pass  (map, 64 rows i):        T[i][v] = sum_j A[i][j] (C - iS)[j][v]              -> work, stored transposed Tt[v][i]
+//   col pass  (map, 32 columns v):     X = (C - iS) T,  Y = W . X,  Z = (C + iS) Y          -> work in place, Zt[v][i]
+//                                      (backward: the same strip of the spectrum of P gives d lamb[band] = sum Re(X_P conj X_G) / N^2)
+//   out pass  (map, 64 rows i):        map[i][j] += Re sum_v Z[i][v] (C + iS)[v][j] / N^2
+// A wave owns a 64 x 64 (row, out) or 64 x 32 (col) block of the result: 4 panel fragments feed 16 / 8 MFMA tiles.
+constexpr int LDA = 256 * 4 + 16;                    // byte stride of an LDS tile [rows][256] f32
+constexpr int LDZ = 64 * 4 + 16;                     // byte stride of an LDS tile [256][64] f32 (read k-major)
+constexpr long PLANE = 65536;                        // floats in one 256x256 plane
+FW_DEV uint4 pfrag(const float* P, int row0, int c) {           // fragment of a global f32 [256][256] panel: rows row0.., k-chunk c
+    const int l = lane_id();
+    return *reinterpret_cast<const uint4*>(P + (row0 + (l & 15)) * 256 + c * 16 + ((l >> 4) << 2));
+}
+FW_DEV uint4 neg4(const uint4& v) { return make_uint4(v.x ^ 0x80000000u, v.y ^ 0x80000000u, v.z ^ 0x80000000u, v.w ^ 0x80000000u); }
+
+__global__ __launch_bounds__(NTH) void bands_row_kernel(const float* __restrict__ map, float* __restrict__ work, const float* __restrict__ panels) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int w = wave_id(), l = lane_id();
+    const int m = blockIdx.x >> 2, i0 = (blockIdx.x & 3) * 64;
+    const float* A = map + ((long)m * 256 + i0) * 256;
+#pragma unroll
+    for (int it = 0; it < 16; ++it) {
+        const int idx = threadIdx.x + it * NTH, r = idx >> 6, s = idx & 63;
+        *reinterpret_cast<uint4*>(smem + r * LDA + s * 16) = *reinterpret_cast<const uint4*>(A + r * 256 + s * 4);
+    }
+    __syncthreads();
+    const float* Cg = panels;
+    const float* Sg = panels + PLANE;
+    const int v0 = 64 * w;
+    f32x4 tr[4][4], ti[4][4];
+    zero_acc(tr); zero_acc(ti);
+    for (int c = 0; c < 16; ++c) {                                     // acc(m = i, n = v) = sum_j A[i][j] panel[v][j]
+        uint4 af[4];
+#pragma unroll
+        for (int mi = 0; mi < 4; ++mi) af[mi] = frag_kc(smem, LDA, 16 * mi, c);
+#pragma unroll
+        for (int ni = 0; ni < 4; ++ni) {
+            const uint4 cf = pfrag(Cg, v0 + 16 * ni, c), sf = pfrag(Sg, v0 + 16 * ni, c);
+#pragma unroll
+            for (int mi = 0; mi < 4; ++mi) { mma_chunk<float>(tr[mi][ni], af[mi], cf); mma_chunk<float>(ti[mi][ni], af[mi], sf); }
+        }
+    }
+    float* Tr = work + (long)m * 2 * PLANE;
+#pragma unroll
+    for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+        for (int ni = 0; ni < 4; ++ni) {
+            const long o = (long)(v0 + 16 * ni + (l & 15)) * 256 + i0 + 16 * mi + 4 * (l >> 4);
+            *reinterpret_cast<f32x4*>(Tr + o) = tr[mi][ni];
+            *reinterpret_cast<f32x4*>(Tr + PLANE + o) = -ti[mi][ni];
+        }
+}
+
+// (xr + i xi)[u][v] = sum_k (C -/+ iS)[u][k] (R + iI)[k][v] for u = u0 .. u0 + 63 and the strip's 32 v; Rs / Is: LDS [32 v][256 k]
+template <bool CONJ>
+FW_DEV void col_dft(const char* Rs, const char* Is, const float* Cg, const float* Sg, int u0, f32x4 (&xr)[4][2], f32x4 (&xi)[4][2]) {
+    zero_acc(xr); zero_acc(xi);
+    for (int c = 0; c < 16; ++c) {
+        uint4 br[2], bi[2];
+#pragma unroll
+        for (int ni = 0; ni < 2; ++ni) { br[ni] = frag_kc(Rs, LDA, 16 * ni, c); bi[ni] = frag_kc(Is, LDA, 16 * ni, c); }
+#pragma unroll
+        for (int mi = 0; mi < 4; ++mi) {
+            const uint4 cf = pfrag(Cg, u0 + 16 * mi, c), sf = pfrag(Sg, u0 + 16 * mi, c), nsf = neg4(sf);
+#pragma unroll
+            for (int ni = 0; ni < 2; ++ni) {
+                mma_chunk<float>(xr[mi][ni], cf, br[ni]); mma_chunk<float>(xr[mi][ni], CONJ ? nsf : sf, bi[ni]);
+                mma_chunk<float>(xi[mi][ni], cf, bi[ni]); mma_chunk<float>(xi[mi][ni], CONJ ? sf : nsf, br[ni]);
+            }
+        }
+    }
+}
+
+template <bool DL>
+__global__ __launch_bounds__(NTH) void bands_col_kernel(float* __restrict__ work, const float* __restrict__ pwork, const float* __restrict__ panels,
+                                                        const unsigned char* __restrict__ bandidx, const float* __restrict__ lamb,
+                                                        float* __restrict__ dlamb, int nb, int lb, int heads) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    __shared__ float lw[16];
+    __shared__ float red[4][16];
+    char* Trs = smem;
+    char* Tis = Trs + 32 * LDA;
+    char* Prs = Tis + 32 * LDA;                                        // DL only
+    char* Pis = Prs + 32 * LDA;
+    const int w = wave_id(), l = lane_id();
+    const int m = blockIdx.x >> 3, v0 = (blockIdx.x & 7) * 32;
+    const int h = m % heads, bsel = lb > 1 ? m / heads : 0;
+    if (threadIdx.x < nb) lw[threadIdx.x] = lamb[((long)threadIdx.x * lb + bsel) * heads + h];
+    float* Tg = work + (long)m * 2 * PLANE + (long)v0 * 256;           // rows v0 .. v0 + 31 of Tt (re), + PLANE: im
+    const float* Pg = DL ? pwork + (long)m * 2 * PLANE + (long)v0 * 256 : nullptr;
+#pragma unroll
+    for (int it = 0; it < 8; ++it) {
+        const int idx = threadIdx.x + it * NTH, r = idx >> 6, s = idx & 63;
+        *reinterpret_cast<uint4*>(Trs + r * LDA + s * 16) = *reinterpret_cast<const uint4*>(Tg + r * 256 + s * 4);
+        *reinterpret_cast<uint4*>(Tis + r * LDA + s * 16) = *reinterpret_cast<const uint4*>(Tg + PLANE + r * 256 + s * 4);
+        if constexpr (DL) {
+            *reinterpret_cast<uint4*>(Prs + r * LDA + s * 16) = *reinterpret_cast<const uint4*>(Pg + r * 256 + s * 4);
+            *reinterpret_cast<uint4*>(Pis + r * LDA + s * 16) = *reinterpret_cast<const uint4*>(Pg + PLANE + r * 256 + s * 4);
+        }
+    }
+    __syncthreads();
+    const float* Cg = panels;
+    const float* Sg = panels + PLANE;
+    const int u0 = 64 * w;
+    f32x4 xr[4][2], xi[4][2];
+    col_dft<false>(Trs, Tis, Cg, Sg, u0, xr, xi);
+    unsigned idx4[4][2];                                               // bands of the lane's bins (u .. u + 3, v); the index is symmetric
+#pragma unroll
+    for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+        for (int ni = 0; ni < 2; ++ni)
+            idx4[mi][ni] = *reinterpret_cast<const unsigned*>(bandidx + (v0 + 16 * ni + (l & 15)) * 256 + u0 + 16 * mi + 4 * (l >> 4));
+    if constexpr (DL) {
+        f32x4 pr[4][2], pi[4][2];
+        col_dft<false>(Prs, Pis, Cg, Sg, u0, pr, pi);
+        for (int band = 0; band < nb; ++band) {
+            float acc = 0.f;
+#pragma unroll
+            for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+                for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+                        if (((idx4[mi][ni] >> (8 * r)) & 255u) == (unsigned)band) acc += pr[mi][ni][r] * xr[mi][ni][r] + pi[mi][ni][r] * xi[mi][ni][r];
+            acc = wave_sum(acc);
+            if (l == 0) red[w][band] = acc;
+        }
+    }
+#pragma unroll
+    for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+        for (int ni = 0; ni < 2; ++ni)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float wgt = lw[(idx4[mi][ni] >> (8 * r)) & 255u];
+                xr[mi][ni][r] *= wgt; xi[mi][ni][r] *= wgt;
+            }
+    __syncthreads();                                                   // every wave has read T: its space takes Yt[v][u]
+    if constexpr (DL) {
+        if (threadIdx.x < nb) {
+            const int band = threadIdx.x;
+            atomicAdd(dlamb + ((long)band * lb + bsel) * heads + h, (red[0][band] + red[1][band] + red[2][band] + red[3][band]) * (1.0f / 65536.0f));
+        }
+    }
+#pragma unroll
+    for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+        for (int ni = 0; ni < 2; ++ni) {
+            store_acc_T<float>(Trs, LDA, u0 + 16 * mi, 16 * ni, xr[mi][ni]);
+            store_acc_T<float>(Tis, LDA, u0 + 16 * mi, 16 * ni, xi[mi][ni]);
+        }
+    __syncthreads();
+    col_dft<true>(Trs, Tis, Cg, Sg, u0, xr, xi);                       // rows i = u0 .. u0 + 63 of Z
+#pragma unroll
+    for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+        for (int ni = 0; ni < 2; ++ni) {
+            const long o = (long)(16 * ni + (l & 15)) * 256 + u0 + 16 * mi + 4 * (l >> 4);
+            *reinterpret_cast<f32x4*>(Tg + o) = xr[mi][ni];
+            *reinterpret_cast<f32x4*>(Tg + PLANE + o) = xi[mi][ni];
+        }
+}
+
+__global__ __launch_bounds__(NTH) void bands_out_kernel(float* __restrict__ map, const float* __restrict__ work, const float* __restrict__ panels) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    char* Zrs = smem;
+    char* Zis = smem + 256 * LDZ;
+    const int w = wave_id(), l = lane_id();
+    const int m = blockIdx.x >> 2, i0 = (blockIdx.x & 3) * 64;
+    const float* Zg = work + (long)m * 2 * PLANE + i0;                 // Zt[v][i0 ..]
+#pragma unroll
+    for (int it = 0; it < 16; ++it) {
+        const int idx = threadIdx.x + it * NTH, r = idx >> 4, s = idx & 15;
+        *reinterpret_cast<uint4*>(Zrs + r * LDZ + s * 16) = *reinterpret_cast<const uint4*>(Zg + r * 256 + s * 4);
+        *reinterpret_cast<uint4*>(Zis + r * LDZ + s * 16) = *reinterpret_cast<const uint4*>(Zg + PLANE + r * 256 + s * 4);
+    }
+    __syncthreads();
+    const float* Cg = panels;
+    const float* Sg = panels + PLANE;
+    const int j0 = 64 * w;
+    f32x4 o[4][4];
+    zero_acc(o);
+    for (int c = 0; c < 16; ++c) {                                     // acc(m = j, n = i) = sum_v C[j][v] Zr[i][v] - S[j][v] Zi[i][v]
+        uint4 br[4], bi[4];
+#pragma unroll
+        for (int ni = 0; ni < 4; ++ni) { br[ni] = frag_km<float>(Zrs, LDZ, 16 * ni, c); bi[ni] = frag_km<float>(Zis, LDZ, 16 * ni, c); }
+#pragma unroll
+        for (int mi = 0; mi < 4; ++mi) {
+            const uint4 cf = pfrag(Cg, j0 + 16 * mi, c), nsf = neg4(pfrag(Sg, j0 + 16 * mi, c));
+#pragma unroll
+            for (int ni = 0; ni < 4; ++ni) { mma_chunk<float>(o[mi][ni], cf, br[ni]); mma_chunk<float>(o[mi][ni], nsf, bi[ni]); }
+        }
+    }
+#pragma unroll
+    for (int mi = 0; mi < 4; ++mi)
+#pragma unroll
+        for (int ni = 0; ni < 4; ++ni) {
+            f32x4* p = reinterpret_cast<f32x4*>(map + ((long)m * 256 + i0 + 16 * ni + (l & 15)) * 256 + j0 + 16 * mi + 4 * (l >> 4));
+            *p = *p + o[mi][ni] * (1.0f / 65536.0f);
+        }
+}
+
+// dvec[row] = sum_j P[row][j] dA[row][j]; one wave per row of 256
+__global__ __launch_bounds__(NTH) void gattn_rowdot_kernel(const float* __restrict__ P, const float* __restrict__ dA, float* __restrict__ dvec) {
+    const long row = (long)blockIdx.x * 4 + wave_id();
+    const int l = lane_id();
+    const f32x4 p = *reinterpret_cast<const f32x4*>(P + row * 256 + 4 * l), g = *reinterpret_cast<const f32x4*>(dA + row * 256 + 4 * l);
+    const float s = wave_sum(p[0] * g[0] + p[1] * g[1] + p[2] * g[2] + p[3] * g[3]);
+    if (l == 0) dvec[row] = s;
+}
+
+constexpr size_t ROW_LDS = 64 * LDA, COL_LDS = 64 * LDA, OUT_LDS = 2 * 256 * LDZ;
+// map += filter(map) over `maps` maps; backward (dlamb != nullptr): also d lamb against the half transform of pmap in pwork
+static void launch_filter(float* map, float* work, const float* pmap, float* pwork, const GAttnArgs& a, hipStream_t st) {
+    const int maps = a.B * a.heads;
+    const bool dl = a.dlamb != nullptr && pmap != nullptr;
+    FW_SET_LDS_ONCE(bands_row_kernel, ROW_LDS);
+    if (dl) hipLaunchKernelGGL(bands_row_kernel, dim3(maps * 4), dim3(NTH), ROW_LDS, st, pmap, pwork, a.panels);
+    hipLaunchKernelGGL(bands_row_kernel, dim3(maps * 4), dim3(NTH), ROW_LDS, st, (const float*)map, work, a.panels);
+    if (dl) {
+        FW_SET_LDS_ONCE((bands_col_kernel<true>), 2 * COL_LDS);
+        hipLaunchKernelGGL((bands_col_kernel<true>), dim3(maps * 8), dim3(NTH), 2 * COL_LDS, st, work, (const float*)pwork, a.panels, a.bandidx, a.lamb,
+                           a.dlamb, a.nb, a.lamb_batch, a.heads);
+    } else {
+        FW_SET_LDS_ONCE((bands_col_kernel<false>), COL_LDS);
+        hipLaunchKernelGGL((bands_col_kernel<false>), dim3(maps * 8), dim3(NTH), COL_LDS, st, work, (const float*)nullptr, a.panels, a.bandidx, a.lamb,
+                           (float*)nullptr, a.nb, a.lamb_batch, a.heads);
+    }
+    FW_SET_LDS_ONCE(bands_out_kernel, OUT_LDS);
+    hipLaunchKernelGGL(bands_out_kernel, dim3(maps * 4), dim3(NTH), OUT_LDS, st, map, (const float*)work, a.panels);
+}
+template <typename T> static int bands_fwd(const GAttnArgs& a, float* work, hipStream_t st) {
+    const size_t lds = fwd_lds<T>(4, false);
+    FW_SET_LDS_ONCE((gattn_probs_kernel<T>), lds);
+    hipLaunchKernelGGL((gattn_probs_kernel<T>), dim3(a.B * a.heads * 4), dim3(NTH), lds, st, a);
+    launch_filter(a.map, work, nullptr, nullptr, a, st);
+    FW_SET_LDS_ONCE((gattn_apply_kernel<T>), lds);
+    hipLaunchKernelGGL((gattn_apply_kernel<T>), dim3(a.B * a.heads * 4), dim3(NTH), lds, st, a);
+    FW_LAUNCH_RET();
+}
+template <typename T> static int bands_bwd(const GAttnArgs& a, float* work, hipStream_t st) {
+    const int maps = a.B * a.heads;
+    const size_t lds_rows = (size_t)4 * GG<T>::TILE, lds = bwd_lds<T>(false);
+    FW_SET_LDS_ONCE((gattn_dc_rows_kernel<T, true>), lds_rows);
+    hipLaunchKernelGGL((gattn_dc_rows_kernel<T, true>), dim3(maps * 4), dim3(NTH), lds_rows, st, a);
+    launch_filter(a.map2, work, a.pmap, work + (long)maps * 2 * PLANE, a, st);
+    hipLaunchKernelGGL(gattn_rowdot_kernel, dim3(maps * 64), dim3(NTH), 0, st, (const float*)a.pmap, (const float*)a.map2, a.dvec);
+    FW_SET_LDS_ONCE((gattn_maps_bwd_kernel<T>), lds);
+    hipLaunchKernelGGL((gattn_maps_bwd_kernel<T>), dim3(maps * 4), dim3(NTH), lds, st, a);
+    FW_LAUNCH_RET();
+}
 template <typename T> static int dispatch(const GAttnArgs& a, bool bwd, hipStream_t st) {
     const bool lamb = a.lamb != nullptr;
     if (a.N == 64) {
         if (lamb) bwd ? launch_bwd<T, 1, true>(a, st) : launch_fwd<T, 1, true>(a, st);
         else bwd ? launch_bwd<T, 1, false>(a, st) : launch_fwd<T, 1, false>(a, st);
+    } else if (lamb) {
+        bwd ? launch_dc_bwd<T>(a, st) : launch_dc_fwd<T>(a, st);
     } else {
         bwd ? launch_bwd<T, 4, false>(a, st) : launch_fwd<T, 4, false>(a, st);
     }
     FW_LAUNCH_RET();
 }
+// lamb: N = 64 with the 64x64 tables (any nb), or N = 256 in the 'DC' form (nb = 2, band 0 = bin (0, 0): no tables); nothing else has a kernel
 static bool common_ok(const GAttnArgs& a, int dtype) {
     const int sz = dtype == FW_DT_BF16 ? 2 : 4;
     if (!(a.q && a.k && a.v && a.lse && a.B > 0 && a.heads > 0 && (a.N == 64 || a.N == 256))) return false;
     if ((a.ld * sz) % 16 || ((uintptr_t)a.q | (uintptr_t)a.k | (uintptr_t)a.v) % 16) return false;
     if (a.thresh && !a.seed) return false;
-    if (a.lamb && !(a.N == 64 && a.bandidx && a.panels && a.nb >= 1 && a.nb <= 16 && (a.lamb_batch == 1 || a.lamb_batch == a.B))) return false;
+    if (a.lamb) {
+        if (!(a.nb >= 1 && a.nb <= 16 && (a.lamb_batch == 1 || a.lamb_batch == a.B))) return false;
+        if (a.N == 64 ? !(a.bandidx && a.panels) : !(a.nb == 2 && !a.bandidx && !a.panels)) return false;
+    }
     return true;
+}
+// <n>_bands on the 256x256 map: the tables are required (that is what tells it from the table-free 'DC' form of fw_gattn_fwd)
+static bool bands_ok(const GAttnArgs& a, int dtype) {
+    const int sz = dtype == FW_DT_BF16 ? 2 : 4;
+    if (!(a.q && a.k && a.v && a.lse && a.B > 0 && a.heads > 0)) return false;
+    if ((a.ld * sz) % 16 || ((uintptr_t)a.q | (uintptr_t)a.k | (uintptr_t)a.v) % 16) return false;
+    if (a.thresh && !a.seed) return false;
+    return a.lamb && a.bandidx && a.panels && (uintptr_t)a.panels % 16 == 0 && (uintptr_t)a.bandidx % 4 == 0 && a.nb >= 1 && a.nb <= 16 &&
+           (a.lamb_batch == 1 || a.lamb_batch == a.B);
 }
 }  // namespace
 
@@ -580,7 +1003,46 @@ extern "C" int fw_gattn_bwd(int dtype, const void* q, const void* k, const void*
     const int sz = dtype == FW_DT_BF16 ? 2 : 4;
     FW_CHECK_ARG(dtype == FW_DT_BF16 || dtype == FW_DT_F32);
     FW_CHECK_ARG(common_ok(a, dtype) && o && dout && dq && dk && dv && (lamb ? dlamb != nullptr : dvec != nullptr));
+    FW_CHECK_ARG(!(lamb && N == 256) || dvec != nullptr);                  // the DC form keeps rowsum(P G) there
     FW_CHECK_ARG((ldo * sz) % 16 == 0 && (lddo * sz) % 16 == 0 && (ldd * sz) % 16 == 0 && drop_p >= 0.f && drop_p < 1.f);
     FW_CHECK_ARG(((uintptr_t)o | (uintptr_t)dout | (uintptr_t)dq | (uintptr_t)dk | (uintptr_t)dv) % 16 == 0);
     return dtype == FW_DT_BF16 ? dispatch<bf16raw>(a, true, (hipStream_t)stream) : dispatch<float>(a, true, (hipStream_t)stream);
+}
+
+// <n>_bands with N x N masks at N = 256 (see fwair.h): probs -> row / col / out passes -> apply
+extern "C" int fw_gattn_bands_fwd(int dtype, const void* q, const void* k, const void* v, long ld, void* out, long ldo, float* lse, int B, int heads,
+                                  float scale, const void* seed, int site, float drop_p, const float* lamb, int nb, int lamb_batch,
+                                  const void* bandidx, const float* panels, float* amap, float* work, void* stream) {
+    GAttnArgs a{};
+    a.q = (const char*)q; a.k = (const char*)k; a.v = (const char*)v; a.ld = ld; a.out = (char*)out; a.ldo = ldo; a.lse = lse;
+    a.B = B; a.heads = heads; a.N = 256; a.scale = scale;
+    a.seed = (const unsigned*)seed; a.site = (unsigned)site; a.thresh = drop_p > 0.f ? fw_drop_thresh(drop_p) : 0u;
+    a.inv_keep = drop_p > 0.f ? 1.0f / (1.0f - drop_p) : 1.0f;
+    a.lamb = lamb; a.nb = nb; a.lamb_batch = lamb_batch; a.bandidx = (const unsigned char*)bandidx; a.panels = panels; a.map = amap;
+    const int sz = dtype == FW_DT_BF16 ? 2 : 4;
+    FW_CHECK_ARG(dtype == FW_DT_BF16 || dtype == FW_DT_F32);
+    FW_CHECK_ARG(bands_ok(a, dtype) && out && amap && work && (ldo * sz) % 16 == 0 && drop_p >= 0.f && drop_p < 1.f);
+    FW_CHECK_ARG(((uintptr_t)out | (uintptr_t)amap | (uintptr_t)work) % 16 == 0);
+    return dtype == FW_DT_BF16 ? bands_fwd<bf16raw>(a, work, (hipStream_t)stream) : bands_fwd<float>(a, work, (hipStream_t)stream);
+}
+
+extern "C" int fw_gattn_bands_bwd(int dtype, const void* q, const void* k, const void* v, long ld, const void* dout, long lddo, const float* lse,
+                                  float* dvec, void* dq, void* dk, void* dv, long ldd, int B, int heads, float scale, const void* seed, int site,
+                                  float drop_p, const float* lamb, float* dlamb, int nb, int lamb_batch, const void* bandidx, const float* panels,
+                                  const float* amap, float* pmap, float* gmap, float* work, void* stream) {
+    GAttnArgs a{};
+    a.q = (const char*)q; a.k = (const char*)k; a.v = (const char*)v; a.ld = ld;
+    a.dout = (const char*)dout; a.lddo = lddo; a.lse = const_cast<float*>(lse); a.dvec = dvec;
+    a.dq = (char*)dq; a.dk = (char*)dk; a.dv = (char*)dv; a.ldd = ldd;
+    a.B = B; a.heads = heads; a.N = 256; a.scale = scale;
+    a.seed = (const unsigned*)seed; a.site = (unsigned)site; a.thresh = drop_p > 0.f ? fw_drop_thresh(drop_p) : 0u;
+    a.inv_keep = drop_p > 0.f ? 1.0f / (1.0f - drop_p) : 1.0f;
+    a.lamb = lamb; a.dlamb = dlamb; a.nb = nb; a.lamb_batch = lamb_batch; a.bandidx = (const unsigned char*)bandidx; a.panels = panels;
+    a.map = const_cast<float*>(amap); a.pmap = pmap; a.map2 = gmap;
+    const int sz = dtype == FW_DT_BF16 ? 2 : 4;
+    FW_CHECK_ARG(dtype == FW_DT_BF16 || dtype == FW_DT_F32);
+    FW_CHECK_ARG(bands_ok(a, dtype) && dout && dq && dk && dv && dvec && dlamb && amap && pmap && gmap && work);
+    FW_CHECK_ARG((lddo * sz) % 16 == 0 && (ldd * sz) % 16 == 0 && drop_p >= 0.f && drop_p < 1.f);
+    FW_CHECK_ARG(((uintptr_t)dout | (uintptr_t)dq | (uintptr_t)dk | (uintptr_t)dv | (uintptr_t)amap | (uintptr_t)pmap | (uintptr_t)gmap | (uintptr_t)work) % 16 == 0);
+    return dtype == FW_DT_BF16 ? bands_bwd<bf16raw>(a, work, (hipStream_t)stream) : bands_bwd<float>(a, work, (hipStream_t)stream);
 }

@@ -14,7 +14,9 @@ stream -- as it does between torch's own CPU and GPU generators -- the Bernoulli
 
 `frequency_decompose_type` in {'DC', '<n>_bands'}: the learnable band re-weighting `lamb` of encoder_ViT.py:51-66,85-92 runs inside
 the attention kernel (64x64 2-D DFT on the f32 MFMA).  Like the reference it needs N = dim_head = 64, i.e. 128x128 inputs (its masks
-are dim_head x dim_head, :56,60); at any other size both raise.
+are dim_head x dim_head, :56,60); at any other size both raise.  `opt.vit_band_grid = 'tokens'` sizes the masks by the attention
+map instead (N x N; identical at N = 64): at N = 256 'DC' then runs as an affine map of the softmax (csrc/fw_gattn.hip dc_coef)
+and '<n>_bands' as a multi-pass 256x256 2-D DFT on the f32 MFMA between a probabilities and an apply kernel (fw_gattn_bands_fwd / bwd).
 """
 import math
 import zlib
@@ -121,24 +123,25 @@ class FeedForward(nn.Module):
 _consts = {}
 
 
-def _spectral_tables(kind, nb, device):
-    """(bandidx u8 [64][64] in un-shifted coordinates, f32 cos | sin panels [2][64][64]) of the 64x64 attention-map decomposition
-    (encoder_ViT.py:53-60: FrequencyDecompose('frequency_decompose', 1/nb, 64, 64) or 'frequency_decompose_dc')."""
+def _spectral_tables(kind, nb, device, n=64):
+    """(bandidx u8 [n][n] in un-shifted coordinates, f32 cos | sin panels [2][n][n]) of the n x n attention-map decomposition
+    (encoder_ViT.py:53-60: FrequencyDecompose('frequency_decompose', 1/nb, n, n) or 'frequency_decompose_dc'; the reference has
+    n = dim_head = 64, `--vit_band_grid tokens` sizes the masks by the map: n = N tokens)."""
     from . import lfs
-    key = (kind, nb, str(device))
+    key = (kind, nb, str(device)) if n == 64 else (kind, nb, str(device), n)
     if key not in _consts:
         if kind == 'DC':
-            idx = torch.ones((64, 64), dtype=torch.uint8)
+            idx = torch.ones((n, n), dtype=torch.uint8)
             idx[0, 0] = 0                                                # band 0 = the mean (DC bin), band 1 = everything else
         else:
-            masks = lfs.band_masks_shifted('frequency_decompose', 1. / nb, 64, 64)
-            shifted = torch.zeros((64, 64), dtype=torch.uint8)
+            masks = lfs.band_masks_shifted('frequency_decompose', 1. / nb, n, n)
+            shifted = torch.zeros((n, n), dtype=torch.uint8)
             for i, m in enumerate(masks):
                 shifted[m] = i
             assert bool(torch.stack(masks).sum(0).eq(1).all())
             idx = torch.fft.ifftshift(shifted, dim=(0, 1)).contiguous()
         assert bool((idx == idx.t()).all())                              # radial masks: the filter commutes with the transpose
-        ang = 2 * math.pi * torch.outer(torch.arange(64, dtype=torch.float64), torch.arange(64, dtype=torch.float64)) / 64
+        ang = 2 * math.pi * torch.outer(torch.arange(n, dtype=torch.float64), torch.arange(n, dtype=torch.float64)) / n
         panels = torch.stack([torch.cos(ang), torch.sin(ang)]).float().contiguous()
         _consts[key] = (idx.to(device), panels.to(device))
     return _consts[key]
@@ -157,16 +160,23 @@ class GlobalAttnFn(torch.autograd.Function):
         bidx, panels = spec if spec is not None else (None, None)
         nb, lb = (lamb.shape[0], lamb.shape[1]) if lamb is not None else (0, 1)
         lam = lamb.detach().contiguous() if lamb is not None else None
-        call('fw_gattn_fwd', dt(qkv.dtype), qkv, qkv[:, inner:], qkv[:, 2 * inner:], qkv.stride(0), out, out.stride(0), lse, B, heads, N,
-             64 ** -0.5, seed, site, float(p), lam, nb, lb, bidx, panels)
-        ctx.save_for_backward(qkv, out, lse, lam)
+        amap = None
+        if N == 256 and lam is not None and bidx is not None:            # <n>_bands on the N x N grid: the map leaves the workgroup
+            amap = torch.empty((B * heads, N, N), dtype=torch.float32, device=qkv.device)          # P + filter(P): kept for backward
+            work = torch.empty((B * heads, 2, N, N), dtype=torch.float32, device=qkv.device)
+            call('fw_gattn_bands_fwd', dt(qkv.dtype), qkv, qkv[:, inner:], qkv[:, 2 * inner:], qkv.stride(0), out, out.stride(0), lse, B, heads,
+                 64 ** -0.5, seed, site, float(p), lam, nb, lb, bidx, panels, amap, work)
+        else:
+            call('fw_gattn_fwd', dt(qkv.dtype), qkv, qkv[:, inner:], qkv[:, 2 * inner:], qkv.stride(0), out, out.stride(0), lse, B, heads, N,
+                 64 ** -0.5, seed, site, float(p), lam, nb, lb, bidx, panels)
+        ctx.save_for_backward(qkv, out, lse, lam, amap)
         ctx.meta = (meta, seed)
         ctx.lamb_param = lamb
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        qkv, out, lse, lam = ctx.saved_tensors
+        qkv, out, lse, lam, amap = ctx.saved_tensors
         (B, N, heads, p, site, spec), seed = ctx.meta
         inner = heads * 64
         dout = Fn.aligned(dout)
@@ -176,9 +186,16 @@ class GlobalAttnFn(torch.autograd.Function):
         dvec = None
         if lam is not None:
             dlam, rl = Fn._grad_target(ctx.lamb_param)
-        else:
+        if lam is None or N == 256:                                      # 'DC' on the N x N grid keeps rowsum(P . dP) there
             dvec = torch.empty((B, heads, N), dtype=torch.float32, device=qkv.device)
         nb, lb = (lam.shape[0], lam.shape[1]) if lam is not None else (0, 1)
+        if amap is not None:
+            pmap, gmap = torch.empty_like(amap), torch.empty_like(amap)
+            work = torch.empty((2, B * heads, 2, N, N), dtype=torch.float32, device=qkv.device)
+            call('fw_gattn_bands_bwd', dt(qkv.dtype), qkv, qkv[:, inner:], qkv[:, 2 * inner:], qkv.stride(0), dout, dout.stride(0), lse, dvec,
+                 dqkv, dqkv[:, inner:], dqkv[:, 2 * inner:], dqkv.stride(0), B, heads, 64 ** -0.5, seed, site, float(p), lam, dlam, nb, lb,
+                 bidx, panels, amap, pmap, gmap, work)
+            return dqkv, rl, None
         call('fw_gattn_bwd', dt(qkv.dtype), qkv, qkv[:, inner:], qkv[:, 2 * inner:], qkv.stride(0), out, out.stride(0), dout, dout.stride(0),
              lse, dvec, dqkv, dqkv[:, inner:], dqkv[:, 2 * inner:], dqkv.stride(0), B, heads, N, 64 ** -0.5, seed, site, float(p),
              lam, dlam, nb, lb, bidx, panels)
@@ -243,8 +260,11 @@ class Attention(nn.Module):
 
 
 class Transformer(nn.Module):
-    def __init__(self, dim, depth, heads, dim_head, mlp_dim, dropout=0., decompose_type='none', wised_batch=None):
+    def __init__(self, dim, depth, heads, dim_head, mlp_dim, dropout=0., decompose_type='none', wised_batch=None, band_grid='head_dim'):
         super().__init__()
+        if band_grid not in ('head_dim', 'tokens'):
+            raise ValueError(f'vit_band_grid: {band_grid!r} (head_dim | tokens)')
+        self.band_grid = band_grid                                       # masks dim_head x dim_head (the reference) or N x N
         self.layers = nn.ModuleList([nn.ModuleList([
             PreNorm(dim, Attention(dim, heads=heads, dim_head=dim_head, dropout=dropout, decompose_type=decompose_type, wised_batch=wised_batch)),
             PreNorm(dim, FeedForward(dim, mlp_dim, dropout=dropout))]) for _ in range(depth)])
@@ -264,12 +284,13 @@ class Transformer(nn.Module):
             qkv = Fn.linear(xn, a.to_qkv.weight)                                              # [B*N, 3 * inner] = q | k | v, head h at column h*64
             lamb, spec = None, None
             if a.num_bands is not None:
-                if N != 64:
+                if N != 64 and self.band_grid != 'tokens':
                     raise NotImplementedError('the band re-weighting needs N = dim_head = 64 tokens (128x128 inputs): the reference sizes '
                                               'its masks dim_head x dim_head (encoder_ViT.py:56,60) and fails otherwise too')
                 if a.lamb.shape[1] not in (1, B):
                     raise NotImplementedError(f'batch-wise lamb was built for batch {a.lamb.shape[1]}, got {B}')
-                lamb, spec = a.lamb, _spectral_tables(a._kind, a.num_bands, x.device)
+                # N = 256 'DC': band 0 is the mean of the map, 1 / N for softmax rows -- an affine map, no tables (csrc/fw_gattn.hip dc_coef)
+                lamb, spec = a.lamb, (None if N != 64 and a._kind == 'DC' else _spectral_tables(a._kind, a.num_bands, x.device, n=N))
             o = GlobalAttnFn.apply(qkv, lamb, (B, N, a.heads, pa, site, spec))
             if po > 0:
                 y = Fn.linear(o, a.to_out[0].weight, a.to_out[0].bias, out_f32=True)
@@ -309,7 +330,8 @@ class ViTEncoder(nn.Module):
         self.pos_embedding = nn.Parameter(torch.randn(1, num_patches, dim))
         self.dropout = nn.Dropout(emb_dropout)
         self.transformer = Transformer(dim, depth, heads, dim_head, mlp_dim, dropout, decompose_type=opt.frequency_decompose_type,
-                                       wised_batch=opt.batch_size if getattr(opt, 'batch_wise_decompose', False) else None)
+                                       wised_batch=opt.batch_size if getattr(opt, 'batch_wise_decompose', False) else None,
+                                       band_grid=getattr(opt, 'vit_band_grid', 'head_dim'))
         self.mlp_head = nn.Sequential(nn.LayerNorm(dim), nn.Linear(dim, dim // out_channels * opt.encoder_dim))
         self.norm = nn.Sequential(nn.BatchNorm2d(opt.encoder_dim), nn.LeakyReLU(0.1, True))
         self.avg = nn.AdaptiveAvgPool2d(1)

@@ -267,16 +267,37 @@ int fw_small_linear_bwd(const float* dy, const float* y, const float* x, const f
  * the 64 x N score block in registers.  Dropout (encoder_ViT.py:67,94): counter-based mask of (seed[0], site, flat index of the
  * [B][heads][N][N] map), re-derived by the backward pass; drop_p = 0 or eval: off.  lamb (optional, N = 64 only -- the reference's
  * masks are dim_head x dim_head, encoder_ViT.py:56,60): f32 [nb][lamb_batch (1 | B)][heads] of encoder_ViT.py:62-66,85-92, evaluated
- * as a 64x64 2-D DFT on the f32 MFMA; bandidx: u8 [64][64] band of every un-shifted spectrum bin; panels: f32 cos[64][64], sin[64][64]. */
+ * as a 64x64 2-D DFT on the f32 MFMA; bandidx: u8 [64][64] band of every un-shifted spectrum bin; panels: f32 cos[64][64], sin[64][64].
+ * N = 256 with lamb: only the 'DC' decomposition on the N x N grid (encoder_ViT.py:59-60 'frequency_decompose_dc' with masks sized
+ * by the map): nb = 2, bandidx = panels = NULL; band 0 is the mean of the map, 1 / N for softmax rows, so the kernel evaluates
+ * attn' = (1 + lamb[1]) attn + (lamb[0] - lamb[1]) / N without a transform; `<n>_bands` at N = 256 is fw_gattn_bands_fwd / bwd, which
+ * require the tables.  Every other lamb / N combination is an argument error. */
 int fw_gattn_fwd(int dtype, const void* q, const void* k, const void* v, long ld, void* out, long ldo, float* lse, int B, int heads, int N,
                  float scale, const void* seed, int site, float drop_p, const float* lamb, int nb, int lamb_batch, const void* bandidx,
                  const float* panels, void* stream);
-/* dq, dk, dv: T, same layout as q / k / v (row stride ldd); dvec: f32 [B][heads][N] scratch (rowsum(dO . O), unused with lamb);
+/* dq, dk, dv: T, same layout as q / k / v (row stride ldd); dvec: f32 [B][heads][N] scratch (rowsum(dO . O); unused with lamb at
+ * N = 64, required with lamb at N = 256, where it receives rowsum(P . dP));
  * dlamb: accumulated (atomics), same layout as lamb. */
 int fw_gattn_bwd(int dtype, const void* q, const void* k, const void* v, long ld, const void* o, long ldo, const void* dout, long lddo,
                  const float* lse, float* dvec, void* dq, void* dk, void* dv, long ldd, int B, int heads, int N, float scale,
                  const void* seed, int site, float drop_p, const float* lamb, float* dlamb, int nb, int lamb_batch, const void* bandidx,
                  const float* panels, void* stream);
+/* The same attention with `<n>_bands` masks sized by the map (N = 256 only; encoder_ViT.py:55-56,85-92 with FrequencyDecompose(
+ * 'frequency_decompose', 1/nb, N, N) in place of the dim_head-sized masks that do not fit a 256x256 map).  bandidx: u8 [256][256]
+ * (symmetric), panels: f32 cos[256][256], sin[256][256] of 2 pi u i / 256.  The map leaves the workgroup: a probabilities kernel,
+ * a row / column / output pass of a batched 256x256 2-D DFT on the f32 MFMA, and an apply kernel (Dropout, attn v).
+ * amap: f32 [B*heads][256][256], receives attn' = attn + filter(attn) (before Dropout) and is what the backward pass needs;
+ * work: f32 [B*heads][2][256][256] scratch. */
+int fw_gattn_bands_fwd(int dtype, const void* q, const void* k, const void* v, long ld, void* out, long ldo, float* lse, int B, int heads,
+                       float scale, const void* seed, int site, float drop_p, const float* lamb, int nb, int lamb_batch, const void* bandidx,
+                       const float* panels, float* amap, float* work, void* stream);
+/* amap: as the forward pass left it; pmap, gmap: f32 [B*heads][256][256] scratch (the probabilities rebuilt from lse; the map
+ * gradient, filtered in place: the filter is self-adjoint); work: f32 [2][B*heads][2][256][256] scratch; dvec: f32 [B][heads][256]
+ * scratch; dlamb accumulated: sum over band of Re(X_P conj(X_G)) / N^2, one atomic per workgroup and band. */
+int fw_gattn_bands_bwd(int dtype, const void* q, const void* k, const void* v, long ld, const void* dout, long lddo, const float* lse,
+                       float* dvec, void* dq, void* dk, void* dv, long ldd, int B, int heads, float scale, const void* seed, int site,
+                       float drop_p, const float* lamb, float* dlamb, int nb, int lamb_batch, const void* bandidx, const float* panels,
+                       const float* amap, float* pmap, float* gmap, float* work, void* stream);
 /* nn.Dropout call sites of the ViT (encoder_ViT.py:31,33,73,158,189) with the same counter-based masks.  mode 0: y = drop(x) (f32);
  * 1: y = res + drop(x) (f32); 2: y = drop(gelu(x)) (T); 3: y = drop(x) * gelu'(aux) (T, backward of 2); 4: y = drop(x + aux[i % period])
  * (f32: pos_embedding add + emb dropout, encoder_ViT.py:187-189).  n = elements of the contiguous tensor; p = 0: identity masks. */
