@@ -9,6 +9,13 @@
 //     and average the RESTORED tiles over their overlap (gather form: at most two tiles per axis cover a pixel; no atomics).
 //   * fw_ssim7 -- structural similarity as utils/val_utils.py:50-66 calls it (skimage.metrics.structural_similarity defaults: 7x7
 //     uniform window, K1 = 0.01, K2 = 0.03, sample covariance, border of 3 pixels cropped, mean over channels), inputs clipped to [0, 1].
+//   * fw_eval_gather / fw_eval_blend / fw_eval_ssim7 -- the same three steps for a whole CHUNK of test images of different sizes in one
+//     launch each, driven by tables in HBM (fwair/evaluate.py EvalEngine): tiles straight from the uint8 images (paired test sets) or
+//     with the test set's Gaussian noise synthesised on the fly (utils/dataset_utils.py:177-182; same counter-based draw as
+//     fw_train_batch, so overlapping tiles see one noisy image that is never stored); the overlap average into a packed f32 buffer
+//     together with the squared error against the ground truth (utils/val_utils.py:52-63) and the uint8 image of utils/image_io.py:383;
+//     SSIM over the packed buffer.  Four consecutive x per thread (one 4-byte load of uint8 / one 16-byte access of f32) where the
+//     row pitch and the pointers are multiples of 4, one x per thread otherwise.
 // All HBM-bound byte / float streaming work: grid-stride kernels, coalesced along x.
 #include "fw_common.h"
 
@@ -123,6 +130,188 @@ __global__ void ssim7_kernel(const float* __restrict__ a, const float* __restric
         atomicAdd(out + img, s);
     }
 }
+
+// ---- batched evaluation (a chunk of images per launch) ----------------------------------------------------------------------------
+// itab[i] = {clean u8 ptr [3][H][W] or 0, degraded u8 ptr or 0, H, W};  ttab[t] = {image, y0, x0, 0};  gtab[i] = {offset of the image
+// in the packed buffer (elements), first tile of the image in the chunk's tile buffer, ny, nx}
+FW_DEV float noisy_u8(float g, float sg, unsigned key, long pi) {                     // train_batch_kernel's draw, same arithmetic
+    const unsigned r1 = fw_hash32((unsigned)pi ^ key), r2 = fw_hash32(r1 + 0x9E3779B9U);
+    const float u1 = ((float)r1 + 1.0f) * 2.3283064365386963e-10f, u2 = (float)r2 * 2.3283064365386963e-10f;
+    const float z = sqrtf(-2.0f * __logf(u1)) * __cosf(6.283185307179586f * u2);
+    return floorf(fminf(fmaxf(g + z * sg, 0.f), 255.f));
+}
+template <int V>
+FW_DEV void eval_gather_body(const unsigned char* __restrict__ src, bool synth, float sg, unsigned key, float* __restrict__ out, int H, int W,
+                             int y0, int x0, int T) {
+    const int q = T / V, n = 3 * T * q;
+    for (int g = blockIdx.x * blockDim.x + threadIdx.x; g < n; g += gridDim.x * blockDim.x) {
+        const int j = (g % q) * V, i = (g / q) % T, c = g / (q * T);
+        const long pi = ((long)c * H + (y0 + i)) * W + (x0 + j);
+        unsigned char v[V];
+        if constexpr (V == 4) *reinterpret_cast<unsigned*>(v) = *reinterpret_cast<const unsigned*>(src + pi);
+        else v[0] = src[pi];
+        float o[V];
+#pragma unroll
+        for (int k = 0; k < V; ++k) {
+            float d = (float)v[k];
+            if (synth) d = noisy_u8(d, sg, key, pi + k);
+            o[k] = __fdiv_rn(d, 255.0f);
+        }
+        float* dst = out + ((long)c * T + i) * T + j;
+        if constexpr (V == 4) *reinterpret_cast<float4*>(dst) = make_float4(o[0], o[1], o[2], o[3]);
+        else dst[0] = o[0];
+    }
+}
+__global__ void eval_gather_kernel(const long long* __restrict__ itab, const int* __restrict__ ttab, const float* __restrict__ sigma,
+                                   const unsigned* __restrict__ seed, unsigned site, float* __restrict__ tiles, int T) {
+    const int t = blockIdx.y;
+    const int im = ttab[t * 4 + 0], y0 = ttab[t * 4 + 1], x0 = ttab[t * 4 + 2];
+    const unsigned char* clean = reinterpret_cast<const unsigned char*>(itab[im * 4 + 0]);
+    const unsigned char* degr = reinterpret_cast<const unsigned char*>(itab[im * 4 + 1]);
+    const int H = (int)itab[im * 4 + 2], W = (int)itab[im * 4 + 3];
+    const unsigned char* src = degr ? degr : clean;
+    if (!src || y0 < 0 || x0 < 0 || y0 + T > H || x0 + T > W) return;              // a tile outside its image is never read
+    const float sg = sigma[im];
+    const bool synth = !degr && sg > 0.f;
+    const unsigned key = fw_site_key(seed[0], site + (unsigned)im);
+    float* out = tiles + (long)t * 3 * T * T;
+    if ((((long)src | W | x0) & 3) == 0) eval_gather_body<4>(src, synth, sg, key, out, H, W, y0, x0, T);
+    else eval_gather_body<1>(src, synth, sg, key, out, H, W, y0, x0, T);
+}
+
+FW_DEV float block_sum(float acc, float* red) {                                        // valid on thread 0
+    acc = wave_sum(acc);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = acc;
+    __syncthreads();
+    float s = 0.f;
+    if (threadIdx.x == 0)
+        for (int i = 0; i < TPB / 64; ++i) s += red[i];
+    return s;
+}
+template <int V>
+FW_DEV float eval_blend_body(const unsigned char* __restrict__ clean, const int* __restrict__ ttab, const float* __restrict__ rest,
+                             float* __restrict__ packed, unsigned char* __restrict__ u8out, int H, int W, int t0, int ny, int nx, int ntiles, int T) {
+    const int wq = W / V;
+    const long n = (long)3 * H * wq;
+    float sse = 0.f;
+    for (long g = (long)blockIdx.x * blockDim.x + threadIdx.x; g < n; g += (long)gridDim.x * blockDim.x) {
+        const int x = (int)(g % wq) * V, y = (int)((g / wq) % H), c = (int)(g / ((long)wq * H));
+        // at most two tiles per axis cover a pixel: the regular one it falls into and the last one, flush with the border (test.py:48-49)
+        const int a0 = min(y / T, ny - 1), b0 = min(x / T, nx - 1);
+        float acc[V], cnt = 0.f;
+#pragma unroll
+        for (int k = 0; k < V; ++k) acc[k] = 0.f;
+        for (int a = a0; a < ny; a += max(ny - 1 - a0, 1)) {
+            for (int b = b0; b < nx; b += max(nx - 1 - b0, 1)) {
+                const int ti = t0 + a * nx + b;
+                if (ti >= ntiles) continue;
+                const int dy = y - ttab[ti * 4 + 1], dx = x - ttab[ti * 4 + 2];
+                if (dy < 0 || dy >= T || dx < 0 || dx >= T) continue;
+                const float* p = rest + (((long)ti * 3 + c) * T + dy) * T + dx;
+                if constexpr (V == 4) {
+                    const float4 r = *reinterpret_cast<const float4*>(p);
+                    acc[0] += r.x; acc[1 % V] += r.y; acc[2 % V] += r.z; acc[3 % V] += r.w;
+                } else acc[0] += p[0];
+                cnt += 1.f;
+            }
+        }
+        const long pi = ((long)c * H + y) * W + x;
+        float o[V];
+        unsigned char gt[V], q[V];
+        if (clean) {
+            if constexpr (V == 4) *reinterpret_cast<unsigned*>(gt) = *reinterpret_cast<const unsigned*>(clean + pi);
+            else gt[0] = clean[pi];
+        }
+#pragma unroll
+        for (int k = 0; k < V; ++k) {
+            o[k] = acc[k] / cnt;
+            if (clean) {
+                const float d = fminf(fmaxf(o[k], 0.f), 1.f) - __fdiv_rn((float)gt[k], 255.0f);
+                sse += d * d;
+            }
+            q[k] = (unsigned char)fminf(fmaxf(o[k] * 255.0f, 0.f), 255.f);           // image_io.py:383: clip, astype(uint8) truncates
+        }
+        if constexpr (V == 4) {
+            *reinterpret_cast<float4*>(packed + pi) = make_float4(o[0], o[1 % V], o[2 % V], o[3 % V]);
+            if (u8out) *reinterpret_cast<unsigned*>(u8out + pi) = *reinterpret_cast<const unsigned*>(q);
+        } else {
+            packed[pi] = o[0];
+            if (u8out) u8out[pi] = q[0];
+        }
+    }
+    return sse;
+}
+__global__ void eval_blend_kernel(const long long* __restrict__ itab, const long long* __restrict__ gtab, const int* __restrict__ ttab,
+                                  const float* __restrict__ rest, float* __restrict__ packed, unsigned char* __restrict__ u8out,
+                                  float* __restrict__ sse, int i0, int ntiles, int T) {
+    __shared__ float red[TPB / 64];
+    const int im = i0 + blockIdx.y;
+    const unsigned char* clean = reinterpret_cast<const unsigned char*>(itab[im * 4 + 0]);
+    const int H = (int)itab[im * 4 + 2], W = (int)itab[im * 4 + 3];
+    const long off = gtab[im * 4 + 0];
+    const int t0 = (int)gtab[im * 4 + 1], ny = (int)gtab[im * 4 + 2], nx = (int)gtab[im * 4 + 3];
+    float* pk = packed + off;
+    unsigned char* u8 = u8out ? u8out + off : nullptr;
+    float acc;
+    if ((((long)clean | (long)u8 | off | W) & 3) == 0 && ((long)pk & 15) == 0)       // tile origins are then multiples of 4 too (T % 4 == 0)
+        acc = eval_blend_body<4>(clean, ttab, rest, pk, u8, H, W, t0, ny, nx, ntiles, T);
+    else
+        acc = eval_blend_body<1>(clean, ttab, rest, pk, u8, H, W, t0, ny, nx, ntiles, T);
+    if (!clean) return;
+    acc = block_sum(acc, red);
+    if (threadIdx.x == 0) atomicAdd(sse + im, acc);
+}
+
+// ssim7_kernel's arithmetic, a = packed restored image (f32), b = clean uint8 / 255; four neighbouring windows per thread share their
+// 7 x 10 pixels (each window still sums its 49 taps in ssim7_kernel's order).  out[image] += sum of the SSIM map.
+__global__ void eval_ssim7_kernel(const long long* __restrict__ itab, const long long* __restrict__ gtab, const float* __restrict__ packed,
+                                  float* __restrict__ out, int i0) {
+    __shared__ float red[TPB / 64];
+    const int im = i0 + blockIdx.y;
+    const unsigned char* clean = reinterpret_cast<const unsigned char*>(itab[im * 4 + 0]);
+    const int H = (int)itab[im * 4 + 2], W = (int)itab[im * 4 + 3];
+    if (!clean || H < 7 || W < 7) return;
+    const float* a = packed + gtab[im * 4 + 0];
+    const int hh = H - 6, ww = W - 6, wq = (ww + 3) / 4;
+    const long n = (long)3 * hh * wq;
+    float acc = 0.f;
+    for (long g = (long)blockIdx.x * blockDim.x + threadIdx.x; g < n; g += (long)gridDim.x * blockDim.x) {
+        const int x = (int)(g % wq) * 4, y = (int)((g / wq) % hh), c = (int)(g / ((long)wq * hh));
+        float s[4][5];
+#pragma unroll
+        for (int o = 0; o < 4; ++o)
+#pragma unroll
+            for (int k = 0; k < 5; ++k) s[o][k] = 0.f;
+        for (int dy = 0; dy < 7; ++dy) {
+            const long row = ((long)c * H + y + dy) * W + x;
+            float u[10], v[10];
+#pragma unroll
+            for (int k = 0; k < 10; ++k) {
+                const bool in = x + k < W;
+                u[k] = in ? fminf(fmaxf(a[row + k], 0.f), 1.f) : 0.f;
+                v[k] = in ? __fdiv_rn((float)clean[row + k], 255.0f) : 0.f;
+            }
+#pragma unroll
+            for (int o = 0; o < 4; ++o)
+#pragma unroll
+                for (int dx = 0; dx < 7; ++dx) {
+                    const float uu = u[o + dx], vv = v[o + dx];
+                    s[o][0] += uu; s[o][1] += vv; s[o][2] += uu * uu; s[o][3] += vv * vv; s[o][4] += uu * vv;
+                }
+        }
+#pragma unroll
+        for (int o = 0; o < 4; ++o) {
+            if (x + o >= ww) continue;
+            const float inv = 1.0f / 49.0f, cn = 49.0f / 48.0f;
+            const float ua = s[o][0] * inv, ub = s[o][1] * inv;
+            const float va = cn * (s[o][2] * inv - ua * ua), vb = cn * (s[o][3] * inv - ub * ub), vab = cn * (s[o][4] * inv - ua * ub);
+            const float C1 = 1e-4f, C2 = 9e-4f;
+            acc += ((2.f * ua * ub + C1) * (2.f * vab + C2)) / ((ua * ua + ub * ub + C1) * (va + vb + C2));
+        }
+    }
+    acc = block_sum(acc, red);
+    if (threadIdx.x == 0) atomicAdd(out + im, acc);
+}
 }  // namespace
 
 #define ST ((hipStream_t)stream)
@@ -151,5 +340,28 @@ extern "C" int fw_ssim7(const float* a, const float* b, float* out, int n, int C
     long gx = (per + TPB - 1) / TPB;
     if (gx > 1024) gx = 1024;
     hipLaunchKernelGGL(ssim7_kernel, dim3((unsigned)gx, (unsigned)n), dim3(TPB), 0, ST, a, b, out, n, C, H, W);
+    FW_LAUNCH_RET();
+}
+extern "C" int fw_eval_gather(const void* itab, const int* ttab, const float* sigma, const void* seed, int site, float* tiles, int N, int T,
+                              void* stream) {
+    FW_CHECK_ARG(itab && ttab && sigma && seed && tiles && N > 0 && N <= 65535 && T > 0 && T % 4 == 0 && ((uintptr_t)tiles & 15) == 0);
+    long gx = ((long)3 * T * T / 4 + TPB - 1) / TPB;
+    if (gx > 256) gx = 256;
+    hipLaunchKernelGGL(eval_gather_kernel, dim3((unsigned)gx, (unsigned)N), dim3(TPB), 0, ST, (const long long*)itab, ttab, sigma,
+                       (const unsigned*)seed, (unsigned)site, tiles, T);
+    FW_LAUNCH_RET();
+}
+extern "C" int fw_eval_blend(const void* itab, const void* gtab, const int* ttab, const float* rest, float* packed, void* u8out, float* sse,
+                             int i0, int nimg, int ntiles, int T, void* stream) {
+    FW_CHECK_ARG(itab && gtab && ttab && rest && packed && sse && i0 >= 0 && nimg > 0 && nimg <= 65535 && ntiles > 0 && T > 0 && T % 4 == 0 &&
+                 ((uintptr_t)rest & 15) == 0);
+    hipLaunchKernelGGL(eval_blend_kernel, dim3(64, (unsigned)nimg), dim3(TPB), 0, ST, (const long long*)itab, (const long long*)gtab, ttab,
+                       rest, packed, (unsigned char*)u8out, sse, i0, ntiles, T);
+    FW_LAUNCH_RET();
+}
+extern "C" int fw_eval_ssim7(const void* itab, const void* gtab, const float* packed, float* out, int i0, int nimg, void* stream) {
+    FW_CHECK_ARG(itab && gtab && packed && out && i0 >= 0 && nimg > 0 && nimg <= 65535);
+    hipLaunchKernelGGL(eval_ssim7_kernel, dim3(64, (unsigned)nimg), dim3(TPB), 0, ST, (const long long*)itab, (const long long*)gtab, packed,
+                       out, i0);
     FW_LAUNCH_RET();
 }

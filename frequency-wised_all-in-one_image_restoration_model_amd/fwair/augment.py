@@ -124,19 +124,26 @@ class DeviceBatcher:
     images_u8: list of [3, H, W] uint8 device tensors (sizes may differ).  tasks[i]: a noise level, or a `--de_type` name; denoising is
     synthesised INSIDE the kernel (counter-based N(0, 1) per pixel of the full image, so the two crops of a sample share their noise
     exactly as the reference's two crops of one noisy image do, dataset_utils.py:126,131-132); 'deraining' / 'dehazing' samples carry
-    a degraded image made once at construction (the reference reads those pairs from disk, :93-95,129).
+    a degraded image made once at construction (the reference reads those pairs from disk, :93-95,129).  degraded_u8: optional list
+    beside images_u8; where an entry is given (a uint8 tensor of its image's shape, e.g. the pair read from disk by fwair.data) it IS
+    the sample's degraded image, instead of the synthetic stand-in or the in-kernel noise.
     `batch(indices)`: crop origins and flip / rotation modes of the whole batch from ONE device RNG call, one kernel launch, no sync.
     The pointer table of a given index list is built once and cached (a training loop cycles a fixed schedule of index lists)."""
 
-    def __init__(self, images_u8, tasks, size, generator=None):
+    def __init__(self, images_u8, tasks, size, generator=None, degraded_u8=None):
         from . import functional as Fn
         self.size = int(size)
         self.images = [im.contiguous() for im in images_u8]
         self.dev = self.images[0].device
         self.degraded, self.sigma = [], []
-        for im, t in zip(self.images, tasks):
+        given = list(degraded_u8) if degraded_u8 is not None else [None] * len(self.images)
+        assert len(given) == len(self.images)
+        for im, t, dg in zip(self.images, tasks, given):
             assert im.dtype == torch.uint8 and im.dim() == 3 and im.shape[0] == 3 and min(im.shape[1:]) >= self.size
-            if isinstance(t, str) and not t.startswith('denoising'):
+            if dg is not None:
+                assert dg.dtype == torch.uint8 and dg.shape == im.shape and dg.device == im.device
+                self.degraded.append(dg.contiguous()); self.sigma.append(0.0)
+            elif isinstance(t, str) and not t.startswith('denoising'):
                 self.degraded.append(degrade(im, t, generator).contiguous()); self.sigma.append(0.0)
             else:
                 sg = float(t.split('_')[-1]) if isinstance(t, str) else float(t)

@@ -7,7 +7,14 @@ image; this module averages the RESTORED tiles, as the surrounding code intends 
 literal behaviour).  Everything stays on the GPU: fw_tile_gather cuts the tiles, one batched forward per `max_tiles`, fw_tile_blend
 averages the overlap (gather form, no atomics), PSNR as utils/val_utils.py:52-63 and SSIM by fw_ssim7 (skimage's
 structural_similarity defaults: 7x7 uniform window, sample covariance, 3-pixel border cropped -- scikit-image itself is not a dependency).
+
+`EvalEngine` does the same for a whole test set at a time: images of different sizes are taken in chunks that fill a fixed tile buffer,
+one fw_eval_gather / fw_eval_blend / fw_eval_ssim7 launch per chunk (tables in device memory), the network at ONE fixed batch shape
+replayed from a HIP graph, metrics left on the device -- no host synchronisation per image.
 """
+import sys
+
+import numpy as np
 import torch
 
 from .lib import call
@@ -55,3 +62,173 @@ def ssim(restored, clean):
     out = torch.zeros(n, dtype=torch.float32, device=a.device)
     call('fw_ssim7', a, b, out, n, C, H, W)
     return float((out / (C * (H - 6) * (W - 6))).mean())
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# a whole test set at a time
+# ---------------------------------------------------------------------------------------------------------------
+_EVAL_SITE = 0x7B000000
+
+
+def plan_tiles(sizes, tile, chunk_tiles):
+    """sizes: [(H, W)] -> (ttab, gtab, chunks) for fw_eval_gather / fw_eval_blend / fw_eval_ssim7.
+    ttab int32 [N, 4] = {image, y0, x0, 0}: the tiles of every image as test.py:47-55 enumerates them (rows major), image after image.
+    chunks = [(i0, i1, t0, t1)]: images [i0, i1) own the rows [t0, t1) of ttab, t1 - t0 <= chunk_tiles; a chunk ends at an image
+    boundary.  gtab int64 [I, 4] = {offset of the image in its chunk's packed buffer (elements), its first tile counted from t0, ny, nx}."""
+    rows, geo, chunks = [], [], []
+    i0 = t0 = off = 0
+    for i, (H, W) in enumerate(sizes):
+        ys, xs = tile_origins(H, tile), tile_origins(W, tile)
+        n = len(ys) * len(xs)
+        if n > chunk_tiles:
+            raise ValueError(f'fwair: image {i} ({H} x {W}) has {n} tiles of {tile}, the tile buffer holds {chunk_tiles}')
+        if len(rows) - t0 + n > chunk_tiles:
+            chunks.append((i0, i, t0, len(rows)))
+            i0, t0, off = i, len(rows), 0
+        geo.append((off, len(rows) - t0, len(ys), len(xs)))
+        rows += [(i, y, x, 0) for y in ys for x in xs]
+        off += 3 * H * W
+    chunks.append((i0, len(sizes), t0, len(rows)))
+    return np.array(rows, dtype=np.int32).reshape(-1, 4), np.array(geo, dtype=np.int64).reshape(-1, 4), chunks
+
+
+class EvalEngine:
+    """test.py:36-84 for a list of images at device rate.
+
+    run(clean_u8, degraded_u8=None, sigma=0, seed=0, want_u8=False) -> (psnr[I], ssim[I]) as device tensors (+ the restored uint8 images
+    when asked; `want_f32` adds the restored f32 images).  clean_u8 / degraded_u8: lists of uint8 [3, H, W] device tensors.  Paired
+    sets restore degraded_u8; otherwise the clean images get Gaussian noise of `sigma` (a number or one per image) synthesised inside
+    fw_eval_gather from `seed` -- an explicit integer kept in the engine's own device word, NOT the live Dropout seed (which advances
+    with every forward), so that the same seed gives the same noisy test images in every process.  clean_u8=None: no ground truth, no
+    metrics (both None).
+    The network always sees batches of exactly `tile_batch` tiles (the last batch of a chunk is padded with copies of its first tile;
+    padded outputs are never read), so that ONE captured HIP graph serves every batch; use_graph=False launches the same forward eagerly.
+    Nothing in run() waits for the device once the tables of a given input list are uploaded (they are cached); the caller
+    synchronises when it reads the results.  The captured graph reads the weights in place: build a new engine (or call `reset()`)
+    after the weights were changed by anything but in-place updates."""
+
+    def __init__(self, net, tile=128, tile_batch=64, use_graph=True, chunk_tiles=None):
+        assert tile % 8 == 0, 'patch size should be a multiple of window_size'            # test.py:44
+        self.net, self.tile, self.tb = net, int(tile), int(tile_batch)
+        self.use_graph = bool(use_graph)
+        self.cap = -(-int(chunk_tiles or 16 * self.tb) // self.tb) * self.tb
+        self.dev = next(net.parameters()).device
+        self._seed = 0
+        self.seed_word = torch.zeros(1, dtype=torch.int32, device=self.dev)
+        self.tiles = self.rest = self.gin = self.gout = self.packed = None
+        self._graph = None
+        self._plans = {}
+
+    def reset(self):
+        self._graph = self.gout = None
+
+    # ---- tables ------------------------------------------------------------------------------------------------------
+    def _plan(self, clean, degraded, sigma):
+        ref = clean if clean is not None else degraded
+        I = len(ref)
+        sig = [float(s) for s in sigma] if isinstance(sigma, (list, tuple)) else [float(sigma)] * I
+        key = (tuple((t.data_ptr(), tuple(t.shape)) for t in clean) if clean is not None else None,
+               tuple((t.data_ptr(), tuple(t.shape)) for t in degraded) if degraded is not None else None, tuple(sig), self.cap)
+        plan = self._plans.get(key)
+        if plan is None:
+            for lst in (clean, degraded):
+                for t, r in zip(lst or (), ref):
+                    assert t.dtype == torch.uint8 and t.dim() == 3 and t.shape[0] == 3 and t.is_contiguous() and t.device == self.dev
+                    assert t.shape == r.shape, 'a degraded image must have the shape of its ground truth'
+            sizes = [tuple(t.shape[1:]) for t in ref]
+            ttab, gtab, chunks = plan_tiles(sizes, self.tile, self.cap)
+            itab = np.array([[clean[i].data_ptr() if clean is not None else 0, degraded[i].data_ptr() if degraded is not None else 0,
+                              sizes[i][0], sizes[i][1]] for i in range(I)], dtype=np.int64)
+            up = lambda a: torch.from_numpy(a).to(self.dev)
+            if len(self._plans) >= 8:
+                self._plans.clear()
+            plan = self._plans[key] = dict(
+                I=I, sizes=sizes, chunks=chunks, itab=up(itab), ttab=up(ttab), gtab=up(gtab), sigma=up(np.array(sig, dtype=np.float32)),
+                npix=up(np.array([3.0 * h * w for h, w in sizes], dtype=np.float32)),
+                nwin=up(np.array([3.0 * (h - 6) * (w - 6) for h, w in sizes], dtype=np.float32)),
+                max_px=max(sum(3 * h * w for h, w in sizes[i0:i1]) for i0, i1, _, _ in chunks))
+        return plan
+
+    # ---- the network at one fixed shape ------------------------------------------------------------------------------
+    def _buffers(self, plan):
+        T = self.tile
+        if self.tiles is None:
+            self.tiles = torch.empty((self.cap, 3, T, T), dtype=torch.float32, device=self.dev)
+            self.rest = torch.empty((self.cap, 3, T, T), dtype=torch.float32, device=self.dev)
+            self.gin = torch.zeros((self.tb, 3, T, T), dtype=torch.float32, device=self.dev)
+        if self.packed is None or self.packed.numel() < plan['max_px']:
+            self.packed = torch.empty(plan['max_px'], dtype=torch.float32, device=self.dev)
+
+    def _capture(self):
+        cur = torch.cuda.current_stream()
+        s = torch.cuda.Stream()
+        s.wait_stream(cur)
+        with torch.cuda.stream(s):                           # lazily built tables and operand copies must exist before the capture
+            for _ in range(2):
+                self.net(x_query=self.gin, x_key=self.gin)
+        cur.wait_stream(s)
+        torch.cuda.synchronize()
+        try:
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                self.gout = self.net(x_query=self.gin, x_key=self.gin)
+            self._graph = g
+        except RuntimeError as e:
+            print(f'fwair: EvalEngine could not capture the forward pass ({type(e).__name__}: {e}); running it eagerly', file=sys.stderr)
+            torch.cuda.synchronize()
+            self.use_graph, self._graph, self.gout = False, None, None
+
+    def _forward(self, s, k):
+        """rest[s : s + k] = net(tiles[s : s + k]), k <= tile_batch."""
+        if k == self.tb:
+            self.gin.copy_(self.tiles[s:s + k])
+        else:
+            self.gin[:k].copy_(self.tiles[s:s + k])
+            self.gin[k:].copy_(self.tiles[s:s + 1].expand(self.tb - k, -1, -1, -1))
+        if self.use_graph and self._graph is None:
+            self._capture()
+        if self._graph is not None:
+            self._graph.replay()
+            out = self.gout
+        else:
+            out = self.net(x_query=self.gin, x_key=self.gin)
+        self.rest[s:s + k].copy_(out[:k])
+
+    @torch.no_grad()
+    def run(self, clean_u8, degraded_u8=None, sigma=0, seed=0, want_u8=False, want_f32=False):
+        plan = self._plan(clean_u8, degraded_u8, sigma)
+        self._buffers(plan)
+        seed = int(seed) & 0xFFFFFFFF
+        if seed != self._seed:
+            self.seed_word.fill_(seed - (1 << 32) if seed >= (1 << 31) else seed)
+            self._seed = seed
+        was_training = self.net.training
+        self.net.eval()
+        I, T = plan['I'], self.tile
+        sse = torch.zeros(I, dtype=torch.float32, device=self.dev)
+        ssum = torch.zeros(I, dtype=torch.float32, device=self.dev)
+        u8s, f32s = [], []
+        for i0, i1, t0, t1 in plan['chunks']:
+            n = t1 - t0
+            ttab = plan['ttab'][t0:]
+            call('fw_eval_gather', plan['itab'], ttab, plan['sigma'], self.seed_word, _EVAL_SITE, self.tiles, n, T)
+            for s in range(0, n, self.tb):
+                self._forward(s, min(self.tb, n - s))
+            px = sum(3 * h * w for h, w in plan['sizes'][i0:i1])
+            u8 = torch.empty(px, dtype=torch.uint8, device=self.dev) if want_u8 else None
+            call('fw_eval_blend', plan['itab'], plan['gtab'], ttab, self.rest, self.packed, u8, sse, i0, i1 - i0, n, T)
+            if clean_u8 is not None:
+                call('fw_eval_ssim7', plan['itab'], plan['gtab'], self.packed, ssum, i0, i1 - i0)
+            off = 0
+            for h, w in plan['sizes'][i0:i1]:
+                if want_u8:
+                    u8s.append(u8[off:off + 3 * h * w].view(3, h, w))
+                if want_f32:
+                    f32s.append(self.packed[off:off + 3 * h * w].view(3, h, w).clone())
+                off += 3 * h * w
+        self.net.train(was_training)
+        if clean_u8 is None:
+            out = (None, None)
+        else:
+            out = (10.0 * torch.log10(plan['npix'] / sse), ssum / plan['nwin'])          # val_utils.py:52-63: 10 log10(1 / mse)
+        return out + ((u8s,) if want_u8 else ()) + ((f32s,) if want_f32 else ())

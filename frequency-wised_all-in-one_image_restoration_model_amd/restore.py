@@ -1,0 +1,111 @@
+#!/usr/bin/env python3
+"""Test a checkpoint on the image folders of a data tree, or restore arbitrary images -- the reference's test.py (its name is not
+reused: a `test.py` on sys.path shadows the standard library's `test` package).
+
+    python restore.py --epochs 1000 --output_path output/run/ --test_de_type denoising_bsd68_25 deraining [--data_root data/]
+                      [--ckpt FILE] [--save_imgs True]
+    python restore.py --ckpt FILE --input PATH --output DIR          (PATH: an image or a directory of images; no ground truth, no metrics)
+
+Loads `<output_path>ckpt/epoch_<epochs>.pth` (train.py:126) unless `--ckpt` names a file, restores every test set of `--test_de_type`
+through fwair.evaluate.EvalEngine (tiles of `--crop_test_imgs_size`, test.py:47-71 averaging the RESTORED tiles; Gaussian noise of
+the denoising sets from seed 0, test.py:88) and writes `<output_path>epoch_<epochs>_results.log` in the line format of test.py:96-100.
+`--save_imgs True` also writes `<output_path>epoch_<E>_imgs/test_<task>/<name>.png` (test.py:20-26,77-78).  The model flags
+(`--degradation_embedding_method`, `--compute_dtype`, ...) must be those the checkpoint was trained with.
+"""
+import argparse
+import os
+import sys
+
+_own = argparse.ArgumentParser(add_help=False)
+_own.add_argument('--data_root', type=str, default='data/', help='directory of the <task>_test folders (fwair/data.py)')
+_own.add_argument('--ckpt', type=str, default='', help='checkpoint file (default: <output_path>ckpt/epoch_<epochs>.pth)')
+_own.add_argument('--input', type=str, default='', help='an image, or a directory of images, to restore without ground truth')
+_own.add_argument('--output', type=str, default='', help='where --input images are written')
+_own.add_argument('--tile_batch', type=int, default=64, help='tiles per forward pass')
+_own.add_argument('--no_graph', action='store_true', help='eager launches instead of HIP-graph replay')
+_ARGS, _rest = _own.parse_known_args()
+sys.argv = [sys.argv[0]] + _rest                       # option.py parses sys.argv at import (reference option.py:3)
+
+import torch                                            # noqa: E402
+
+from fwair.data import FolderTestSet, load_u8          # noqa: E402
+from fwair.evaluate import EvalEngine                   # noqa: E402
+from net.model import AirNet                            # noqa: E402
+from option import options as opt                       # noqa: E402
+
+_ENGINE = {}
+
+
+def _engine(net):
+    if _ENGINE.get('net') is not net:
+        _ENGINE.update(net=net, engine=EvalEngine(net, tile=opt.crop_test_imgs_size, tile_batch=_ARGS.tile_batch, use_graph=not _ARGS.no_graph))
+    return _ENGINE['engine']
+
+
+def save_u8(img, path):
+    """utils/image_io.py:375-391 on the uint8 image fw_eval_blend wrote: [3, H, W] -> PNG."""
+    from PIL import Image
+    Image.fromarray(img.cpu().numpy().transpose(1, 2, 0)).save(path)
+
+
+def test_by_task(net, task, epochs):
+    """test.py:17-84 -> 'PSNR/SSIM: %.2f/%.4f' (means over the images of the set, AverageMeter with N = 1 per image)."""
+    print('starting testing %s...' % (task))
+    dev = next(net.parameters()).device
+    ts = FolderTestSet(_ARGS.data_root, task)
+    clean, degraded = ts.load(dev)
+    for im in clean:
+        H, W = im.shape[1:]
+        assert H >= opt.crop_test_imgs_size and W >= opt.crop_test_imgs_size, "invalid test image size (%d, %d)" % (H, W)     # test.py:43
+    out = _engine(net).run(clean, degraded, sigma=ts.sigma, seed=0, want_u8=bool(opt.save_imgs))
+    if opt.save_imgs:
+        output_path = opt.output_path + 'epoch_%s_imgs/' % str(epochs) + 'test_' + task + '/'
+        os.makedirs(output_path, exist_ok=True)
+        for name, img in zip(ts.names, out[2]):
+            save_u8(img, output_path + name + '.png')
+    result = 'PSNR/SSIM: %.2f/%.4f' % (float(out[0].mean()), float(out[1].mean()))
+    print(result)
+    return result
+
+
+def restore_files(net, src, dst):
+    """--input / --output: every image of `src` (cropped to multiples of 16 as the datasets do), restored, written as <name>.png."""
+    paths = sorted(os.path.join(src, f) for f in os.listdir(src)) if os.path.isdir(src) else [src]
+    dev = next(net.parameters()).device
+    imgs = []
+    for p in paths:
+        im = load_u8(p)
+        H, W = im.shape[1:]
+        assert H >= opt.crop_test_imgs_size and W >= opt.crop_test_imgs_size, "invalid test image size (%d, %d)" % (H, W)
+        imgs.append(torch.from_numpy(im).to(dev))
+    os.makedirs(dst, exist_ok=True)
+    _, _, out = _engine(net).run(None, imgs, want_u8=True)
+    for p, img in zip(paths, out):
+        save_u8(img, os.path.join(dst, os.path.basename(p).split('.')[0] + '.png'))
+    return len(paths)
+
+
+def main():
+    torch.cuda.set_device(opt.cuda)
+    dev = torch.device('cuda', opt.cuda)
+    path = _ARGS.ckpt or opt.ckpt_path + 'epoch_%s.pth' % str(opt.epochs)
+    sd = torch.load(path, map_location=dev, weights_only=True)
+    if 'E.E.queue' in sd:
+        opt.batch_size = sd['E.E.queue'].shape[-1] // 3       # MoCo queue K = 3 * the training batch (net/model.py:35)
+    net = AirNet(opt).to(dev)
+    net.load_state_dict(sd)
+    net.eval()
+    if _ARGS.input:
+        assert _ARGS.output, '--input needs --output DIR'
+        n = restore_files(net, _ARGS.input, _ARGS.output)
+        print('restored %d images into %s' % (n, _ARGS.output))
+        return
+    os.makedirs(opt.output_path, exist_ok=True)
+    with open(os.path.join(opt.output_path, 'epoch_%s_results.log' % str(opt.epochs)), 'w') as result_log_file:
+        for task in opt.test_de_type:
+            result = test_by_task(net, task=task, epochs=opt.epochs)
+            result_log_file.write(task + ': ' + ' ' * (25 - len(task)) + result + '\n')
+
+
+if __name__ == '__main__':
+    main()

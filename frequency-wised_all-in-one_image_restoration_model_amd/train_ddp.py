@@ -13,7 +13,12 @@ per-epoch checkpoints and resume (`--save_every`, `--resume`; optimizer moments 
 
 Data: the reference's `utils.dataset_utils.TrainDataset` when that package is importable (put the reference root on
 PYTHONPATH behind this directory) -- each rank draws its own shard; `--synthetic_steps N` trains on N synthetic batches
-per epoch instead (no dataset on disk needed).
+per epoch instead (no dataset on disk needed).  `--data_root DIR` reads the image folders of DIR (the reference's `data/` tree, see
+fwair/data.py) without the reference or torchvision: the training images are decoded once and kept in HBM, every batch is one
+fw_train_batch launch (fwair.data.FolderTrainSet), and the per-epoch evaluation restores the `<task>_test` folders through
+fwair.evaluate.EvalEngine.
+
+    python train_ddp.py --data_root data/ --de_type denoising_15 denoising_25 denoising_50 deraining dehazing ... [--items_per_task 400]
 """
 import argparse
 import os
@@ -27,6 +32,9 @@ _own.add_argument('--resume', type=str, default='', help='checkpoint epoch_<E>.p
 _own.add_argument('--save_every', type=int, default=0, help='also checkpoint every this many epochs')
 _own.add_argument('--no_graph', action='store_true', help='eager launches instead of HIP-graph replay')
 _own.add_argument('--no_eval', action='store_true', help='skip the per-epoch evaluation / results.log of train.py:131-139')
+_own.add_argument('--data_root', type=str, default='', help='train and evaluate on the image folders of this directory (fwair/data.py)')
+_own.add_argument('--items_per_task', type=int, default=400, help='items per task and epoch with --data_root (dataset_utils.py:144)')
+_own.add_argument('--data_cache_gb', type=float, default=48, help='device memory the decoded training set may take with --data_root')
 _ARGS, _rest = _own.parse_known_args()
 sys.argv = [sys.argv[0]] + _rest                       # option.py parses sys.argv at import (reference option.py:3)
 
@@ -53,7 +61,17 @@ def sigma_of(task):
 _LOADER = []                  # (dataset, sampler, loader): built once -- a DataLoader with `num_workers` processes per epoch is a fork storm
 
 
+_FOLDERS = {}                 # --data_root: the training set and the test sets, decoded once and resident in HBM
+
+
 def batches(epoch, rank, world, B, dev):
+    if _ARGS.data_root:
+        if 'train' not in _FOLDERS:
+            from fwair.data import FolderTrainSet
+            _FOLDERS['train'] = FolderTrainSet(_ARGS.data_root, opt.de_type, opt.patch_size, dev, rank=rank, world=world, per_gpu_batch=B,
+                                               items_per_task=_ARGS.items_per_task, seed=1234, cache_gb=_ARGS.data_cache_gb)
+        yield from _FOLDERS['train'].epoch(epoch)
+        return
     if _ARGS.synthetic_steps > 0:
         sig = [sigma_of(t) for t in opt.de_type] or [25]
         mixed = any(not t.startswith('denoising_') or t.endswith('_0') for t in opt.de_type)
@@ -84,7 +102,10 @@ def evaluate_tasks(net, epoch, dev, results):
     The tiles are restored by fwair.evaluate.tiled_restore (test.py:48-71 on the device, averaging the RESTORED tiles).  With
     `--synthetic_steps` the test images are synthetic too (4 images of 1.5 x patch_size per task); otherwise the reference's
     TestDataset is read.  PSNR and SSIM (utils/val_utils.py:50-66) are computed on the device (fwair.evaluate: fw_ssim7 restates
-    skimage's structural_similarity defaults)."""
+    skimage's structural_similarity defaults).  With `--data_root` the `<task>_test` folders are restored a test set at a time by
+    fwair.evaluate.EvalEngine (noise seed 0, as test.py:88 seeds)."""
+    if _ARGS.data_root:
+        return evaluate_folders(net, epoch, dev, results)
     from fwair import augment as A
     from fwair.evaluate import psnr, ssim, tiled_restore
     results.write('%s Epochs Results:\n' % str(epoch + 1))
@@ -110,6 +131,23 @@ def evaluate_tasks(net, epoch, dev, results):
                 rest = tiled_restore(net, inp.to(dev), opt.crop_test_imgs_size)
                 vals.append(psnr(rest, cl.to(dev))); svals.append(ssim(rest, cl.to(dev)))
         result = 'PSNR/SSIM: %.2f/%.4f' % (sum(vals) / len(vals) if vals else float('nan'), sum(svals) / len(svals) if svals else float('nan'))
+        results.write(task + ': ' + ' ' * (25 - len(task)) + result + '\n')
+    results.flush()
+    net.train()
+
+
+def evaluate_folders(net, epoch, dev, results):
+    from fwair.data import FolderTestSet
+    from fwair.evaluate import EvalEngine
+    results.write('%s Epochs Results:\n' % str(epoch + 1))
+    engine = EvalEngine(net, tile=opt.crop_test_imgs_size, use_graph=not _ARGS.no_graph)    # captured anew: the weights of this epoch
+    for task in opt.test_de_type:
+        if task not in _FOLDERS:
+            ts = FolderTestSet(_ARGS.data_root, task)
+            _FOLDERS[task] = (ts,) + ts.load(dev)
+        ts, clean, degraded = _FOLDERS[task]
+        p, s = engine.run(clean, degraded, sigma=ts.sigma, seed=0)
+        result = 'PSNR/SSIM: %.2f/%.4f' % (float(p.mean()), float(s.mean()))                # the one host sync of the test set
         results.write(task + ': ' + ' ' * (25 - len(task)) + result + '\n')
     results.flush()
     net.train()

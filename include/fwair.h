@@ -322,6 +322,25 @@ int fw_tile_blend(const float* tiles, const int* ys, const int* xs, float* out, 
 /* utils/val_utils.py:50-66 (skimage structural_similarity defaults: 7x7 uniform window, K1 .01, K2 .03, sample covariance, 3-pixel
  * border cropped, inputs clipped to [0, 1]): out[i] += sum of the SSIM map of image i over channels and interior pixels. */
 int fw_ssim7(const float* a, const float* b, float* out, int n, int C, int H, int W, void* stream);
+/* The same three steps for a CHUNK of test images of different sizes, one launch each, driven by tables in device memory
+ * (fwair/evaluate.py EvalEngine).  itab: int64 [I][4] = {clean u8 [3][H][W] or 0, degraded u8 or 0, H, W}; ttab: int32 [N][4] =
+ * {image, y0, x0, 0}, the tiles of the chunk, image by image, rows major; gtab: int64 [I][4] = {offset of the image in the packed
+ * buffer (elements), its first tile in the chunk, ny, nx}.  T % 4 == 0.
+ * fw_eval_gather (test.py:47-57 on utils/dataset_utils.py:174-185): tiles f32 [N][3][T][T] = the degraded image / 255 where one is
+ * given; otherwise the clean image with the test set's noise synthesised in the kernel, floor(clip(g + z * sigma[image], 0, 255)) / 255,
+ * z = the counter-based N(0, 1) of fw_train_batch at (seed[0], site + image, flat CHW pixel index of the full image): overlapping
+ * tiles see the same noisy image, which is never stored.  sigma[image] = 0: the clean image itself. */
+int fw_eval_gather(const void* itab, const int* ttab, const float* sigma, const void* seed, int site, float* tiles, int N, int T,
+                   void* stream);
+/* test.py:61-71 with the RESTORED tiles for images i0 .. i0 + nimg - 1 (ttab: the chunk's tiles, ntiles of them; rest: f32
+ * [ntiles][3][T][T]): packed[gtab offset ..] = the overlap average, f32 [3][H][W] per image; sse[image] += sum of (clip(restored) -
+ * clean / 255)^2 over the image (utils/val_utils.py:52-63; skipped without a clean image), one atomic per workgroup; u8out (or 0):
+ * (uint8) clip(restored * 255, 0, 255) at the same offsets (utils/image_io.py:383). */
+int fw_eval_blend(const void* itab, const void* gtab, const int* ttab, const float* rest, float* packed, void* u8out, float* sse,
+                  int i0, int nimg, int ntiles, int T, void* stream);
+/* utils/val_utils.py:64 as fw_ssim7 computes it, between the packed restored images and the clean uint8 images of the tables:
+ * out[image] += sum of the SSIM map over channels and interior pixels, for images i0 .. i0 + nimg - 1. */
+int fw_eval_ssim7(const void* itab, const void* gtab, const float* packed, float* out, int i0, int nimg, void* stream);
 
 /* ---- fused LeFF forward (net/utils/leff.py:92-117) for the high-resolution stages, bf16 operands ----------------------------
  * y = res + rowscale * linear2(GELU(dwconv3x3(GELU(linear1(xn))))) in one kernel per 8 x 16 pixel patch: the hidden tensor is
