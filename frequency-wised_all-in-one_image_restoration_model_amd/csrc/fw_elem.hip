@@ -876,211 +876,266 @@ __global__ void colsum_t_kernel(const T* __restrict__ x, long ldx, float* __rest
 }
 
 // ------------------------------------------------------------------------------------------------
-// InputProj: 3x3 conv 3 -> C + LeakyReLU(0.01) on an NCHW f32 image  (decoder_Uformer.py:453-472)
+// The 3-channel convolutions at the two ends of the network, in tile form
+//   InputProj : 3x3 conv 3 -> C + LeakyReLU(0.01) on an NCHW f32 image      (decoder_Uformer.py:453-472)
+//   OutputProj: 3x3 conv C -> 3 on tokens, + global residual, NCHW f32 out  (decoder_Uformer.py:476-499,1171)
+// A workgroup walks 8x32-pixel tiles (persistent loop).  The 3-plane side of the convolution (the image, or dout) is staged
+// per tile as a zero-padded 3 x 10 x 34 halo patch in LDS -- read from clamped coordinates and zeroed by a select, the patch of
+// the NEXT tile requested before the current one is computed; the token-major side (out, dy, fea, dfea) moves once, as 16-byte
+// pieces of whole rows: thread = (channel quad q, pixel lane), consecutive threads hold consecutive quads of one token.
 // ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void inproj_fwd_kernel(const float* __restrict__ img, const float* __restrict__ w, const float* __restrict__ bias,
-                                                         float* __restrict__ out, long ldo, int B, int H, int W, int C, float slope) {
-    extern __shared__ __attribute__((aligned(16))) float sm[];         // tap-major weights [27][C] + bias [C]
-    for (int i = threadIdx.x; i < C * 27; i += 256) sm[(i % 27) * C + i / 27] = w[i];
-    for (int i = threadIdx.x; i < C; i += 256) sm[27 * C + i] = bias[i];
-    __syncthreads();
-    const int c4n = C >> 2;
-    const long total = (long)B * H * W * c4n;
-    for (long i = gtid(); i < total; i += gstride()) {
-        const int c = (int)(i % c4n) * 4; const long tok = i / c4n;
-        const int x = (int)(tok % W); const int y = (int)((tok / W) % H); const long b = tok / ((long)W * H);
-        f32x4 acc = *reinterpret_cast<const f32x4*>(sm + 27 * C + c);
-        // branch-free: the 27 taps are read from clamped coordinates (independent loads, issued together) and zeroed by a select --
-        // a load under a lane-varying branch is waited for before the next one is issued (137 us per launch with the branches)
-        float px[27];
+constexpr int EC_TY = 8, EC_TX = 32, EC_PH = EC_TY + 2, EC_PW = EC_TX + 2, EC_PLANE = EC_PH * EC_PW, EC_PN = 3 * EC_PLANE, EC_PIX = EC_TY * EC_TX;
+constexpr int EC_PREG = (EC_PN + 255) / 256;
+struct EcTiles {
+    int tx, ty; long n;
+    __device__ EcTiles(int B, int H, int W) : tx((W + EC_TX - 1) / EC_TX), ty((H + EC_TY - 1) / EC_TY) { n = (long)B * tx * ty; }
+    __device__ void at(long t, long& b, int& y0, int& x0) const { x0 = (int)(t % tx) * EC_TX; y0 = (int)((t / tx) % ty) * EC_TY; b = t / ((long)tx * ty); }
+};
+// the halo patch of tile t of src[B][3][H][W] into registers: clamped coordinates, zero outside the image (all loads independent)
+FW_DEV void ec_patch_load(float (&r)[EC_PREG], const float* __restrict__ src, const EcTiles& T, long t, int H, int W) {
+    long b; int y0, x0;
+    T.at(t, b, y0, x0);
 #pragma unroll
-        for (int ci = 0; ci < 3; ++ci)
-#pragma unroll
-            for (int ky = 0; ky < 3; ++ky) {
-                int yy = y + ky - 1; yy = yy < 0 ? 0 : (yy >= H ? H - 1 : yy);
-#pragma unroll
-                for (int kx = 0; kx < 3; ++kx) {
-                    int xx = x + kx - 1; xx = xx < 0 ? 0 : (xx >= W ? W - 1 : xx);
-                    px[ci * 9 + ky * 3 + kx] = img[((b * 3 + ci) * H + yy) * W + xx];
-                }
-            }
-#pragma unroll
-        for (int ky = 0; ky < 3; ++ky) {
-            const bool yok = y + ky - 1 >= 0 && y + ky - 1 < H;
-#pragma unroll
-            for (int kx = 0; kx < 3; ++kx) {
-                const bool ok = yok && x + kx - 1 >= 0 && x + kx - 1 < W;
-#pragma unroll
-                for (int ci = 0; ci < 3; ++ci)
-                    acc += *reinterpret_cast<const f32x4*>(sm + (ci * 9 + ky * 3 + kx) * C + c) * (ok ? px[ci * 9 + ky * 3 + kx] : 0.f);
-            }
-        }
-        for (int e = 0; e < 4; ++e) acc[e] = lrelu_f(acc[e], slope);
-        *reinterpret_cast<f32x4*>(out + tok * ldo + c) = acc;
+    for (int k = 0; k < EC_PREG; ++k) {
+        int i = threadIdx.x + k * 256; i = i < EC_PN ? i : EC_PN - 1;
+        const int ci = i / EC_PLANE, rem = i % EC_PLANE;
+        const int y = y0 + rem / EC_PW - 1, x = x0 + rem % EC_PW - 1;
+        const bool ok = y >= 0 && y < H && x >= 0 && x < W;
+        const int yc = y < 0 ? 0 : (y >= H ? H - 1 : y), xc = x < 0 ? 0 : (x >= W ? W - 1 : x);
+        const float v = src[((b * 3 + ci) * H + yc) * W + xc];
+        r[k] = ok ? v : 0.f;
     }
 }
-// dw[c][ci][ky][kx] += sum_t dy'[t][c] img[..];  db[c] += sum_t dy'[t][c];   dy' = dy * lrelu'(out)
-template <int STRIPE>
-__global__ __launch_bounds__(256) void inproj_bwd_kernel(const float* __restrict__ img, const float* __restrict__ out, long ldo, const float* __restrict__ dy, long ldy,
-                                                         float* __restrict__ dw, float* __restrict__ db, int B, int H, int W, int C, float slope) {
-    extern __shared__ float red[];                       // [C][28]: block partials before ONE atomic per word
-    for (int i = threadIdx.x; i < C * 28; i += 256) red[i] = 0.f;
+FW_DEV void ec_patch_store(const float (&r)[EC_PREG], float* patch) {
+#pragma unroll
+    for (int k = 0; k < EC_PREG; ++k) { const int i = threadIdx.x + k * 256; if (i < EC_PN) patch[i] = r[k]; }
+}
+
+// out[tok][4q..4q+3] = sum_{ci,py,px} patch[ci][ty+py][tx+px] * wr[ci][py][px]: the 27 x 4 weights and the bias of a lane's quad
+// live in registers for the whole launch.
+//   MODE 0  InputProj forward: src = image, wr = w[c][ci][py][px], + bias, LeakyReLU
+//   MODE 1  OutputProj data gradient: src = dout, dfea[tok][c] = sum dout[co][tok - tap] w[co][c][tap], i.e. wr = w[co][c][2-py][2-px]
+template <int MODE>
+__global__ __launch_bounds__(256) void edge_conv3_rows_kernel(const float* __restrict__ src, const float* __restrict__ w, const float* __restrict__ bias,
+                                                              float* __restrict__ out, long ldo, int B, int H, int W, int C, float slope) {
+    __shared__ float patch[2][EC_PN];
+    const int c4n = C >> 2, PL = 256 / c4n;
+    const int q = threadIdx.x % c4n, pl = threadIdx.x / c4n;
+    f32x4 wr[27], bq = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int t = 0; t < 27; ++t)
+#pragma unroll
+        for (int e = 0; e < 4; ++e)
+            wr[t][e] = MODE == 0 ? w[(4 * q + e) * 27 + t] : w[((long)(t / 9) * C + 4 * q + e) * 9 + 8 - t % 9];
+    if (MODE == 0) bq = *reinterpret_cast<const f32x4*>(bias + 4 * q);
+    const EcTiles T(B, H, W);
+    float pr[EC_PREG];
+    long t = blockIdx.x;
+    if (t < T.n) { ec_patch_load(pr, src, T, t, H, W); ec_patch_store(pr, patch[0]); }
     __syncthreads();
-    const long ntok = (long)B * H * W;
-    const long nstripes = (ntok + STRIPE - 1) / STRIPE;
-    for (long i = gtid(); i < nstripes * C; i += gstride()) {
-        const int c = (int)(i % C); const long st = i / C;
-        float g[27], gb = 0.f;
+    for (int cur = 0; t < T.n; t += gridDim.x, cur ^= 1) {
+        const bool more = t + gridDim.x < T.n;
+        if (more) ec_patch_load(pr, src, T, t + gridDim.x, H, W);
+        long b; int y0, x0;
+        T.at(t, b, y0, x0);
+        const float* pc = patch[cur];
+        if (pl < PL)
+            for (int p = pl; p < EC_PIX; p += PL) {
+                const int ty = p / EC_TX, tx = p % EC_TX, y = y0 + ty, x = x0 + tx;
+                const float* pp = pc + ty * EC_PW + tx;
+                f32x4 acc = bq;
+                // summation order: filter taps (ky, kx) ascending, plane innermost, a padded tap adding w * 0 -- the order of the per-token
+                // kernels this one replaces, so out / dfea keep their bits (the MFMA forward and the weight gradients sum in another order)
 #pragma unroll
-        for (int t = 0; t < 27; ++t) g[t] = 0.f;
-        for (long tok = st * STRIPE; tok < ntok && tok < (st + 1) * STRIPE; ++tok) {
-            const int x = (int)(tok % W); const int y = (int)((tok / W) % H); const long b = tok / ((long)W * H);
-            // branch-free: the 27 image taps are read from clamped coordinates (independent loads, issued together) and
-            // zeroed by a 0/1 factor -- a load under a lane-varying branch is waited for before the next one is issued
-            float px[27];
+                for (int ky = 0; ky < 3; ++ky)
 #pragma unroll
-            for (int ci = 0; ci < 3; ++ci)
+                    for (int kx = 0; kx < 3; ++kx)
 #pragma unroll
-                for (int ky = 0; ky < 3; ++ky) {
-                    int yy = y + ky - 1; yy = yy < 0 ? 0 : (yy >= H ? H - 1 : yy);
+                        for (int ci = 0; ci < 3; ++ci) {
+                            const int py = MODE == 0 ? ky : 2 - ky, px = MODE == 0 ? kx : 2 - kx;
+                            acc += wr[ci * 9 + py * 3 + px] * pp[ci * EC_PLANE + py * EC_PW + px];
+                        }
+                if (MODE == 0)
 #pragma unroll
-                    for (int kx = 0; kx < 3; ++kx) {
-                        int xx = x + kx - 1; xx = xx < 0 ? 0 : (xx >= W ? W - 1 : xx);
-                        px[ci * 9 + ky * 3 + kx] = img[((b * 3 + ci) * H + yy) * W + xx];
-                    }
-                }
-            float d = dy[tok * ldy + c];
-            const float o = out[tok * ldo + c];
-            d = o <= 0.f ? d * slope : d;
-            gb += d;
-#pragma unroll
-            for (int ky = 0; ky < 3; ++ky) {
-                const float dyk = (y + ky - 1 >= 0 && y + ky - 1 < H) ? d : 0.f;
-#pragma unroll
-                for (int kx = 0; kx < 3; ++kx) {
-                    const float dk = (x + kx - 1 >= 0 && x + kx - 1 < W) ? dyk : 0.f;
-#pragma unroll
-                    for (int ci = 0; ci < 3; ++ci) g[ci * 9 + ky * 3 + kx] += dk * px[ci * 9 + ky * 3 + kx];
-                }
+                    for (int e = 0; e < 4; ++e) acc[e] = lrelu_f(acc[e], slope);
+                if (y < H && x < W) *reinterpret_cast<f32x4*>(out + ((b * H + y) * W + x) * ldo + 4 * q) = acc;
             }
-        }
-        atomicAdd(&red[c * 28 + 27], gb);
-        for (int t = 0; t < 27; ++t) atomicAdd(&red[c * 28 + t], g[t]);
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < C * 28; i += 256) {
-        const int c = i / 28, t = i % 28;
-        if (t < 27) atomicAdd(dw + c * 27 + t, red[i]); else atomicAdd(db + c, red[i]);
+        if (more) ec_patch_store(pr, patch[cur ^ 1]);
+        __syncthreads();
     }
 }
 
-// ------------------------------------------------------------------------------------------------
-// OutputProj: 3x3 conv C -> 3 on tokens, + global residual, NCHW f32 out  (decoder_Uformer.py:476-499,1171)
-// ------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void outproj_fwd_kernel(const float* __restrict__ fea, long ldf, const float* __restrict__ w, const float* __restrict__ bias,
-                                                          const float* __restrict__ img, float* __restrict__ out, int B, int H, int W, int C) {
-    extern __shared__ __attribute__((aligned(16))) float sm[];         // weights as [tap][co][C]
-    for (int i = threadIdx.x; i < 3 * C * 9; i += 256) { const int tap = i % 9, cc = (i / 9) % C, co = i / (9 * C); sm[(tap * 3 + co) * C + cc] = w[i]; }
+// Weight + bias gradients: a [28] x tokens x C reduction.  The token-major operand is read once (V channels per lane, 16 bytes at
+// V = 4), U tokens in flight per lane; the 27 taps come from the LDS patch; a lane keeps its 27 x V + V partials in registers over
+// the whole persistent loop.  One fold per workgroup: the partials of one channel slot go through LDS ([28][256], plain stores,
+// conflict-free), 28 x C/V threads sum the pixel lanes and add ONE atomic per word (at most 512 workgroups per launch).
+//   MODE 0  InputProj: src = image, d = dy * lrelu'(out) (sign of out), dw[c][ci][py][px], db[c]
+//   MODE 1  OutputProj: src = dout, d = fea; dw[co][c][ky][kx] = sum_tok fea[tok][c] dout[co][tok - (ky-1, kx-1)], i.e. patch tap
+//           (2-ky, 2-kx); db[co] = sum of the centre taps (taken from the q = 0 lanes)
+template <int V, int MODE>
+__global__ __launch_bounds__(256, 2) void edge_conv3_wgrad_kernel(const float* __restrict__ src, const float* __restrict__ a, long lda, const float* __restrict__ o,
+                                                                  long ldo, float* __restrict__ dw, float* __restrict__ db, int B, int H, int W, int C, float slope) {
+    constexpr int U = 4;
+    __shared__ float patch[2][EC_PN];
+    __shared__ float red[28 * 256];
+    const int cvn = C / V, PL = 256 / cvn;
+    const int q = threadIdx.x % cvn, pl = threadIdx.x / cvn;
+    float g[27][V], gb[V];
+#pragma unroll
+    for (int e = 0; e < V; ++e) {
+        gb[e] = 0.f;
+#pragma unroll
+        for (int t = 0; t < 27; ++t) g[t][e] = 0.f;
+    }
+    const EcTiles T(B, H, W);
+    float pr[EC_PREG];
+    long t = blockIdx.x;
+    if (t < T.n) { ec_patch_load(pr, src, T, t, H, W); ec_patch_store(pr, patch[0]); }
     __syncthreads();
-    const long total = (long)B * H * W;
-    for (long tok = gtid(); tok < total; tok += gstride()) {
-        const int x = (int)(tok % W); const int y = (int)((tok / W) % H); const long b = tok / ((long)W * H);
-        f32x4 a0 = f32x4{0.f, 0.f, 0.f, 0.f}, a1 = a0, a2 = a0;
-        for (int ky = 0; ky < 3; ++ky) {
-            const int yy = y + ky - 1;
-            if (yy < 0 || yy >= H) continue;
-            for (int kx = 0; kx < 3; ++kx) {
-                const int xx = x + kx - 1;
-                if (xx < 0 || xx >= W) continue;
-                const float* f = fea + ((b * H + yy) * W + xx) * ldf;
-                const float* wt = sm + (ky * 3 + kx) * 3 * C;
-                for (int c = 0; c < C; c += 4) {
-                    const f32x4 v = *reinterpret_cast<const f32x4*>(f + c);
-                    a0 += v * *reinterpret_cast<const f32x4*>(wt + c);
-                    a1 += v * *reinterpret_cast<const f32x4*>(wt + C + c);
-                    a2 += v * *reinterpret_cast<const f32x4*>(wt + 2 * C + c);
+    for (int cur = 0; t < T.n; t += gridDim.x, cur ^= 1) {
+        const bool more = t + gridDim.x < T.n;
+        if (more) ec_patch_load(pr, src, T, t + gridDim.x, H, W);
+        long b; int y0, x0;
+        T.at(t, b, y0, x0);
+        const float* pc = patch[cur];
+        if (pl < PL)
+            for (int p0 = pl; p0 < EC_PIX; p0 += U * PL) {
+                float d[U][V], ov[U][V];
+                int off[U]; bool ok[U];
+                // phase 1: every load of the U tokens, from clamped coordinates
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    const int p = p0 + u * PL, pin = p < EC_PIX ? p : EC_PIX - 1;
+                    const int ty = pin / EC_TX, tx = pin % EC_TX, y = y0 + ty, x = x0 + tx;
+                    ok[u] = p < EC_PIX && y < H && x < W;
+                    off[u] = ty * EC_PW + tx;
+                    const long tok = (b * H + (y < H ? y : H - 1)) * W + (x < W ? x : W - 1);
+                    if (V == 4) {
+                        *reinterpret_cast<f32x4*>(d[u]) = *reinterpret_cast<const f32x4*>(a + tok * lda + 4 * q);
+                        if (MODE == 0) *reinterpret_cast<f32x4*>(ov[u]) = *reinterpret_cast<const f32x4*>(o + tok * ldo + 4 * q);
+                    } else {
+#pragma unroll
+                        for (int e = 0; e < V; ++e) { d[u][e] = a[tok * lda + V * q + e]; if (MODE == 0) ov[u][e] = o[tok * ldo + V * q + e]; }
+                    }
+                }
+                // phase 2: fix-ups and the 27 x V multiply-adds per token
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+#pragma unroll
+                    for (int e = 0; e < V; ++e) {
+                        float v = d[u][e];
+                        if (MODE == 0) v = ov[u][e] <= 0.f ? v * slope : v;
+                        d[u][e] = ok[u] ? v : 0.f;
+                    }
+                    const float* pp = pc + off[u];
+                    if (MODE == 0) {
+#pragma unroll
+                        for (int e = 0; e < V; ++e) gb[e] += d[u][e];
+                    } else {
+#pragma unroll
+                        for (int e = 0; e < V && e < 3; ++e) gb[e] += ok[u] ? pp[e * EC_PLANE + EC_PW + 1] : 0.f;
+                    }
+#pragma unroll
+                    for (int ci = 0; ci < 3; ++ci)
+#pragma unroll
+                        for (int py = 0; py < 3; ++py)
+#pragma unroll
+                            for (int px = 0; px < 3; ++px) {
+                                const float tap = pp[ci * EC_PLANE + py * EC_PW + px];
+#pragma unroll
+                                for (int e = 0; e < V; ++e) g[ci * 9 + py * 3 + px][e] += d[u][e] * tap;
+                            }
                 }
             }
-        }
-        const long p = (b * 3 * H + y) * W + x;
-        const long hw = (long)H * W;
-        out[p] = bias[0] + a0[0] + a0[1] + a0[2] + a0[3] + (img ? img[p] : 0.f);
-        out[p + hw] = bias[1] + a1[0] + a1[1] + a1[2] + a1[3] + (img ? img[p + hw] : 0.f);
-        out[p + 2 * hw] = bias[2] + a2[0] + a2[1] + a2[2] + a2[3] + (img ? img[p + 2 * hw] : 0.f);
+        if (more) ec_patch_store(pr, patch[cur ^ 1]);
+        __syncthreads();
     }
-}
-// dfea[tok][c] = sum_{co,tap} dout[co][tok - tap] w[co][c][tap]
-__global__ __launch_bounds__(256) void outproj_bwd_data_kernel(const float* __restrict__ dout, const float* __restrict__ w, float* __restrict__ dfea, long ldf,
-                                                               int B, int H, int W, int C) {
-    extern __shared__ __attribute__((aligned(16))) float sm[];         // weights as [tap][co][C]
-    for (int i = threadIdx.x; i < 3 * C * 9; i += 256) { const int tap = i % 9, cc = (i / 9) % C, co = i / (9 * C); sm[(tap * 3 + co) * C + cc] = w[i]; }
-    __syncthreads();
-    const int c4n = C >> 2;
-    const long total = (long)B * H * W * c4n;
-    for (long i = gtid(); i < total; i += gstride()) {
-        const int c = (int)(i % c4n) * 4; const long tok = i / c4n;
-        const int x = (int)(tok % W); const int y = (int)((tok / W) % H); const long b = tok / ((long)W * H);
-        f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+    // the fold: one channel slot e at a time through red[28][256]
 #pragma unroll
-        for (int ky = 0; ky < 3; ++ky) {
-            const int yo = y - ky + 1;
-            if (yo < 0 || yo >= H) continue;
+    for (int e = 0; e < V; ++e) {
+        if (e) __syncthreads();
 #pragma unroll
-            for (int kx = 0; kx < 3; ++kx) {
-                const int xo = x - kx + 1;
-                if (xo < 0 || xo >= W) continue;
-#pragma unroll
-                for (int co = 0; co < 3; ++co)
-                    acc += *reinterpret_cast<const f32x4*>(sm + ((ky * 3 + kx) * 3 + co) * C + c) * dout[((b * 3 + co) * H + yo) * W + xo];
+        for (int k = 0; k < 27; ++k) red[k * 256 + threadIdx.x] = g[k][e];
+        red[27 * 256 + threadIdx.x] = gb[e];
+        __syncthreads();
+        for (int i = threadIdx.x; i < cvn * 28; i += 256) {
+            const int qq = i % cvn, k = i / cvn, c = qq * V + e;
+            float s = 0.f;
+            for (int p = 0; p < PL; ++p) s += red[k * 256 + p * cvn + qq];
+            if (MODE == 0) {
+                atomicAdd(k < 27 ? dw + c * 27 + k : db + c, s);
+            } else if (k < 27) {
+                atomicAdd(dw + ((long)(k / 9) * C + c) * 9 + 8 - k % 9, s);
+            } else if (qq == 0 && e < 3) {
+                atomicAdd(db + e, s);
             }
         }
-        *reinterpret_cast<f32x4*>(dfea + tok * ldf + c) = acc;
     }
 }
-template <int STRIPE>
-__global__ __launch_bounds__(256) void outproj_bwd_w_kernel(const float* __restrict__ dout, const float* __restrict__ fea, long ldf, float* __restrict__ dw,
-                                                            float* __restrict__ db, int B, int H, int W, int C) {
-    extern __shared__ float red[];                       // [C][27] + [3]
-    for (int i = threadIdx.x; i < C * 27 + 3; i += 256) red[i] = 0.f;
+
+// OutputProj forward on the f32 MFMA.  Per tile the 10 x 34 halo pixels are the rows of a [340][C] x [C][27] product
+// prod[pixel][co*9 + tap] = fea[pixel] . w[co][:, tap]: a wave takes 16 halo pixels at a time, its A fragments are 16-byte pieces of
+// the token rows straight from memory (read once, 64 contiguous bytes per row and load; rows outside the image are zeroed by a
+// select), the B fragments (the weights, zero-padded to 32 columns) sit in LDS in fragment order.  The products go to LDS; each
+// output pixel then adds its 9 shifted entries per plane, the bias and the residual image, and is stored along x.
+constexpr int OP_PS = 33;                                   // prod row stride (floats): the 9-entry gather is conflict-free
+__global__ __launch_bounds__(256) void outproj_fwd_mfma_kernel(const float* __restrict__ fea, long ldf, const float* __restrict__ w, const float* __restrict__ bias,
+                                                               const float* __restrict__ img, float* __restrict__ out, int B, int H, int W, int C) {
+    extern __shared__ __attribute__((aligned(16))) float sm[];
+    const int KC = (C + 15) >> 4;                          // 64-byte k-chunks of a token row
+    uint4* wl = reinterpret_cast<uint4*>(sm);               // [KC][2][64 lanes] B fragments
+    float* prod = sm + KC * 2 * 64 * 4;                     // [352][OP_PS]
+    for (int i = threadIdx.x; i < KC * 2 * 64 * 4; i += 256) {
+        const int s = i & 3, l = (i >> 2) & 63, nt = (i >> 8) & 1, ch = i >> 9;
+        const int k = ch * 16 + 4 * (l >> 4) + s, n = nt * 16 + (l & 15);
+        sm[i] = (k < C && n < 27) ? w[((long)(n / 9) * C + k) * 9 + n % 9] : 0.f;
+    }
     __syncthreads();
-    const long ntok = (long)B * H * W;
-    const long nstripes = (ntok + STRIPE - 1) / STRIPE;
-    for (long i = gtid(); i < nstripes * C; i += gstride()) {
-        const int c = (int)(i % C); const long st = i / C;
-        float g[27], gb[3] = {0.f, 0.f, 0.f};
+    const int l = lane_id(), wave = threadIdx.x >> 6;
+    const EcTiles T(B, H, W);
+    for (long t = blockIdx.x; t < T.n; t += gridDim.x) {
+        long b; int y0, x0;
+        T.at(t, b, y0, x0);
+        for (int grp = wave; grp < (EC_PLANE + 15) / 16; grp += 4) {
+            int r = grp * 16 + (l & 15); r = r < EC_PLANE ? r : EC_PLANE - 1;
+            const int y = y0 + r / EC_PW - 1, x = x0 + r % EC_PW - 1;
+            const bool ok = y >= 0 && y < H && x >= 0 && x < W;
+            const int yc = y < 0 ? 0 : (y >= H ? H - 1 : y), xc = x < 0 ? 0 : (x >= W ? W - 1 : x);
+            const float* row = fea + ((b * H + yc) * W + xc) * ldf;
+            f32x4 acc0 = f32x4{0.f, 0.f, 0.f, 0.f}, acc1 = acc0;
+            for (int c0 = 0; c0 < KC; c0 += 4) {
+                uint4 af[4];
 #pragma unroll
-        for (int t = 0; t < 27; ++t) g[t] = 0.f;
-        for (long tok = st * STRIPE; tok < ntok && tok < (st + 1) * STRIPE; ++tok) {
-            const int x = (int)(tok % W); const int y = (int)((tok / W) % H); const long b = tok / ((long)W * H);
-            float d[3], f[9];                              // branch-free: 9 clamped feature taps issued together, zeroed by a 0/1 factor
+                for (int j = 0; j < 4; ++j) {                   // all four loads first, from clamped offsets
+                    const int k = (c0 + j) * 16 + 4 * (l >> 4);
+                    af[j] = *reinterpret_cast<const uint4*>(row + (k < C ? k : 0));
+                }
 #pragma unroll
-            for (int ky = 0; ky < 3; ++ky) {
-                int yy = y + ky - 1; yy = yy < 0 ? 0 : (yy >= H ? H - 1 : yy);
-#pragma unroll
-                for (int kx = 0; kx < 3; ++kx) {
-                    int xx = x + kx - 1; xx = xx < 0 ? 0 : (xx >= W ? W - 1 : xx);
-                    f[ky * 3 + kx] = fea[((b * H + yy) * W + xx) * ldf + c];
+                for (int j = 0; j < 4; ++j) {
+                    const int k = (c0 + j) * 16 + 4 * (l >> 4);
+                    if (!(ok && k < C)) af[j] = make_uint4(0u, 0u, 0u, 0u);
+                    const int ch = c0 + j < KC ? c0 + j : KC - 1;     // a chunk past the end multiplies zeros
+                    mma_chunk<float>(acc0, af[j], wl[(ch * 2 + 0) * 64 + l]);
+                    mma_chunk<float>(acc1, af[j], wl[(ch * 2 + 1) * 64 + l]);
                 }
             }
+            float* pd = prod + (grp * 16 + 4 * (l >> 4)) * OP_PS + (l & 15);
 #pragma unroll
-            for (int co = 0; co < 3; ++co) { d[co] = dout[((b * 3 + co) * H + y) * W + x]; gb[co] += d[co]; }
+            for (int rr = 0; rr < 4; ++rr) { pd[rr * OP_PS] = acc0[rr]; pd[rr * OP_PS + 16] = acc1[rr]; }
+        }
+        __syncthreads();
+        for (int i = threadIdx.x; i < 3 * EC_PIX; i += 256) {
+            const int co = i / EC_PIX, p = i % EC_PIX, ty = p / EC_TX, tx = p % EC_TX, y = y0 + ty, x = x0 + tx;
+            const float* pp = prod + (ty * EC_PW + tx) * OP_PS + co * 9;
+            const long po = ((b * 3 + co) * H + (y < H ? y : H - 1)) * W + (x < W ? x : W - 1);     // clamped: the load is not under the branch
+            float s = bias[co] + (img ? img[po] : 0.f);
 #pragma unroll
             for (int ky = 0; ky < 3; ++ky)
 #pragma unroll
-                for (int kx = 0; kx < 3; ++kx) {
-                    const float fv = (y + ky - 1 >= 0 && y + ky - 1 < H && x + kx - 1 >= 0 && x + kx - 1 < W) ? f[ky * 3 + kx] : 0.f;
-#pragma unroll
-                    for (int co = 0; co < 3; ++co) g[co * 9 + ky * 3 + kx] += d[co] * fv;
-                }
+                for (int kx = 0; kx < 3; ++kx) s += pp[(ky * EC_PW + kx) * OP_PS + ky * 3 + kx];
+            if (y < H && x < W) out[po] = s;
         }
-        if (c == 0) for (int co = 0; co < 3; ++co) atomicAdd(&red[C * 27 + co], gb[co]);
-        for (int t = 0; t < 27; ++t) atomicAdd(&red[c * 27 + t], g[t]);
-    }
-    __syncthreads();
-    for (int i = threadIdx.x; i < C * 27 + 3; i += 256) {
-        if (i >= C * 27) { atomicAdd(db + (i - C * 27), red[i]); continue; }
-        const int c = i / 27, t = i % 27;                 // t = co*9 + tap
-        atomicAdd(dw + ((t / 9) * C + c) * 9 + t % 9, red[i]);
+        __syncthreads();
     }
 }
 
@@ -1458,33 +1513,53 @@ extern "C" int fw_colsum(int x_dtype, const void* x, long ldx, float* out, long 
     else hipLaunchKernelGGL(colsum_kernel, dim3(grid), dim3(TPB), 0, ST, (const float*)x, ldx, out, rows, cols, rpb);
     FW_LAUNCH_RET();
 }
+#ifndef FW_EC_WGRAD_CAP
+#define FW_EC_WGRAD_CAP 512                                 /* workgroups of a weight-gradient launch: each ends in one atomic per gradient word */
+#endif
+static inline int ec_grid(int B, int H, int W, int cap) {
+    const long n = (long)B * ((H + EC_TY - 1) / EC_TY) * ((W + EC_TX - 1) / EC_TX);
+    return (int)(n < cap ? n : cap);
+}
+static inline bool ec_al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+constexpr int OP_PROD_BYTES = ((EC_PLANE + 15) / 16) * 16 * OP_PS * 4;
+constexpr int OP_MAX_C = 896;                               // 56 k-chunks x 2 KB of B fragments + the product tile = 157.4 KB of the CU's 160 KB
 extern "C" int fw_inproj_fwd(const float* img, const float* w, const float* bias, float* out, long ldo, int B, int H, int W, int C,
                              float slope, void* stream) {
-    FW_CHECK_ARG(img && w && bias && out && C % 4 == 0 && ldo % 4 == 0);
-    hipLaunchKernelGGL(inproj_fwd_kernel, dim3(grid_for((long)B * H * W * (C / 4), 2048)), dim3(TPB), (size_t)C * 28 * 4, ST, img, w, bias, out, ldo, B, H, W, C, slope);
+    FW_CHECK_ARG(img && w && bias && out && C % 4 == 0 && ldo % 4 == 0 && C > 0 && C <= 1024 && B > 0 && H > 0 && W > 0);
+    FW_CHECK_ARG(ec_al16(out) && ec_al16(bias));
+    hipLaunchKernelGGL(edge_conv3_rows_kernel<0>, dim3(ec_grid(B, H, W, 768)), dim3(TPB), 0, ST, img, w, bias, out, ldo, B, H, W, C, slope);
     FW_LAUNCH_RET();
 }
+// any C: a lane owns four channels (16-byte loads) when C, the row strides and the pointers allow it, one channel otherwise; more
+// channels than one launch has lanes for (1 024 / 256) go in channel slices
 extern "C" int fw_inproj_bwd(const float* img, const float* out, long ldo, const float* dy, long ldy, float* dw, float* db, int B,
                              int H, int W, int C, float slope, void* stream) {
-    FW_CHECK_ARG(img && out && dy && dw && db);
-    constexpr int STRIPE = 32;
-    hipLaunchKernelGGL((inproj_bwd_kernel<STRIPE>), dim3(grid_for((((long)B * H * W + STRIPE - 1) / STRIPE) * C, 1024)), dim3(TPB), (size_t)C * 28 * 4, ST,
-                       img, out, ldo, dy, ldy, dw, db, B, H, W, C, slope);
+    FW_CHECK_ARG(img && out && dy && dw && db && C > 0 && B > 0 && H > 0 && W > 0);
+    const dim3 grid(ec_grid(B, H, W, FW_EC_WGRAD_CAP));
+    const bool v4 = C % 4 == 0 && ldo % 4 == 0 && ldy % 4 == 0 && ec_al16(out) && ec_al16(dy);
+    const int slice = v4 ? 1024 : 256;
+    for (int c0 = 0; c0 < C; c0 += slice) {
+        const int cs = C - c0 < slice ? C - c0 : slice;
+        if (v4) hipLaunchKernelGGL((edge_conv3_wgrad_kernel<4, 0>), grid, dim3(TPB), 0, ST, img, dy + c0, ldy, out + c0, ldo, dw + (long)c0 * 27, db + c0, B, H, W, cs, slope);
+        else hipLaunchKernelGGL((edge_conv3_wgrad_kernel<1, 0>), grid, dim3(TPB), 0, ST, img, dy + c0, ldy, out + c0, ldo, dw + (long)c0 * 27, db + c0, B, H, W, cs, slope);
+    }
     FW_LAUNCH_RET();
 }
 extern "C" int fw_outproj_fwd(const float* fea, long ldf, const float* w, const float* bias, const float* img, float* out, int B,
                               int H, int W, int C, void* stream) {
-    FW_CHECK_ARG(fea && w && bias && out && C % 4 == 0 && ldf % 4 == 0);
-    hipLaunchKernelGGL(outproj_fwd_kernel, dim3(grid_for((long)B * H * W, 2048)), dim3(TPB), (size_t)C * 27 * 4, ST, fea, ldf, w, bias, img, out, B, H, W, C);
+    FW_CHECK_ARG(fea && w && bias && out && C % 4 == 0 && ldf % 4 == 0 && C > 0 && C <= OP_MAX_C && B > 0 && H > 0 && W > 0 && ec_al16(fea));
+    const size_t lds = (size_t)((C + 15) / 16) * 2048 + OP_PROD_BYTES;
+    FW_SET_LDS_ONCE(outproj_fwd_mfma_kernel, (OP_MAX_C / 16) * 2048 + OP_PROD_BYTES);
+    hipLaunchKernelGGL(outproj_fwd_mfma_kernel, dim3(ec_grid(B, H, W, 512)), dim3(TPB), lds, ST, fea, ldf, w, bias, img, out, B, H, W, C);
     FW_LAUNCH_RET();
 }
 extern "C" int fw_outproj_bwd(const float* dout, const float* fea, long ldf, const float* w, float* dfea, long lddf, float* dw,
                               float* db, int B, int H, int W, int C, void* stream) {
-    FW_CHECK_ARG(dout && fea && w && dfea && dw && db && C % 4 == 0 && ldf % 4 == 0 && lddf % 4 == 0);
-    hipLaunchKernelGGL(outproj_bwd_data_kernel, dim3(grid_for((long)B * H * W * (C / 4), 2048)), dim3(TPB), (size_t)C * 27 * 4, ST, dout, w, dfea, lddf, B, H, W, C);
-    constexpr int STRIPE = 32;
-    hipLaunchKernelGGL((outproj_bwd_w_kernel<STRIPE>), dim3(grid_for((((long)B * H * W + STRIPE - 1) / STRIPE) * C, 1024)), dim3(TPB),
-                       (size_t)(C * 27 + 3) * 4, ST, dout, fea, ldf, dw, db, B, H, W, C);
+    FW_CHECK_ARG(dout && fea && w && dfea && dw && db && C % 4 == 0 && ldf % 4 == 0 && lddf % 4 == 0 && C > 0 && C <= 1024 && B > 0 && H > 0 && W > 0);
+    FW_CHECK_ARG(ec_al16(fea) && ec_al16(dfea));
+    hipLaunchKernelGGL(edge_conv3_rows_kernel<1>, dim3(ec_grid(B, H, W, 768)), dim3(TPB), 0, ST, dout, w, (const float*)nullptr, dfea, lddf, B, H, W, C, 0.f);
+    hipLaunchKernelGGL((edge_conv3_wgrad_kernel<4, 1>), dim3(ec_grid(B, H, W, FW_EC_WGRAD_CAP)), dim3(TPB), 0, ST, dout, fea, ldf, (const float*)nullptr, 0L, dw, db,
+                       B, H, W, C, 0.f);
     FW_LAUNCH_RET();
 }
 extern "C" int fw_l1_loss(const float* a, const float* b, float* da, long n, float gscale, float* loss, void* stream) {

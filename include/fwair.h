@@ -120,12 +120,16 @@ int fw_pixel_shuffle(int dtype, const void* g, const float* bias, float* out, lo
 int fw_pixel_unshuffle(int dtype, const float* dout, long ldo, void* dg, int B, int H, int W, int Cout, void* stream);
 int fw_colsum(int x_dtype, const void* x, long ldx, float* out, long rows, int cols, void* stream);
 
-/* ---- InputProj 3x3 conv 3->C + LeakyReLU(0.01) (decoder_Uformer.py:453-472), NCHW f32 image ----------- */
+/* ---- InputProj 3x3 conv 3->C + LeakyReLU(0.01) (decoder_Uformer.py:453-472), NCHW f32 image -----------
+ * fwd: C % 4 == 0, C <= 1024, ldo % 4 == 0, out and bias 16-byte aligned.  bwd: any C and any strides (16-byte loads when C, ldo,
+ * ldy are multiples of 4 and out / dy are 16-byte aligned, one channel per lane otherwise); dw / db are accumulated into. */
 int fw_inproj_fwd(const float* img, const float* w, const float* bias, float* out, long ldo, int B, int H, int W, int C,
                   float slope, void* stream);
 int fw_inproj_bwd(const float* img, const float* out, long ldo, const float* dy, long ldy, float* dw, float* db, int B, int H,
                   int W, int C, float slope, void* stream);
-/* ---- OutputProj 3x3 conv C->3 + global residual x + y (decoder_Uformer.py:476-499,1171) --------------- */
+/* ---- OutputProj 3x3 conv C->3 + global residual x + y (decoder_Uformer.py:476-499,1171) ---------------
+ * C % 4 == 0, ldf % 4 == 0, lddf % 4 == 0, fea / dfea 16-byte aligned; fwd: C <= 896 (weight fragments + product tile in LDS),
+ * bwd: C <= 1024; dw / db are accumulated into, dfea is overwritten.  img may be null (no residual). */
 int fw_outproj_fwd(const float* fea, long ldf, const float* w, const float* bias, const float* img, float* out, int B, int H,
                    int W, int C, void* stream);
 int fw_outproj_bwd(const float* dout, const float* fea, long ldf, const float* w, float* dfea, long lddf, float* dw, float* db,
