@@ -358,12 +358,9 @@ def test_colsum(rows, cols, ld):
 
 
 # ------------------------------------------------------------------------------------------------ LeFF dwconv
-@pytest.mark.parametrize('twin', [True, False])
-@pytest.mark.parametrize('dtype', DTYPES)
-def test_dwconv(dtype, twin):
+def check_dwconv(dtype, twin, B, H, W, C=112):
     """twin: the caller kept g1 = GELU(h1); else (the model's path) the kernels take the pre-activation h1 and apply GELU on load --
     the forward stencil and the input-centric weight gradient."""
-    B, H, W, C = 2, 16, 16, 112
     h1 = q(rnd(B * H * W, C), dtype).requires_grad_(True)
     w = (rnd(C, 1, 3, 3, seed=1) * 0.3).requires_grad_(True)
     b = (rnd(C, seed=2) * 0.1).requires_grad_(True)
@@ -385,10 +382,14 @@ def test_dwconv(dtype, twin):
     close(db, b.grad, TOL[dtype] * 2, 'db')
 
 
-# ------------------------------------------------------------------------------------------------ convs as GEMM
+@pytest.mark.parametrize('twin', [True, False])
 @pytest.mark.parametrize('dtype', DTYPES)
-def test_downsample_conv(dtype):
-    B, H, W, C = 2, 16, 16, 56
+def test_dwconv(dtype, twin):
+    check_dwconv(dtype, twin, 2, 16, 16)
+
+
+# ------------------------------------------------------------------------------------------------ convs as GEMM
+def check_downsample_conv(dtype, B, H, W, C=56):
     x = rnd(B * H * W, C).requires_grad_(True)
     w = (rnd(2 * C, C, 4, 4, seed=1) * 0.05).requires_grad_(True)
     b = rnd(2 * C, seed=2)
@@ -415,8 +416,11 @@ def test_downsample_conv(dtype):
 
 
 @pytest.mark.parametrize('dtype', DTYPES)
-def test_upsample_convT(dtype):
-    B, H, W, Cin, Cout = 2, 8, 8, 112, 56
+def test_downsample_conv(dtype):
+    check_downsample_conv(dtype, 2, 16, 16)
+
+
+def check_upsample_convT(dtype, B, H, W, Cin=112, Cout=56):
     x = q(rnd(B * H * W, Cin), dtype).requires_grad_(True)
     w = (rnd(Cin, Cout, 2, 2, seed=1) * 0.1).requires_grad_(True)
     b = rnd(Cout, seed=2)
@@ -443,6 +447,11 @@ def test_upsample_convT(dtype):
     db = torch.zeros(Cout, device=DEV)
     ops().colsum(dcat[:, :Cout], db)
     close(db, dy.sum(0), 1e-4, 'dbias')
+
+
+@pytest.mark.parametrize('dtype', DTYPES)
+def test_upsample_convT(dtype):
+    check_upsample_convT(dtype, 2, 8, 8)
 
 
 def test_in_out_proj():
