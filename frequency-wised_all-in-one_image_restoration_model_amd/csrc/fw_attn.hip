@@ -181,137 +181,26 @@ FW_DEV float bias_mask(const float* tab, int heads, int h, int i, int j, int shi
 FW_DEV float col_reduce_sum(float v) { v += __shfl_xor(v, 16, 64); v += __shfl_xor(v, 32, 64); return v; }
 FW_DEV float col_reduce_max(float v) { v = fmaxf(v, __shfl_xor(v, 16, 64)); v = fmaxf(v, __shfl_xor(v, 32, 64)); return v; }
 
-// ---- B1: the disc band filter on a 64x64 tile held transposed in registers ----------------------------------
-// Wave w passes / receives its strip: in[jt] = A^T[j = 16 jt ..][i = 16 w ..], out[jt] = B1(A)^T likewise.
-// scrA / scrB: two workgroup-wide LDS scratch regions of >= 64*LDP and >= 2*64*LDV bytes that no wave is still reading
-// on entry (the caller has passed a block barrier since their last use); on return both are free again.
-template <typename T>
-FW_DEV void band_filter(const f32x4 (&in)[4], f32x4 (&out)[4], char* scrA, char* scrB, const char* lfs) {
-    using G = Geo<T, 56>;
-    constexpr int SZ = G::SZ, LDP = G::LDP, LDV = G::LDV, JC = G::JC, VC = G::VC;
-    const char* tab = lfs;
-    const float* Mw = reinterpret_cast<const float*>(lfs + (size_t)OFF_END * SZ);
-    const int l = lane_id(), w = wave_id();
-    // Ps[i][j] <- in^T   (scrA, rows i of the own strip)
-#pragma unroll
-    for (int jt = 0; jt < 4; ++jt) store_acc_T<T>(scrA, LDP, jt * 16, w * 16, in[jt]);
-    wave_fence();
-    // T[i][v] = sum_j P[i][j] Fv[j][v]   (Tr with cos, Ti with -sin), rows i of the own strip; stored transposed -> Ts[v][i] (scrB)
-    {
-        f32x4 tr[2], ti[2];
-#pragma unroll
-        for (int n = 0; n < 2; ++n) { tr[n] = f32x4{0.f, 0.f, 0.f, 0.f}; ti[n] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-#pragma unroll
-        for (int c = 0; c < JC; ++c) {
-            const uint4 a = frag_kc(scrA, LDP, w * 16, c);
-#pragma unroll
-            for (int n = 0; n < 2; ++n) {
-                const uint4 bc = frag_kc(tab + (size_t)OFF_C2 * SZ, 64 * SZ, n * 16, c);
-                const uint4 bs = frag_kc(tab + (size_t)OFF_S2N * SZ, 64 * SZ, n * 16, c);
-                mma_chunk<T>(tr[n], a, bc); mma_chunk<T>(ti[n], a, bs);
-            }
-        }
-#pragma unroll
-        for (int n = 0; n < 2; ++n) {
-            store_acc_T<T>(scrB, LDP, w * 16, n * 16, tr[n]);                 // Tr^T [v][i]
-            store_acc_T<T>(scrB + 32 * LDP, LDP, w * 16, n * 16, ti[n]);      // Ti^T [v][i]
-        }
-    }
-    __syncthreads();                         // T complete (all strips); every wave is done reading Ps
-    // X[u][v] = sum_i Fu[u][i] T[i][v]:  Xr = Cu Tr + Su Ti,  Xi = Cu Ti - Su Tr;  Y = Mw * X -> Ys[v][u] (scrA)
-    // 3 row tiles of u (|fu| <= 22 -> 48 rows): waves 0..2 take one each, wave 3 clears the k padding u = 48..63 of Ys
-    if (w < 3) {
-        f32x4 xr[2], xi[2];
-#pragma unroll
-        for (int n = 0; n < 2; ++n) { xr[n] = f32x4{0.f, 0.f, 0.f, 0.f}; xi[n] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-#pragma unroll
-        for (int c = 0; c < JC; ++c) {
-            const uint4 ac = frag_kc(tab + (size_t)OFF_CU * SZ, 64 * SZ, w * 16, c);
-            const uint4 as = frag_kc(tab + (size_t)OFF_SU * SZ, 64 * SZ, w * 16, c);
-            const uint4 an = frag_kc(tab + (size_t)OFF_SUN * SZ, 64 * SZ, w * 16, c);
-#pragma unroll
-            for (int n = 0; n < 2; ++n) {
-                const uint4 br = frag_kc(scrB, LDP, n * 16, c), bi = frag_kc(scrB + 32 * LDP, LDP, n * 16, c);
-                mma_chunk<T>(xr[n], ac, br); mma_chunk<T>(xr[n], as, bi);
-                mma_chunk<T>(xi[n], ac, bi); mma_chunk<T>(xi[n], an, br);
-            }
-        }
-#pragma unroll
-        for (int n = 0; n < 2; ++n) {
-            f32x4 wt;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) wt[r] = Mw[(w * 16 + ((l >> 4) << 2) + r) * NV + n * 16 + (l & 15)];
-            store_acc_T<T>(scrA, LDP, w * 16, n * 16, xr[n] * wt);             // Yr^T [v][u]
-            store_acc_T<T>(scrA + 32 * LDP, LDP, w * 16, n * 16, xi[n] * wt);  // Yi^T [v][u]
-        }
-    } else {
-        for (int idx = l; idx < 64 * 4; idx += 64) {
-            const int row = idx >> 2, part = idx & 3;          // 64 rows (2 panels x 32), 16 pad elements in 4 parts
-            char* p = scrA + row * LDP + 48 * SZ + part * 4 * SZ;
-            if (SZ == 4) *reinterpret_cast<uint4*>(p) = make_uint4(0, 0, 0, 0); else *reinterpret_cast<uint2*>(p) = make_uint2(0, 0);
-        }
-    }
-    __syncthreads();                         // Y complete; every wave is done reading T
-    // Z^T[v][i] = sum_u Y^T[v][u] FuH[i][u]:  Zr = Yr C - Yi S,  Zi = Yi C + Yr S;  own columns i; stored transposed -> Zs[i][v] (scrB)
-    {
-        f32x4 zr[2], zi[2];
-#pragma unroll
-        for (int m = 0; m < 2; ++m) { zr[m] = f32x4{0.f, 0.f, 0.f, 0.f}; zi[m] = f32x4{0.f, 0.f, 0.f, 0.f}; }
-#pragma unroll
-        for (int c = 0; c < JC; ++c) {
-            const uint4 bc = frag_kc(tab + (size_t)OFF_CH * SZ, 64 * SZ, w * 16, c);
-            const uint4 bs = frag_kc(tab + (size_t)OFF_SH * SZ, 64 * SZ, w * 16, c);
-            const uint4 bn = frag_kc(tab + (size_t)OFF_SHN * SZ, 64 * SZ, w * 16, c);
-#pragma unroll
-            for (int m = 0; m < 2; ++m) {
-                const uint4 ar = frag_kc(scrA, LDP, m * 16, c), ai = frag_kc(scrA + 32 * LDP, LDP, m * 16, c);
-                mma_chunk<T>(zr[m], ar, bc); mma_chunk<T>(zr[m], ai, bn);
-                mma_chunk<T>(zi[m], ai, bc); mma_chunk<T>(zi[m], ar, bs);
-            }
-        }
-#pragma unroll
-        for (int m = 0; m < 2; ++m) {
-            store_acc_T<T>(scrB, LDV, m * 16, w * 16, zr[m]);                 // Zr [i][v]
-            store_acc_T<T>(scrB + 64 * LDV, LDV, m * 16, w * 16, zi[m]);      // Zi [i][v]
-        }
-    }
-    wave_fence();
-    // out^T[j][i] = sum_v Gc[j][v] Zr[i][v] + Gsn[j][v] Zi[i][v]   (own columns i)
-#pragma unroll
-    for (int m = 0; m < 4; ++m) out[m] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int c = 0; c < VC; ++c) {
-        const uint4 br = frag_kc(scrB, LDV, w * 16, c), bi = frag_kc(scrB + 64 * LDV, LDV, w * 16, c);
-#pragma unroll
-        for (int m = 0; m < 4; ++m) {
-            const uint4 ac = frag_kc(tab + (size_t)OFF_GC * SZ, 32 * SZ, m * 16, c);
-            const uint4 as = frag_kc(tab + (size_t)OFF_GSN * SZ, 32 * SZ, m * 16, c);
-            mma_chunk<T>(out[m], ac, br); mma_chunk<T>(out[m], as, bi);
-        }
-    }
-    __syncthreads();                         // both scratch regions are free again
-}
-
-template <typename T, int D, int NKT, int LFS> struct Smem {
+// The v1 kernels: one key tile, no frequency selection.  They serve what the v2 kernels below do not take: inter-band attention
+// over two bands (mode 1, L = 2: the key tile is the other band's).  Their two-key-tile and frequency-selection forms were
+// removed when attn2x_* / attn2_* took those cases; git history has them.
+template <typename T, int D> struct Smem {
     using G = Geo<T, D>;
-    static constexpr int LDPK = NKT * 64 * G::SZ + 16;                       // P' tile [64 i][NKT*64 j]
-    static constexpr int SCR = LFS == 2 ? (2 * 64 * G::LDV > 64 * G::LDP ? 2 * 64 * G::LDV : 64 * G::LDP) : 0;
-    static constexpr int RA = (64 * LDPK > SCR ? 64 * LDPK : SCR) > G::TILE_D ? (64 * LDPK > SCR ? 64 * LDPK : SCR) : G::TILE_D;
-    static constexpr int RB = (SCR > G::TILE_D ? SCR : G::TILE_D);
-    static constexpr int FWD_BYTES = RA + RB * NKT + G::TILE_D * NKT;        // A | B (K tiles) | V tiles
+    static constexpr int RA = 64 * G::LDP > G::TILE_D ? 64 * G::LDP : G::TILE_D;   // Q, then the P' tile [64 i][64 j]
+    static constexpr int FWD_BYTES = RA + G::TILE_D + G::TILE_D;                    // A | B (K tile) | V tile
 };
 
 // =====================================================================================================
 // forward
 // =====================================================================================================
-template <typename T, int D, int NKT, int LFS>
+template <typename T, int D>
 __global__ __launch_bounds__(NTH, 3) void attn_fwd_kernel(AttnArgs a) {
     using G = Geo<T, D>;
-    using S = Smem<T, D, NKT, LFS>;
+    using S = Smem<T, D>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    char* rA = smem;                        // Q -> P' (and LFS scratch A)
-    char* rB = smem + S::RA;                // K tiles (kt) -> LFS scratch B -> O staging
-    char* rV = rB + S::RB * NKT;            // V tiles
+    char* rA = smem;                        // Q -> P'
+    char* rB = smem + S::RA;                // K tile -> O staging
+    char* rV = rB + G::TILE_D;              // V tile
     const int l = lane_id(), w = wave_id();
     const int nWx = a.W / 8, nWy = a.H / 8, nW = nWx * nWy;
     const int items = a.nwin * a.L * a.heads;
@@ -323,43 +212,35 @@ __global__ __launch_bounds__(NTH, 3) void attn_fwd_kernel(AttnArgs a) {
         const int b = win / nW, wi = win % nW, wy = wi / nWx, wx = wi % nWx;
         const bool last_y = wy == nWy - 1, last_x = wx == nWx - 1;
         const int nq = lq * a.B + b;
+        const int lk = a.mode == 0 ? lq : other_band(lq, 0);
         {
-            TileLoad<T, D> tq, tk[NKT], tv[NKT];
+            TileLoad<T, D> tq, tk, tv;
             tq.issue(a.q, a.ld, nq, wy, wx, a.H, a.W, a.shift, h * D);
-#pragma unroll
-            for (int kt = 0; kt < NKT; ++kt) {
-                const int lk = a.mode == 0 ? lq : other_band(lq, kt);
-                tk[kt].issue(a.k, a.ld, lk * a.B + b, wy, wx, a.H, a.W, a.shift, h * D);
-                tv[kt].issue(a.v, a.ld, lk * a.B + b, wy, wx, a.H, a.W, a.shift, h * D);
-            }
+            tk.issue(a.k, a.ld, lk * a.B + b, wy, wx, a.H, a.W, a.shift, h * D);
+            tv.issue(a.v, a.ld, lk * a.B + b, wy, wx, a.H, a.W, a.shift, h * D);
             tq.commit(rA);
-#pragma unroll
-            for (int kt = 0; kt < NKT; ++kt) { tk[kt].commit(rB + kt * S::RB); tv[kt].commit(rV + kt * G::TILE_D); }
+            tk.commit(rB); tv.commit(rV);
         }
         __syncthreads();
         // S^T[j][i] = sum_d K[j][d] Q[i][d], own columns i
-        f32x4 p[4 * NKT];
+        f32x4 p[4];
 #pragma unroll
-        for (int jt = 0; jt < 4 * NKT; ++jt) p[jt] = f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int jt = 0; jt < 4; ++jt) p[jt] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int kt = 0; kt < NKT; ++kt)
+        for (int c = 0; c < G::KC; ++c) {
+            const uint4 bq = frag_kc(rA, G::LDR, w * 16, c);
 #pragma unroll
-            for (int c = 0; c < G::KC; ++c) {
-                const uint4 bq = frag_kc(rA, G::LDR, w * 16, c);
-#pragma unroll
-                for (int m = 0; m < 4; ++m) mma_chunk<T>(p[4 * kt + m], frag_kc(rB + kt * S::RB, G::LDR, m * 16, c), bq);
-            }
+            for (int m = 0; m < 4; ++m) mma_chunk<T>(p[m], frag_kc(rB, G::LDR, m * 16, c), bq);
+        }
         // scale, bias, mask, softmax over j
         {
             float mx = -3.0e38f;
+            const float* tab = a.bias + (size_t)(lq * a.L + lk) * 225 * a.heads;
 #pragma unroll
-            for (int jt = 0; jt < 4 * NKT; ++jt) {
-                const int kt = jt >> 2;
-                const int lk = a.mode == 0 ? lq : other_band(lq, kt);
-                const float* tab = a.bias + (size_t)(lq * a.L + lk) * 225 * a.heads;
+            for (int jt = 0; jt < 4; ++jt) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    const int j = (jt & 3) * 16 + ((l >> 4) << 2) + r;
+                    const int j = jt * 16 + ((l >> 4) << 2) + r;
                     const float s = p[jt][r] * a.scale + bias_mask(tab, a.heads, h, i, j, a.shift, last_y, last_x);
                     p[jt][r] = s;
                     mx = fmaxf(mx, s);
@@ -368,45 +249,29 @@ __global__ __launch_bounds__(NTH, 3) void attn_fwd_kernel(AttnArgs a) {
             mx = col_reduce_max(mx);
             float sum = 0.f;
 #pragma unroll
-            for (int jt = 0; jt < 4 * NKT; ++jt)
+            for (int jt = 0; jt < 4; ++jt)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) { const float e = __expf(p[jt][r] - mx); p[jt][r] = e; sum += e; }
             sum = col_reduce_sum(sum);
             const float inv = 1.0f / sum;
 #pragma unroll
-            for (int jt = 0; jt < 4 * NKT; ++jt) p[jt] *= inv;
+            for (int jt = 0; jt < 4; ++jt) p[jt] *= inv;
             if ((l >> 4) == 0) a.lse[(size_t)item * 64 + i] = mx + __logf(sum);
         }
         __syncthreads();                    // Q / K tiles are dead from here on
-        if constexpr (LFS >= 1) {
-            static_assert(NKT == 1, "frequency selection acts on one 64x64 map");
-            const float* cf = a.coef + ((size_t)b * a.heads + h) * 3;
-            const float ca = cf[0], cb = cf[1], cc = cf[2];
-            if constexpr (LFS == 2) {
-                f32x4 f1[4];
-                band_filter<T>(p, f1, rA, rB, a.lfs);
+        // P[i][j] -> rA rows i of the own strip (transposed store), then O^T[d][i] = sum_j V[j][d] P[i][j]
 #pragma unroll
-                for (int jt = 0; jt < 4; ++jt) p[jt] = p[jt] * ca + cb + f1[jt] * cc;
-            } else {
-#pragma unroll
-                for (int jt = 0; jt < 4; ++jt) p[jt] = p[jt] * ca + cb;
-            }
-        }
-        // P'[i][j] -> rA rows i of the own strip (transposed store), then O^T[d][i] = sum_j V[j][d] P'[i][j]
-#pragma unroll
-        for (int jt = 0; jt < 4 * NKT; ++jt) store_acc_T<T>(rA, S::LDPK, jt * 16, w * 16, p[jt]);
+        for (int jt = 0; jt < 4; ++jt) store_acc_T<T>(rA, G::LDP, jt * 16, w * 16, p[jt]);
         wave_fence();
         f32x4 o[G::DT];
 #pragma unroll
         for (int m = 0; m < G::DT; ++m) o[m] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int kt = 0; kt < NKT; ++kt)
+        for (int c = 0; c < G::JC; ++c) {
+            const uint4 bp = frag_kc(rA, G::LDP, w * 16, c);
 #pragma unroll
-            for (int c = 0; c < G::JC; ++c) {
-                const uint4 bp = frag_kc(rA, S::LDPK, w * 16, kt * G::JC + c);
-#pragma unroll
-                for (int m = 0; m < G::DT; ++m) mma_chunk<T>(o[m], frag_km<T>(rV + kt * G::TILE_D, G::LDR, m * 16, c), bp);
-            }
+            for (int m = 0; m < G::DT; ++m) mma_chunk<T>(o[m], frag_km<T>(rV, G::LDR, m * 16, c), bp);
+        }
 #pragma unroll
         for (int m = 0; m < G::DT; ++m) store_acc_T<T>(rB, G::LDR, m * 16, w * 16, o[m]);      // O [i][d], own rows
         wave_fence();
@@ -418,7 +283,7 @@ __global__ __launch_bounds__(NTH, 3) void attn_fwd_kernel(AttnArgs a) {
 // =====================================================================================================
 // backward
 // =====================================================================================================
-template <typename T, int D, int NKT, int LFS> struct SmemB {
+template <typename T, int D> struct SmemB {
     using G = Geo<T, D>;
     static constexpr int SCR = 2 * 64 * G::LDV > 64 * G::LDP ? 2 * 64 * G::LDV : 64 * G::LDP;   // >= one [64][64] tile
     static constexpr int OFF_Q = 0, OFF_DO = G::TILE_D, OFF_K = 2 * G::TILE_D, OFF_V = 3 * G::TILE_D;
@@ -427,10 +292,10 @@ template <typename T, int D, int NKT, int LFS> struct SmemB {
     static constexpr int BYTES = OFF_BIN + 1024;
 };
 
-template <typename T, int D, int NKT, int LFS>
+template <typename T, int D>
 __global__ __launch_bounds__(NTH, 2) void attn_bwd_kernel(AttnArgs a) {
     using G = Geo<T, D>;
-    using S = SmemB<T, D, NKT, LFS>;
+    using S = SmemB<T, D>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* sQ = smem + S::OFF_Q; char* sDO = smem + S::OFF_DO; char* sK = smem + S::OFF_K; char* sV = smem + S::OFF_V;
     char* sX = smem + S::OFF_X; char* sY = smem + S::OFF_Y;
@@ -440,229 +305,143 @@ __global__ __launch_bounds__(NTH, 2) void attn_bwd_kernel(AttnArgs a) {
     const int h = blockIdx.y, lq = blockIdx.z;
     const int dqx = (h == a.heads - 1) ? a.dq_pad * G::SZ / G::CB : 0;       // granules of zero padding behind the last head's dq
     const int i = w * 16 + (l & 15);                         // the query of this lane's score columns
-    f32x4 dbacc[NKT][4];                                     // bias-gradient accumulators of (i, j = 16 jt + 4 (l>>4) + r), all windows
+    f32x4 dbacc[4];                                          // bias-gradient accumulators of (i, j = 16 jt + 4 (l>>4) + r), all windows
 #pragma unroll
-    for (int kt = 0; kt < NKT; ++kt)
-#pragma unroll
-        for (int jt = 0; jt < 4; ++jt) dbacc[kt][jt] = f32x4{0.f, 0.f, 0.f, 0.f};
-    // A workgroup walks a CONTIGUOUS range of windows: they belong to one image (or a few), so the three coefficient-gradient
-    // sums of (image, head) are carried in registers across windows and leave as ONE atomic triple per wave when the image
-    // changes -- per-window atomics on the B * heads * 3 hot words serialised (same-address atomics), and every one of them
-    // sat in front of the next window's tile loads in the in-order vmcnt queue.
+    for (int jt = 0; jt < 4; ++jt) dbacc[jt] = f32x4{0.f, 0.f, 0.f, 0.f};
+    // a workgroup walks a CONTIGUOUS range of windows
     const int per = (a.nwin + gridDim.x - 1) / gridDim.x;
     const int win_begin = blockIdx.x * per, win_end = min(a.nwin, win_begin + per);
-    float cs1 = 0.f, cs2 = 0.f, cs3 = 0.f;
-    int cs_b = -1;
-    auto flush_coef = [&]() {
-        if constexpr (LFS >= 1) {
-            if (cs_b >= 0) {
-                const float t1 = wave_sum(cs1), t2 = wave_sum(cs2), t3 = wave_sum(cs3);
-                if (l == 0) {
-                    float* dc = a.dcoef + ((size_t)cs_b * a.heads + h) * 3;
-                    atomicAdd(dc, t1); atomicAdd(dc + 1, t2);
-                    if (LFS == 2) atomicAdd(dc + 2, t3);
-                }
-            }
-            cs1 = cs2 = cs3 = 0.f;
-        }
-    };
+    const int lk = a.mode == 0 ? lq : other_band(lq, 0);
     for (int win = win_begin; win < win_end; ++win) {
         const int b = win / nW, wi = win % nW, wy = wi / nWx, wx = wi % nWx;
         const bool last_y = wy == nWy - 1, last_x = wx == nWx - 1;
         const int nq = lq * a.B + b;
         const size_t item = ((size_t)win * a.L + lq) * a.heads + h;
-        if (b != cs_b) { flush_coef(); cs_b = b; }
+        const int nk = lk * a.B + b;
         TileLoad<T, D> tq, tdo;
         tq.issue(a.q, a.ld, nq, wy, wx, a.H, a.W, a.shift, h * D);
         tdo.issue(a.dout, a.lddo, nq, wy, wx, a.H, a.W, a.shift, h * D);
         const float lse = a.lse[item * 64 + i];
-        float di = 0.f;
-        if constexpr (NKT > 1) {
-            // D_i = sum_d O[i][d] dO[i][d]   (rowsum(P o dP) == rowsum(O o dO) when P' = P); the 4 lanes of a column share the row
-            const long row = token_row(nq, wy, wx, i, a.H, a.W, a.shift);
-            const T* op = reinterpret_cast<const T*>(a.out) + row * a.ldo + h * D;
-            const T* gp = reinterpret_cast<const T*>(a.dout) + row * a.lddo + h * D;
-            float s = 0.f;
-            for (int d = (l >> 4); d < D; d += 4) s += TT<T>::ld(op + d) * TT<T>::ld(gp + d);
-            di = col_reduce_sum(s);
-        }
         f32x4 dq[G::DT];
 #pragma unroll
         for (int m = 0; m < G::DT; ++m) dq[m] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll 1
-        for (int kt = 0; kt < NKT; ++kt) {
-            const int lk = a.mode == 0 ? lq : other_band(lq, kt);
-            const int nk = lk * a.B + b;
-            const int tabid = lq * a.L + lk;
-            {
-                TileLoad<T, D> tk, tv;
-                tk.issue(a.k, a.ld, nk, wy, wx, a.H, a.W, a.shift, h * D);
-                tv.issue(a.v, a.ld, nk, wy, wx, a.H, a.W, a.shift, h * D);
-                __syncthreads();                             // every wave is done with the previous K / V tiles and scratch
-                if (kt == 0) { tq.commit(sQ); tdo.commit(sDO); }
-                tk.commit(sK); tv.commit(sV);
-            }
-            __syncthreads();
-            // P^T[j][i] = exp(scale * K Q^T + bias + mask - lse_i), own columns i
-            f32x4 p[4], dp[4];
-            const float* tab = a.bias + (size_t)tabid * 225 * a.heads;
-            auto compute_p = [&]() {
-#pragma unroll
-                for (int jt = 0; jt < 4; ++jt) p[jt] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int c = 0; c < G::KC; ++c) {
-                    const uint4 bq = frag_kc(sQ, G::LDR, w * 16, c);
-#pragma unroll
-                    for (int m = 0; m < 4; ++m) mma_chunk<T>(p[m], frag_kc(sK, G::LDR, m * 16, c), bq);
-                }
-#pragma unroll
-                for (int jt = 0; jt < 4; ++jt)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const int j = jt * 16 + ((l >> 4) << 2) + r;
-                        p[jt][r] = __expf(p[jt][r] * a.scale + bias_mask(tab, a.heads, h, i, j, a.shift, last_y, last_x) - lse);
-                    }
-            };
-            compute_p();
-            float ca = 1.f, cc = 0.f;
-            // P'[i][j] = a P + b (+ c B1(P))  -> sX rows i of the own strip
-            if constexpr (LFS >= 1) {
-                const float* cf = a.coef + ((size_t)b * a.heads + h) * 3;
-                ca = cf[0]; const float cb = cf[1]; cc = cf[2];
-                if constexpr (LFS == 2) {
-                    f32x4 f[4];
-                    band_filter<T>(p, f, sX, sY, a.lfs);
-#pragma unroll
-                    for (int jt = 0; jt < 4; ++jt) store_acc_T<T>(sX, G::LDP, jt * 16, w * 16, p[jt] * ca + cb + f[jt] * cc);
-                } else {
-#pragma unroll
-                    for (int jt = 0; jt < 4; ++jt) store_acc_T<T>(sX, G::LDP, jt * 16, w * 16, p[jt] * ca + cb);
-                }
-            } else {
-#pragma unroll
-                for (int jt = 0; jt < 4; ++jt) store_acc_T<T>(sX, G::LDP, jt * 16, w * 16, p[jt]);
-            }
-            __syncthreads();
-            // dV^T[d][j] = sum_i dO[i][d] P'[i][j], own columns j  (both operands read along the token axis: transposing reads)
-            {
-                f32x4 dv[G::DT];
-#pragma unroll
-                for (int m = 0; m < G::DT; ++m) dv[m] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-                for (int c = 0; c < G::JC; ++c) {
-                    const uint4 bn = frag_km<T>(sX, G::LDP, w * 16, c);
-#pragma unroll
-                    for (int m = 0; m < G::DT; ++m) mma_chunk<T>(dv[m], frag_km<T>(sDO, G::LDR, m * 16, c), bn);
-                }
-#pragma unroll
-                for (int m = 0; m < G::DT; ++m) store_acc_T<T>(sY, G::LDR, m * 16, w * 16, dv[m]);   // dV [j][d], own rows j
-                wave_fence();
-                char* dvp = (NKT > 1 && kt_slot(lq, lk) == 1) ? a.dv2 : a.dv;
-                store_rows16<T, D>(sY, dvp, a.ldd, nk, wy, wx, a.H, a.W, a.shift, h * D, w * 16);
-            }
-            // dP'^T[j][i] = sum_d V[j][d] dO[i][d], own columns i
-#pragma unroll
-            for (int jt = 0; jt < 4; ++jt) dp[jt] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int c = 0; c < G::KC; ++c) {
-                const uint4 bd = frag_kc(sDO, G::LDR, w * 16, c);
-#pragma unroll
-                for (int m = 0; m < 4; ++m) mma_chunk<T>(dp[m], frag_kc(sV, G::LDR, m * 16, c), bd);
-            }
-            __syncthreads();                                 // every wave is done reading P' (sX) and its dV staging rows (sY)
-            if constexpr (LFS >= 1) {
-                // G^T = B1(dP')^T ; d(a,b,c) = (<dP',P>, sum dP', <G,P>) ; dP = a dP' + c G
-                float s1 = 0.f, s2 = 0.f, s3 = 0.f;
-                if constexpr (LFS == 2) {
-                    f32x4 g[4];
-                    band_filter<T>(dp, g, sX, sY, a.lfs);
-#pragma unroll
-                    for (int jt = 0; jt < 4; ++jt)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            s1 += dp[jt][r] * p[jt][r];
-                            s2 += dp[jt][r];
-                            s3 += g[jt][r] * p[jt][r];
-                            dp[jt][r] = dp[jt][r] * ca + g[jt][r] * cc;
-                        }
-                } else {
-#pragma unroll
-                    for (int jt = 0; jt < 4; ++jt)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            s1 += dp[jt][r] * p[jt][r];
-                            s2 += dp[jt][r];
-                            dp[jt][r] = dp[jt][r] * ca;
-                        }
-                }
-                cs1 += s1; cs2 += s2; cs3 += s3;
-            }
-            // D_i (NKT == 1: straight from registers), dS^T = P^T o (dP^T - D_i)
-            if constexpr (NKT == 1) {
-                float s = 0.f;
-#pragma unroll
-                for (int jt = 0; jt < 4; ++jt)
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) s += p[jt][r] * dp[jt][r];
-                di = col_reduce_sum(s);
-            }
-#pragma unroll
-            for (int jt = 0; jt < 4; ++jt) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) dp[jt][r] = p[jt][r] * (dp[jt][r] - di);
-                if (NKT == 1 || kt == 0) dbacc[0][jt] += dp[jt]; else dbacc[NKT - 1][jt] += dp[jt];   // static indices: registers
-            }
-            // dS -> sX as [i][j], rows i of the own strip; dQ reads it along j (row fragments), dK along i (transposing reads)
-#pragma unroll
-            for (int jt = 0; jt < 4; ++jt) store_acc_T<T>(sX, G::LDP, jt * 16, w * 16, dp[jt]);
-            __syncthreads();
-            // dQ^T[d][i] += sum_j K[j][d] dS[i][j] (own i) ;  dK^T[d][j] = sum_i Q[i][d] dS[i][j] (own j)
-            f32x4 dk[G::DT];
-#pragma unroll
-            for (int m = 0; m < G::DT; ++m) dk[m] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int c = 0; c < G::JC; ++c) {
-                const uint4 bx = frag_kc(sX, G::LDP, w * 16, c), by = frag_km<T>(sX, G::LDP, w * 16, c);
-#pragma unroll
-                for (int m = 0; m < G::DT; ++m) {
-                    mma_chunk<T>(dq[m], frag_km<T>(sK, G::LDR, m * 16, c), bx);
-                    mma_chunk<T>(dk[m], frag_km<T>(sQ, G::LDR, m * 16, c), by);
-                }
-            }
-#pragma unroll
-            for (int m = 0; m < G::DT; ++m) store_acc_T<T>(sY, G::LDR, m * 16, w * 16, dk[m] * a.scale);   // dK [j][d], own rows j
-            wave_fence();
-            char* dkp = (NKT > 1 && kt_slot(lq, lk) == 1) ? a.dk2 : a.dk;
-            store_rows16<T, D>(sY, dkp, a.ldd, nk, wy, wx, a.H, a.W, a.shift, h * D, w * 16);
+        {
+            TileLoad<T, D> tk, tv;
+            tk.issue(a.k, a.ld, nk, wy, wx, a.H, a.W, a.shift, h * D);
+            tv.issue(a.v, a.ld, nk, wy, wx, a.H, a.W, a.shift, h * D);
+            __syncthreads();                                 // every wave is done with the previous window's tiles and scratch
+            tq.commit(sQ); tdo.commit(sDO);
+            tk.commit(sK); tv.commit(sV);
         }
-        __syncthreads();                                     // sX / sY / sQ / sDO are free: all waves are past their last reads
-#pragma unroll
-        for (int m = 0; m < G::DT; ++m) store_acc_T<T>(sY, G::LDR, m * 16, w * 16, dq[m] * a.scale);         // dQ [i][d], own rows i
-        wave_fence();
-        store_rows16<T, D>(sY, a.dq, a.ldd, nq, wy, wx, a.H, a.W, a.shift, h * D, w * 16, dqx);
-        // the next window's Q / dO loads touch neither sY nor anything a wave still reads
-    }
-    flush_coef();
-    // flush the bias-gradient accumulators: fold the (i, j) pairs into the 225 relative positions on chip, then one
-    // atomic per bin into the parameter layout [table][225][heads] (all workgroups of a head hit the same 225 words)
-    float* bins = reinterpret_cast<float*>(smem + S::OFF_BIN);
-#pragma unroll
-    for (int kt = 0; kt < NKT; ++kt) {
         __syncthreads();
-        for (int idx = threadIdx.x; idx < 225; idx += NTH) bins[idx] = 0.f;
-        __syncthreads();
+        // P^T[j][i] = exp(scale * K Q^T + bias + mask - lse_i), own columns i
+        f32x4 p[4], dp[4];
+        const float* tab = a.bias + (size_t)(lq * a.L + lk) * 225 * a.heads;
+#pragma unroll
+        for (int jt = 0; jt < 4; ++jt) p[jt] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int c = 0; c < G::KC; ++c) {
+            const uint4 bq = frag_kc(sQ, G::LDR, w * 16, c);
+#pragma unroll
+            for (int m = 0; m < 4; ++m) mma_chunk<T>(p[m], frag_kc(sK, G::LDR, m * 16, c), bq);
+        }
 #pragma unroll
         for (int jt = 0; jt < 4; ++jt)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int j = jt * 16 + ((l >> 4) << 2) + r;
-                atomicAdd(&bins[((i >> 3) - (j >> 3) + 7) * 15 + (i & 7) - (j & 7) + 7], dbacc[kt][jt][r]);
+                p[jt][r] = __expf(p[jt][r] * a.scale + bias_mask(tab, a.heads, h, i, j, a.shift, last_y, last_x) - lse);
             }
+        // P[i][j] -> sX rows i of the own strip
+#pragma unroll
+        for (int jt = 0; jt < 4; ++jt) store_acc_T<T>(sX, G::LDP, jt * 16, w * 16, p[jt]);
         __syncthreads();
-        const int lk = a.mode == 0 ? lq : other_band(lq, kt);
-        float* dst = a.dbias + (size_t)(lq * a.L + lk) * 225 * a.heads;
-        for (int idx = threadIdx.x; idx < 225; idx += NTH) atomicAdd(dst + idx * a.heads + h, bins[idx]);
+        // dV^T[d][j] = sum_i dO[i][d] P[i][j], own columns j  (both operands read along the token axis: transposing reads)
+        {
+            f32x4 dv[G::DT];
+#pragma unroll
+            for (int m = 0; m < G::DT; ++m) dv[m] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int c = 0; c < G::JC; ++c) {
+                const uint4 bn = frag_km<T>(sX, G::LDP, w * 16, c);
+#pragma unroll
+                for (int m = 0; m < G::DT; ++m) mma_chunk<T>(dv[m], frag_km<T>(sDO, G::LDR, m * 16, c), bn);
+            }
+#pragma unroll
+            for (int m = 0; m < G::DT; ++m) store_acc_T<T>(sY, G::LDR, m * 16, w * 16, dv[m]);   // dV [j][d], own rows j
+            wave_fence();
+            store_rows16<T, D>(sY, a.dv, a.ldd, nk, wy, wx, a.H, a.W, a.shift, h * D, w * 16);
+        }
+        // dP^T[j][i] = sum_d V[j][d] dO[i][d], own columns i
+#pragma unroll
+        for (int jt = 0; jt < 4; ++jt) dp[jt] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int c = 0; c < G::KC; ++c) {
+            const uint4 bd = frag_kc(sDO, G::LDR, w * 16, c);
+#pragma unroll
+            for (int m = 0; m < 4; ++m) mma_chunk<T>(dp[m], frag_kc(sV, G::LDR, m * 16, c), bd);
+        }
+        __syncthreads();                                     // every wave is done reading P (sX) and its dV staging rows (sY)
+        // D_i = rowsum(P o dP) straight from registers, dS^T = P^T o (dP^T - D_i)
+        float di;
+        {
+            float s = 0.f;
+#pragma unroll
+            for (int jt = 0; jt < 4; ++jt)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) s += p[jt][r] * dp[jt][r];
+            di = col_reduce_sum(s);
+        }
+#pragma unroll
+        for (int jt = 0; jt < 4; ++jt) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) dp[jt][r] = p[jt][r] * (dp[jt][r] - di);
+            dbacc[jt] += dp[jt];
+        }
+        // dS -> sX as [i][j], rows i of the own strip; dQ reads it along j (row fragments), dK along i (transposing reads)
+#pragma unroll
+        for (int jt = 0; jt < 4; ++jt) store_acc_T<T>(sX, G::LDP, jt * 16, w * 16, dp[jt]);
+        __syncthreads();
+        // dQ^T[d][i] = sum_j K[j][d] dS[i][j] (own i) ;  dK^T[d][j] = sum_i Q[i][d] dS[i][j] (own j)
+        f32x4 dk[G::DT];
+#pragma unroll
+        for (int m = 0; m < G::DT; ++m) dk[m] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int c = 0; c < G::JC; ++c) {
+            const uint4 bx = frag_kc(sX, G::LDP, w * 16, c), by = frag_km<T>(sX, G::LDP, w * 16, c);
+#pragma unroll
+            for (int m = 0; m < G::DT; ++m) {
+                mma_chunk<T>(dq[m], frag_km<T>(sK, G::LDR, m * 16, c), bx);
+                mma_chunk<T>(dk[m], frag_km<T>(sQ, G::LDR, m * 16, c), by);
+            }
+        }
+#pragma unroll
+        for (int m = 0; m < G::DT; ++m) store_acc_T<T>(sY, G::LDR, m * 16, w * 16, dk[m] * a.scale);   // dK [j][d], own rows j
+        wave_fence();
+        store_rows16<T, D>(sY, a.dk, a.ldd, nk, wy, wx, a.H, a.W, a.shift, h * D, w * 16);
+        __syncthreads();                                     // sX / sY / sQ / sDO are free: all waves are past their last reads
+#pragma unroll
+        for (int m = 0; m < G::DT; ++m) store_acc_T<T>(sY, G::LDR, m * 16, w * 16, dq[m] * a.scale);         // dQ [i][d], own rows i
+        wave_fence();
+        store_rows16<T, D>(sY, a.dq, a.ldd, nq, wy, wx, a.H, a.W, a.shift, h * D, w * 16, dqx);
+        // the next window's loads touch neither sY nor anything a wave still reads
     }
+    // flush the bias-gradient accumulators: fold the (i, j) pairs into the 225 relative positions on chip, then one
+    // atomic per bin into the parameter layout [table][225][heads] (all workgroups of a head hit the same 225 words)
+    float* bins = reinterpret_cast<float*>(smem + S::OFF_BIN);
+    __syncthreads();
+    for (int idx = threadIdx.x; idx < 225; idx += NTH) bins[idx] = 0.f;
+    __syncthreads();
+#pragma unroll
+    for (int jt = 0; jt < 4; ++jt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int j = jt * 16 + ((l >> 4) << 2) + r;
+            atomicAdd(&bins[((i >> 3) - (j >> 3) + 7) * 15 + (i & 7) - (j & 7) + 7], dbacc[jt][r]);
+        }
+    __syncthreads();
+    float* dst = a.dbias + (size_t)(lq * a.L + lk) * 225 * a.heads;
+    for (int idx = threadIdx.x; idx < 225; idx += NTH) atomicAdd(dst + idx * a.heads + h, bins[idx]);
 }
 
 
@@ -690,9 +469,8 @@ template <typename T> struct FiltTab {
     static constexpr int LDP = 64 * SZ + 16;
     static constexpr int OFF_CU = 0, OFF_C2 = 48 * LDP, OFF_SU = 80 * LDP, OFF_S2N = 128 * LDP, OFF_MW = 160 * LDP;
     static constexpr int BYTES = OFF_MW + NU * NV * 4;      // with the mask weights on chip
-    static constexpr int BYTES_NOMW = OFF_MW;                // mask weights read from global (L1-resident, 8 values per lane and window)
 };
-template <typename T, bool MW> FW_DEV void stage_filter_tables(char* lds, const char* lfs) {
+template <typename T> FW_DEV void stage_filter_tables(char* lds, const char* lfs) {
     using F = FiltTab<T>;
     constexpr int SZ = F::SZ, GR = 64 * SZ / 16;                       // 16-byte granules per 64-element row
     for (int idx = threadIdx.x; idx < 160 * GR; idx += NTH) {
@@ -700,18 +478,17 @@ template <typename T, bool MW> FW_DEV void stage_filter_tables(char* lds, const 
         const int src = r < 48 ? OFF_CU + r * 64 : r < 80 ? OFF_C2 + (r - 48) * 64 : r < 128 ? OFF_SU + (r - 80) * 64 : OFF_S2N + (r - 128) * 64;
         *reinterpret_cast<uint4*>(lds + r * F::LDP + g * 16) = *reinterpret_cast<const uint4*>(lfs + (size_t)src * SZ + g * 16);
     }
-    if constexpr (MW) {
-        const char* mw = lfs + (size_t)OFF_END * SZ;
-        for (int idx = threadIdx.x; idx < NU * NV / 4; idx += NTH)
-            *reinterpret_cast<uint4*>(lds + F::OFF_MW + idx * 16) = *reinterpret_cast<const uint4*>(mw + idx * 16);
-    }
+    const char* mw = lfs + (size_t)OFF_END * SZ;
+    for (int idx = threadIdx.x; idx < NU * NV / 4; idx += NTH)
+        *reinterpret_cast<uint4*>(lds + F::OFF_MW + idx * 16) = *reinterpret_cast<const uint4*>(mw + idx * 16);
 }
 template <typename T> FW_DEV uint4 frag_neg(const uint4& v) {
     constexpr unsigned m = sizeof(T) == 2 ? 0x80008000u : 0x80000000u;
     return make_uint4(v.x ^ m, v.y ^ m, v.z ^ m, v.w ^ m);
 }
-// B1 on NT tiles at once.  in[t][jt] / out[t][jt] as in band_filter; scrA[t], scrB[t]: per-tile scratch pairs (>= 64*LDP and
-// >= max(64*LDP, 2*64*LDV) bytes) free on entry and on return; tab: the LDS image of stage_filter_tables.
+// B1, the disc band filter, on NT 64x64 tiles held transposed in registers.  Wave w passes / receives its strip:
+// in[t][jt] = A^T[j = 16 jt ..][i = 16 w ..], out[t][jt] = B1(A)^T likewise.  scrA[t], scrB[t]: per-tile workgroup-wide scratch pairs
+// (>= 64*LDP and >= max(64*LDP, 2*64*LDV) bytes) free on entry and on return; tab: the LDS image of stage_filter_tables.
 template <typename T, int NT>
 FW_DEV void band_filter2(const f32x4 (&in)[NT][4], f32x4 (&out)[NT][4], char* const (&scrA)[NT], char* const (&scrB)[NT], const char* tab,
                          const float* Mw) {
@@ -850,8 +627,8 @@ FW_DEV float bias_mask_lds(const float* bins, int i, int j, int shift, bool last
     return b;
 }
 
-// DUAL = true : both backward filters in one pass, mask weights on chip, one workgroup per CU (bf16: 111 KB of LDS)
-// DUAL = false: one filter at a time, mask weights from global memory: 79.5 KB -> two workgroups per CU (bf16)
+// Backward, bf16: both filters in one pass, mask weights on chip, one workgroup per CU (111 KB of LDS).  (One filter at a time with
+// the mask weights read from global memory -- 79.5 KB, two workgroups per CU -- lost to it and was removed; git history has it.)
 // The 16 score elements of a lane are the same (query i, key j) pairs in every window: their relative-position biases and
 // whether the pair straddles the cyclic shift's seam vertically / horizontally are computed ONCE per workgroup; per window the
 // -100 mask is one select per element (it applies in the last window row / column only, decoder_Uformer.py:634-651).
@@ -878,12 +655,11 @@ struct BiasRegs {
     FW_MEM unsigned mask(bool last_y, bool last_x) const { return (last_y ? dy : 0u) | (last_x ? dx : 0u); }
 };
 
-template <typename T, int D, int LFS, bool DUAL = true> struct Smem2 {
+template <typename T, int D, int LFS> struct Smem2 {
     using G = Geo<T, D>;
-    static constexpr bool MW = DUAL || sizeof(T) == 4;
-    static constexpr int TAB = LFS == 2 ? (MW ? FiltTab<T>::BYTES : FiltTab<T>::BYTES_NOMW) : 0;
+    static constexpr int TAB = LFS == 2 ? FiltTab<T>::BYTES : 0;
     static constexpr int SCR = 2 * 64 * G::LDV > 64 * G::LDP ? 2 * 64 * G::LDV : 64 * G::LDP;
-    static constexpr int NTF = (LFS == 2 && sizeof(T) == 2 && DUAL) ? 2 : 1;         // tiles per backward filter pass
+    static constexpr int NTF = (LFS == 2 && sizeof(T) == 2) ? 2 : 1;                 // tiles per backward filter pass
     static constexpr int OFF_BIAS = TAB;
     static constexpr int OFF_T = TAB + 1024;                                          // tiles start here
     static constexpr int RA = SCR > G::TILE_D ? SCR : G::TILE_D;                      // fwd: Q -> P' / scratch A
@@ -906,7 +682,7 @@ __global__ __launch_bounds__(NTH, 1) void attn2_fwd_kernel(AttnArgs a) {
     const int per = (a.nwin + gridDim.x - 1) / gridDim.x;
     const int win_begin = blockIdx.x * per, win_end = min(a.nwin, win_begin + per);
     if (win_begin >= win_end) return;
-    if constexpr (LFS == 2) stage_filter_tables<T, true>(smem, a.lfs);
+    if constexpr (LFS == 2) stage_filter_tables<T>(smem, a.lfs);
     const float* Mw = reinterpret_cast<const float*>(smem + FiltTab<T>::OFF_MW);
     {
         const float* tb = a.bias + (size_t)(lq * a.L + lq) * 225 * a.heads + h;
@@ -1000,10 +776,10 @@ __global__ __launch_bounds__(NTH, 1) void attn2_fwd_kernel(AttnArgs a) {
     }
 }
 
-template <typename T, int D, int LFS, bool DUAL>
+template <typename T, int D, int LFS>
 __global__ __launch_bounds__(NTH, 1) void attn2_bwd_kernel(AttnArgs a) {
     using G = Geo<T, D>;
-    using S = Smem2<T, D, LFS, DUAL>;
+    using S = Smem2<T, D, LFS>;
     constexpr int NTF = S::NTF;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const char* tab = smem;
@@ -1019,9 +795,8 @@ __global__ __launch_bounds__(NTH, 1) void attn2_bwd_kernel(AttnArgs a) {
     const int per = (a.nwin + gridDim.x - 1) / gridDim.x;
     const int win_begin = blockIdx.x * per, win_end = min(a.nwin, win_begin + per);
     if (win_begin >= win_end) return;
-    if constexpr (LFS == 2) stage_filter_tables<T, S::MW>(smem, a.lfs);
-    const float* Mw = S::MW ? reinterpret_cast<const float*>(smem + FiltTab<T>::OFF_MW)
-                            : reinterpret_cast<const float*>(a.lfs + (size_t)OFF_END * TT<T>::SZ);
+    if constexpr (LFS == 2) stage_filter_tables<T>(smem, a.lfs);
+    const float* Mw = reinterpret_cast<const float*>(smem + FiltTab<T>::OFF_MW);
     {
         const float* tb = a.bias + (size_t)(lq * a.L + lq) * 225 * a.heads + h;
         for (int idx = threadIdx.x; idx < 225; idx += NTH) bins[idx] = tb[(size_t)idx * a.heads];
@@ -1536,53 +1311,49 @@ int fwd2_launch(const AttnArgs& a, hipStream_t st) {
     hipLaunchKernelGGL((attn2_fwd_kernel<T, D, LFS>), dim3(chunks, a.heads, a.L), dim3(NTH), S::FWD_BYTES, st, a);
     FW_LAUNCH_RET();
 }
-template <typename T, int D, int LFS, bool DUAL>
-int bwd2_launch_d(const AttnArgs& a, hipStream_t st) {
-    using S = Smem2<T, D, LFS, DUAL>;
-    FW_SET_LDS_ONCE((attn2_bwd_kernel<T, D, LFS, DUAL>), S::BWD_BYTES);
+template <typename T, int D, int LFS>
+int bwd2_launch(const AttnArgs& a, hipStream_t st) {
+    using S = Smem2<T, D, LFS>;
+    FW_SET_LDS_ONCE((attn2_bwd_kernel<T, D, LFS>), S::BWD_BYTES);
     const int per_cu = 2 * S::BWD_BYTES <= 160 * 1024 ? 2 : 1;
     int chunks = (256 * per_cu) / (a.heads * a.L);
     if (chunks < 1) chunks = 1;
     if (chunks > a.nwin) chunks = a.nwin;
-    hipLaunchKernelGGL((attn2_bwd_kernel<T, D, LFS, DUAL>), dim3(chunks, a.heads, a.L), dim3(NTH), S::BWD_BYTES, st, a);
+    hipLaunchKernelGGL((attn2_bwd_kernel<T, D, LFS>), dim3(chunks, a.heads, a.L), dim3(NTH), S::BWD_BYTES, st, a);
     FW_LAUNCH_RET();
-}
-template <typename T, int D, int LFS>
-int bwd2_launch(const AttnArgs& a, hipStream_t st) {
-    static const int dual = getenv("FW_ATTN_DUAL") ? atoi(getenv("FW_ATTN_DUAL")) : 1;
-    if constexpr (LFS == 2 && sizeof(T) == 2) { if (!dual) return bwd2_launch_d<T, D, LFS, false>(a, st); }
-    return bwd2_launch_d<T, D, LFS, true>(a, st);
 }
 
-template <typename T, int D, int NKT, int LFS>
+template <typename T, int D>
 int fwd_launch(const AttnArgs& a, hipStream_t st) {
-    using S = Smem<T, D, NKT, LFS>;
-    FW_SET_LDS_ONCE((attn_fwd_kernel<T, D, NKT, LFS>), S::FWD_BYTES);
+    using S = Smem<T, D>;
+    FW_SET_LDS_ONCE((attn_fwd_kernel<T, D>), S::FWD_BYTES);
     const int items = a.nwin * a.L * a.heads;
-    hipLaunchKernelGGL((attn_fwd_kernel<T, D, NKT, LFS>), dim3(items < 4096 ? items : 4096), dim3(NTH), S::FWD_BYTES, st, a);
+    hipLaunchKernelGGL((attn_fwd_kernel<T, D>), dim3(items < 4096 ? items : 4096), dim3(NTH), S::FWD_BYTES, st, a);
     FW_LAUNCH_RET();
 }
-template <typename T, int D, int NKT, int LFS>
+template <typename T, int D>
 int bwd_launch(const AttnArgs& a, hipStream_t st) {
-    using S = SmemB<T, D, NKT, LFS>;
-    FW_SET_LDS_ONCE((attn_bwd_kernel<T, D, NKT, LFS>), S::BYTES);
-    hipLaunchKernelGGL((attn_bwd_kernel<T, D, NKT, LFS>), dim3(a.chunks, a.heads, a.L), dim3(NTH), S::BYTES, st, a);
+    using S = SmemB<T, D>;
+    FW_SET_LDS_ONCE((attn_bwd_kernel<T, D>), S::BYTES);
+    hipLaunchKernelGGL((attn_bwd_kernel<T, D>), dim3(a.chunks, a.heads, a.L), dim3(NTH), S::BYTES, st, a);
     FW_LAUNCH_RET();
 }
 
 template <typename T>
 int dispatch(bool bwd, int D, int nkt, int lfs, const AttnArgs& a, hipStream_t st) {
-    static const int v2 = getenv("FW_ATTN_V2") ? atoi(getenv("FW_ATTN_V2")) : 1;              // 0: the v1 kernels for one key tile too
+    // one key tile over the query's own band (decoder W-MSA + LFS, encoder intra / origin, ViT): the v2 kernels
 #define FW_ATT2(DD, FF)                                                                        \
-    if (v2 && D == DD && nkt == 1 && a.mode == 0 && lfs == FF)                                 \
+    if (D == DD && nkt == 1 && a.mode == 0 && lfs == FF)                                       \
         return bwd ? bwd2_launch<T, DD, FF>(a, st) : fwd2_launch<T, DD, FF>(a, st);
     FW_ATT2(56, 0) FW_ATT2(56, 1) FW_ATT2(56, 2) FW_ATT2(28, 0) FW_ATT2(64, 0)
 #undef FW_ATT2
-    if (v2 && D == 28 && nkt == 2 && a.mode == 1 && a.L == 3 && lfs == 0) return x2_launch<T, 28>(bwd, a, st);
-#define FW_ATT(DD, KK, FF)                                                                     \
-    if (D == DD && nkt == KK && lfs == FF)                                                     \
-        return bwd ? bwd_launch<T, DD, KK, FF>(a, st) : fwd_launch<T, DD, KK, FF>(a, st);
-    FW_ATT(56, 1, 0) FW_ATT(56, 1, 1) FW_ATT(56, 1, 2) FW_ATT(28, 1, 0) FW_ATT(28, 2, 0) FW_ATT(64, 1, 0)
+    // inter-band, three bands: both key tiles in one pass
+    if (D == 28 && nkt == 2 && a.mode == 1 && a.L == 3 && lfs == 0) return x2_launch<T, 28>(bwd, a, st);
+    // what is left for the v1 kernels: inter-band with two bands (mode 1, one key tile of the other band, no frequency selection)
+#define FW_ATT(DD)                                                                             \
+    if (D == DD && nkt == 1 && lfs == 0)                                                       \
+        return bwd ? bwd_launch<T, DD>(a, st) : fwd_launch<T, DD>(a, st);
+    FW_ATT(56) FW_ATT(28) FW_ATT(64)
 #undef FW_ATT
     return -1000;      // unsupported (head_dim, key tiles, lfs) combination
 }
@@ -1640,8 +1411,8 @@ extern "C" int fw_attn_bwd(int dtype, int D, int nkt, int lfs, const void* q, co
     FW_CHECK_ARG(dq_pad == 0 || (dq_pad > 0 && dq_pad < 8 && (heads * D + dq_pad) % 8 == 0));
     FW_CHECK_ARG(dq_pad == 0 || ((dq_pad * sz) % (((D * sz) % 16 == 0) ? 16 : 8) == 0 && (D + dq_pad) * sz <= ((D * sz + 63) / 64) * 64));
     a.dq_pad = dq_pad;
-    static const int bwd_wgs = getenv("FW_ATTN_BWD_WGS") ? atoi(getenv("FW_ATTN_BWD_WGS")) : 1024;
-    int chunks = bwd_wgs / (heads * L);          // 4-wave workgroups, 2 per CU: about two rounds of the chip
+    constexpr int BWD_WGS = 1024;                // v1 backward: 4-wave workgroups, 2 per CU: about two rounds of the chip
+    int chunks = BWD_WGS / (heads * L);
     if (chunks < 1) chunks = 1;
     if (chunks > a.nwin) chunks = a.nwin;
     a.chunks = chunks;

@@ -1322,8 +1322,9 @@ __global__ void fill_kernel(float* __restrict__ p, long n, float v) {
 }  // namespace
 
 #define ST ((hipStream_t)stream)
-static int dw_tiled() { static const int v = getenv("FW_DWCONV_TILED") ? atoi(getenv("FW_DWCONV_TILED")) : 1; return v; }
-static long dw_tiled_min() { static const long v = getenv("FW_DWCONV_TILED_MIN") ? atol(getenv("FW_DWCONV_TILED_MIN")) : 10000000L; return v; }   // elements B*H*W*C from which the LDS-tiled form is used: 272.8 images/s at 80 M (stage 0 only), 273.7 at 20 M, 274.6 at 10 M, 274.0 at 1 M
+// elements B*H*W*C from which the LDS-tiled forms are used: 272.8 images/s at 80 M (stage 0 only), 273.7 at 20 M, 274.6 at 10 M, 274.0 at 1 M
+constexpr long DW_TILED_MIN = 10000000L;
+static bool dw_tiled(int B, int H, int W, int C) { return H % DT_TY == 0 && (long)B * H * W * C >= DW_TILED_MIN; }
 template <typename T, int MODE, bool GIN = false>
 static int dwconv_tile_launch(const T* in, long ldi, const float* w, const float* bias, const T* pre, T* out, T* out2, long ldo, int B, int H, int W,
                               int C, hipStream_t st) {
@@ -1378,9 +1379,8 @@ extern "C" int fw_dwconv_fwd(int dtype, const void* g1, long ld1, int in_gelu, c
     FW_CHECK_ARG(g1 && w && bias && h2 && g2 && C % e == 0 && ld1 % e == 0 && ld2 % e == 0 && W % SX == 0);
     const long n = (long)B * H * (W / SX) * (C / 4);
     // the LDS-tiled form wins where the tensors outgrow the 256 MB infinity cache (stage-0 layers); below that the strips are as fast
-    static const int piped = getenv("FW_DWCONV_PIPE_FWD") ? atoi(getenv("FW_DWCONV_PIPE_FWD")) : 1;
-    if (piped && dw_tiled() && H % DT_TY == 0 && (long)B * H * W * C >= dw_tiled_min() && (long)H * W * ld1 < (1L << 31)) {
-        static const long want = getenv("FW_DWCONV_PIPE_WGS") ? atol(getenv("FW_DWCONV_PIPE_WGS")) : 2048;
+    if (dw_tiled(B, H, W, C) && (long)H * W * ld1 < (1L << 31)) {      // a workgroup walks several tiles (dwconv_fwd_pipe_kernel)
+        constexpr long want = 2048;                 // workgroups aimed for
         const long ncol = (long)((C + DT_CB - 1) / DT_CB) * ((W + DT_TX - 1) / DT_TX), nrow = (long)B * (H / DT_TY);
         long NT = ncol * nrow / want;
         NT = NT < 1 ? 1 : (NT > 32 ? 32 : NT);
@@ -1399,7 +1399,7 @@ extern "C" int fw_dwconv_fwd(int dtype, const void* g1, long ld1, int in_gelu, c
 #undef FW_PIPE_FWD
         FW_LAUNCH_RET();
     }
-    if (dw_tiled() && H % DT_TY == 0 && (long)B * H * W * C >= dw_tiled_min()) {
+    if (dw_tiled(B, H, W, C)) {
         if (dtype == FW_DT_BF16)
             return in_gelu ? dwconv_tile_launch<bf16raw, 0, true>((const bf16raw*)g1, ld1, w, bias, (const bf16raw*)nullptr, (bf16raw*)h2, (bf16raw*)g2, ld2, B, H, W, C, ST)
                            : dwconv_tile_launch<bf16raw, 0>((const bf16raw*)g1, ld1, w, bias, (const bf16raw*)nullptr, (bf16raw*)h2, (bf16raw*)g2, ld2, B, H, W, C, ST);
@@ -1421,16 +1421,15 @@ extern "C" int fw_dwconv_bwd(int dtype, const void* dh2, long ldg, const void* g
     const long n = (long)B * H * (W / SX) * (C / 4);
     const int nvg = (C / 4 + WG_VL - 1) / WG_VL;
     const long nst = (long)B * H * (W / SX);
-    static const int nstrip_max = getenv("FW_DWWG_NSTRIP") ? atoi(getenv("FW_DWWG_NSTRIP")) : 16;
-    int NSTRIP = nstrip_max;                       // strips per thread: fewer on small layers so that enough blocks are in flight
-    static const long wg_min_blocks = getenv("FW_DWWG_MIN_BLOCKS") ? atol(getenv("FW_DWWG_MIN_BLOCKS")) : 384;
+    constexpr int NSTRIP_MAX = 16;
+    constexpr long wg_min_blocks = 384;
+    int NSTRIP = NSTRIP_MAX;                       // strips per thread: fewer on small layers so that enough blocks are in flight
     while (NSTRIP > 2 && ((nst + (long)NSTRIP * WG_SL - 1) / ((long)NSTRIP * WG_SL)) * nvg < wg_min_blocks) NSTRIP >>= 1;   // every block ends in 1280 atomics: not too many blocks
     const long nsg = (nst + (long)NSTRIP * WG_SL - 1) / ((long)NSTRIP * WG_SL);
     const dim3 gridw((unsigned)(nsg * nvg));
-    const bool tiled = dw_tiled() && H % DT_TY == 0 && (long)B * H * W * C >= dw_tiled_min();
-    static const int fused = getenv("FW_DWCONV_FUSED_BWD") ? atoi(getenv("FW_DWCONV_FUSED_BWD")) : 1;
-    if (tiled && fused && !g1 && (long)H * W * ldg < (1L << 31)) {                    // one pass: data gradient + weight / bias gradient (dwconv_bwd_fused_kernel)
-        static const long want = getenv("FW_DWCONV_FUSED_WGS") ? atol(getenv("FW_DWCONV_FUSED_WGS")) : 1024;
+    const bool tiled = dw_tiled(B, H, W, C);
+    if (tiled && !g1 && (long)H * W * ldg < (1L << 31)) {                    // one pass: data gradient + weight / bias gradient (dwconv_bwd_fused_kernel)
+        constexpr long want = 1024;
         const long ncol = (long)((C + DT_CB - 1) / DT_CB) * ((W + DT_TX - 1) / DT_TX), nrow = (long)B * (H / DT_TY);
         long NT = ncol * nrow / want;               // tiles a workgroup walks: as many as still leave ~`want` workgroups
         NT = NT < 1 ? 1 : (NT > 32 ? 32 : NT);

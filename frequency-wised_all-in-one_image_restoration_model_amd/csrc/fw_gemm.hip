@@ -422,7 +422,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs a) {
 }
 
 // =====================================================================================================
-// Weight-gradient kernel, bf16:  C[m][n] = sum_t X[t][m] W[t][n]  (both operands token-major: dW = dY^T x).
+// Weight-gradient product, bf16:  C[m][n] = sum_t X[t][m] W[t][n]  (both operands token-major: dW = dY^T x).
 // The tile kernel above transposes both operands in registers while staging them (v_perm + 8-byte LDS writes every K step).
 // Here the token-major tiles go to LDS AS THEY ARE -- global_load_lds, no VGPR round trip, no VALU -- and the MFMA fragments,
 // which need 8 consecutive TOKENS per lane, are read with gfx950's transposing LDS read (ds_read_b64_tr_b16, two per
@@ -432,19 +432,6 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs a) {
 // The bias gradient (column sums of X) comes from MFMAs against an all-ones A fragment -- no extra pass over the data.
 FW_DEV int swz256(int r) { return ((r & 3) << 2) | ((r >> 2) & 3); }
 
-// one [64 tokens][128 cols] tile; wave w fills token rows 16w .. 16w+15 with 4 wave-instructions of 4 rows each
-FW_DEV void glds_issue_km(const char* base, long ld, int col0, int cols_total, int k0, char* tile) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int it = 0; it < 4; ++it) {
-        const int R0 = wave * 16 + it * 4;
-        const int r = R0 + (lane >> 4), p = lane & 15;
-        int col = col0 + ((p ^ swz256(r)) << 3);
-        if (col >= cols_total) col = 0;                    // columns past the matrix only feed masked outputs; stay inside the row
-        const char* g = base + ((long)(k0 + r) * ld + col) * 2;
-        __builtin_amdgcn_global_load_lds((glb_void_t*)g, (lds_void_t*)(tile + R0 * 256), 16, 0, 0);
-    }
-}
 // MFMA fragment of operand rows (= tile columns) m0 .. m0+15 over token chunk c (32 tokens): two transposing reads
 FW_DEV uint4 frag_tr256(const char* tile, int m0, int chunk) {
     const int l = lane_id();
@@ -455,116 +442,6 @@ FW_DEV uint4 frag_tr256(const char* tile, int m0, int chunk) {
     const uint2 lo = __builtin_bit_cast(uint2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((fw_lds_s16x4*)p0));
     const uint2 hi = __builtin_bit_cast(uint2, __builtin_amdgcn_ds_read_tr16_b64_v4i16((fw_lds_s16x4*)p1));
     return make_uint4(lo.x, lo.y, hi.x, hi.y);
-}
-
-// XT = true : X token-major as well (dW = dY^T x; bias gradient by ones-MFMA).
-// XT = false: X k-contiguous [M][K] (dX = dY W with W stored [K][N]): its tile is the 128-byte-row image of gemm_kernel
-//             (global_load_lds + frag_sw), only W takes the transposing path.
-template <bool XT>
-__global__ __launch_bounds__(256) void gemm_tr_kernel(GemmArgs a) {
-    using T = bf16raw;
-    constexpr int KT = 64, WM = 4, TILE = 64 * 256;      // k per step, m tiles per wave, bytes per operand tile (= 128 * LDS_ROW)
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    auto xs = [&](int i) -> char* { return smem + i * 2 * TILE; };
-    auto ws = [&](int i) -> char* { return smem + i * 2 * TILE + TILE; };
-    const int wave = threadIdx.x >> 6;
-    int bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
-    {                                                     // contiguous eighths of the (slice, n tile, m tile) order per XCD, see gemm_kernel
-        const unsigned total = gridDim.x * gridDim.y * gridDim.z;
-        if (gridDim.z > 1) {
-            const unsigned lin = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
-            const unsigned w = xcd_contiguous(lin, total);
-            bx = (int)(w % gridDim.x);
-            by = (int)((w / gridDim.x) % gridDim.y);
-            bz = (int)(w / (gridDim.x * gridDim.y));
-        } else if (gridDim.z == 1 && gridDim.y > 1) {
-            // no split-K: every XCD takes a contiguous eighth of a GROUPED tile order (bands of 8 m tiles, n tiles swept inside a
-            // band), so the ~64 tiles an XCD has in flight touch 8 x 8 operand panels that fit its 4 MB L2 instead of re-fetching
-            // X once per n tile (PMC: 2.5x the algorithmic bytes crossed the fabric in plain row-major order)
-            const unsigned lin = blockIdx.x + gridDim.x * blockIdx.y;
-            const unsigned w = xcd_contiguous(lin, total);
-            const unsigned per_band = 8 * gridDim.y;
-            const unsigned band = w / per_band, first = band * 8;
-            const unsigned gsz = min(gridDim.x - first, 8u);
-            bx = (int)(first + (w % per_band) % gsz);
-            by = (int)((w % per_band) / gsz);
-        }
-    }
-    const int m_blk = bx * 128, n_blk = by * 128;
-    const int wm0 = (wave & 1) * 64, wn0 = (wave >> 1) * 64;
-    const int k_begin = bz * a.kper;
-    const int k_end = min(a.K, k_begin + a.kper);
-    const int nsteps = (k_end - k_begin) / KT;           // whole steps only (host guarantees K % KT == 0)
-
-    f32x4 acc[4][WM], xsacc[WM];
-    zero_acc(acc);
-#pragma unroll
-    for (int m = 0; m < WM; ++m) xsacc[m] = f32x4{0.f, 0.f, 0.f, 0.f};
-    const bool do_xsum = XT && a.xsum != nullptr && by == 0 && wn0 == 0;    // wave-uniform
-    const uint4 ones = make_uint4(0x3F803F80u, 0x3F803F80u, 0x3F803F80u, 0x3F803F80u);   // bf16 1.0 x 8
-
-    auto issue = [&](int k0, int buf) {
-        if constexpr (XT) glds_issue_km(a.X, a.ldx, m_blk, a.M, k0, xs(buf));
-        else glds_issue<T, BM>(a.X, a.ldx, m_blk, a.M, k0 * 2, xs(buf));
-        glds_issue_km(a.W, a.ldw, n_blk, a.N, k0, ws(buf));
-    };
-    if (nsteps > 0) issue(k_begin, 0);
-    __syncthreads();
-    for (int s = 0; s < nsteps; ++s) {
-        const int cur = s & 1;
-        if (s + 1 < nsteps) issue(k_begin + (s + 1) * KT, cur ^ 1);
-#pragma unroll
-        for (int c = 0; c < 2; ++c) {
-            uint4 af[4], bfr[WM];
-#pragma unroll
-            for (int m = 0; m < 4; ++m) af[m] = frag_tr256(ws(cur), wn0 + 16 * m, c);
-#pragma unroll
-            for (int n = 0; n < WM; ++n) bfr[n] = XT ? frag_tr256(xs(cur), wm0 + 16 * n, c) : frag_sw(xs(cur), wm0 + 16 * n, c);
-#pragma unroll
-            for (int m = 0; m < 4; ++m)
-#pragma unroll
-                for (int n = 0; n < WM; ++n) mma_chunk<T>(acc[m][n], af[m], bfr[n]);
-            if (do_xsum) {
-#pragma unroll
-                for (int n = 0; n < WM; ++n) mma_chunk<T>(xsacc[n], ones, bfr[n]);
-            }
-        }
-        __syncthreads();                                 // also drains the in-flight global_load_lds (vmcnt(0))
-    }
-    const int l = lane_id();
-    if (do_xsum && (l >> 4) == 0) {                      // every row of the ones-product holds the column sums: take row 0
-#pragma unroll
-        for (int n = 0; n < WM; ++n) {
-            const int m = m_blk + wm0 + n * 16 + l;
-            if (m < a.M) {
-                if (a.xsum_zstride > 0) a.xsum[(long)bz * a.xsum_zstride + m] = xsacc[n][0];
-                else atomicAdd(a.xsum + m, xsacc[n][0]);
-            }
-        }
-    }
-    f32x4 bias4[4];
-#pragma unroll
-    for (int nt = 0; nt < 4; ++nt) {
-        const int n0 = n_blk + wn0 + nt * 16 + ((l >> 4) << 2);
-        bias4[nt] = epi_bias(a, n0 < a.N ? n0 : 0, bz);
-    }
-#pragma unroll
-    for (int mt = 0; mt < WM; ++mt) {
-        const int m = m_blk + wm0 + mt * 16 + (l & 15);
-        const int mc = m < a.M ? m : a.M - 1;
-        const float rs = a.rowscale ? a.rowscale[mc / a.rows_per_scale] : 1.0f;
-        uint4 ext[4];
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt) {
-            const int n0 = n_blk + wn0 + nt * 16 + ((l >> 4) << 2);
-            epi_fetch<T>(a, ext[nt], mc, n0 < a.N ? n0 : 0, bz);
-        }
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt) {
-            const int n0 = n_blk + wn0 + nt * 16 + ((l >> 4) << 2);
-            if (m < a.M && n0 < a.N) epi_apply<T>(a, bias4[nt], ext[nt], acc[nt][mt], m, n0, rs, bz);
-        }
-    }
 }
 
 // Epilogue of a 128 x (64 * 4 / WM ... ) wave tile: acc[nt][mt] holds C[m = .. + mt*16 + (l & 15)][n0 = .. + nt*16 + 4*(l >> 4) .. +3].
@@ -740,16 +617,19 @@ static inline bool plain_epilogue(const GemmArgs& a) {
     return a.act == 0 && !a.rowscale && !a.residual && !a.C2 && a.alpha == 1.0f && !(a.accumulate && a.c_zstride == 0);
 }
 
-// ---- the same product with a DEEP global -> LDS pipeline ------------------------------------------------------------
-// gemm_tr_kernel above keeps ONE stage in flight per workgroup and drains it (`__syncthreads()` = vmcnt(0)) every K step: with
-// two workgroups per CU a step costs one L2 / fabric round trip (1.4 us for 32 KB measured in the B = 16 step), i.e. the kernel
-// is bound by LATENCY, not by bytes or MFMAs.  Here the stages form a ring of NS LDS buffers: NS-1 stages are in flight, a wave
+// ---- that product with a DEEP global -> LDS pipeline ----------------------------------------------------------------
+// XT = true : X token-major as well (dW = dY^T x; bias gradient by ones-MFMA).
+// XT = false: X k-contiguous [M][K] (dX = dY W with W stored [K][N]): its tile is the 128-byte-row image of gemm_kernel
+//             (LDS-DMA + frag_sw), only W takes the transposing path.
+// A first form of this kernel (removed; git history has it) kept ONE stage in flight per workgroup and drained it
+// (`__syncthreads()` = vmcnt(0)) every K step: with two workgroups per CU a step cost one L2 / fabric round trip (1.4 us for 32 KB
+// measured in the B = 16 step), i.e. it was bound by LATENCY, not by bytes or MFMAs.  Here the stages form a ring of NS LDS buffers: NS-1 stages are in flight, a wave
 // waits only for ITS loads of the oldest one (counted `s_waitcnt vmcnt(N)`: loads complete in issue order), a raw `s_barrier`
 // then makes every wave's share of that stage visible, the buffer freed by the previous step is re-issued at once, and the
 // MFMAs of the stage run while the younger stages keep arriving.  One barrier per stage; WAR is covered by the same barrier
 // (a wave reaches it only after the MFMAs that consumed its fragments of the previous stage).
 // hipcc (ROCm 7.2) cannot tell which LDS bytes an in-flight global_load_lds will write, so it puts `s_waitcnt vmcnt(0)` in front
-// of the first ds_read that follows one (it does so in gemm_tr_kernel / gemm_kernel above: their "prefetch" of the next stage is
+// of the first ds_read that follows one (it does so in gemm_kernel above: its "prefetch" of the next stage is
 // waited for BEFORE the current stage is computed -- no overlap inside a workgroup).  The ring therefore issues its LDS-DMA from
 // inline asm, which the compiler neither counts nor waits for, and counts completion itself (cdna_hip_programming.md 5.7):
 // M0 carries the wave-uniform LDS destination and is written in the same statement that uses it.
@@ -926,7 +806,7 @@ static inline int staged_mode(const GemmArgs& a) {
 template <bool XT, int KT, int NS, bool PLAIN>
 FW_DEV void tr_ring_tile(const GemmArgs& a, int bx, int by, int bz, char* smem) {
     using T = bf16raw;
-    static_assert(NS >= 2 && NS <= 5, "ring depth");
+    static_assert(NS == 2 || NS == 3, "ring depth");
     constexpr int WM = 4;
     constexpr bool X64 = !XT && KT == 32;                      // k-contiguous X in 64-byte rows (GldsKc64): 32-deep steps, e.g. K = 224
     constexpr int XB = XT ? KT * 256 : 128 * (X64 ? ROW64 : LDS_ROW), WB = KT * 256, STAGE = XB + WB;
@@ -969,8 +849,6 @@ FW_DEV void tr_ring_tile(const GemmArgs& a, int bx, int by, int bz, char* smem) 
         // stages s+1 .. s+NS-2 may stay in flight; near the tail fewer were issued
         const int younger = min(NS - 2, nsteps - 1 - s);
         if (younger >= NS - 2) wait_vmcnt<(NS - 2) * LPS>();
-        else if (NS >= 4 && younger == NS - 3) wait_vmcnt<(NS >= 4 ? NS - 3 : 0) * LPS>();
-        else if (NS >= 5 && younger == NS - 4) wait_vmcnt<(NS >= 5 ? NS - 4 : 0) * LPS>();
         else wait_vmcnt<0>();
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
@@ -1013,7 +891,7 @@ FW_DEV void tr_ring_tile(const GemmArgs& a, int bx, int by, int bz, char* smem) 
 }
 
 template <bool XT, int KT, int NS, bool PLAIN>
-__global__ __launch_bounds__(256, (KT == 32 && NS == 3) ? 3 : 2) void gemm_tr_ring_kernel(GemmArgs a) {
+__global__ __launch_bounds__(256, KT == 32 ? 3 : 2) void gemm_tr_ring_kernel(GemmArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     int bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
     {                                                     // contiguous eighths of the (slice, n tile, m tile) order per XCD, see gemm_kernel
@@ -1172,7 +1050,8 @@ int launch_tr_ring(const GemmArgs& a, hipStream_t st) {
 
 // ---- gemm_kernel's NT product (both operands k-contiguous, whole 128-byte K steps) on the same ring ---------------------
 // Forward Linears of the C >= 224 stages, im2col / pixel-shuffle convolutions: y = x W^T.  Stage = [128 + BN rows][128 B].
-// BN = 128: 4 stages of 32 KB (1 workgroup per CU, 96 KB in flight); BN = 64: 3 stages of 24 KB (2 workgroups per CU).
+// Two stages (BN = 128: 2 x 32 KB, two workgroups per CU), or three of 24 KB at BN = 64 (still two workgroups per CU).  Deeper
+// rings at BN = 128 (3 or 4 stages, one resident workgroup) measured slower and were removed; git history has them.
 template <typename T, int BN, int NS, bool PLAIN>
 __global__ __launch_bounds__(256) void gemm_ring_kernel(GemmArgs a) {
     constexpr int KT = 128 / TT<T>::SZ;
@@ -1226,7 +1105,6 @@ __global__ __launch_bounds__(256) void gemm_ring_kernel(GemmArgs a) {
     for (int s = 0; s < nsteps; ++s) {
         const int younger = min(NS - 2, nsteps - 1 - s);
         if (younger >= NS - 2) wait_vmcnt<(NS - 2) * LPS>();
-        else if (NS >= 4 && younger == NS - 3) wait_vmcnt<(NS >= 4 ? NS - 3 : 0) * LPS>();
         else wait_vmcnt<0>();
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
@@ -1269,7 +1147,7 @@ int launch_ring(const GemmArgs& a, hipStream_t st) {
     return plain_epilogue(a) ? launch_ring_p<T, BN, NS, true>(a, st) : launch_ring_p<T, BN, NS, false>(a, st);
 }
 
-// ---- the NT product on 64-BYTE K steps: four 16 KB stages in the same 64 KB (BN = 128), three loads in flight ----------------
+// ---- the NT product on 64-BYTE K steps: three 16 KB stages (BN = 128), two loads in flight, three workgroups per CU ----------
 // gemm_ring_kernel above holds 2 x 32 KB stages: one stage in flight per workgroup, 62 % of its wave cycles parked in s_waitcnt
 // (SQ_WAIT_ANY).  The weight-gradient kernel -- four 16 KB stages of 32-deep steps in the same LDS, two workgroups per CU -- waits
 // 33 %.  This is that shape for k-contiguous operands: LDS rows of 64 bytes, 16-byte slot p of row r stored at slot
@@ -1282,7 +1160,7 @@ __global__ __launch_bounds__(256) void gemm_ring64_kernel(GemmArgs a) {
     constexpr int WM = (BN == 128) ? 4 : 2;
     constexpr int XBYTES = BM * ROW64, WBYTES = BN * ROW64, STAGE = XBYTES + WBYTES;
     constexpr int LPS = BM / 64 + BN / 64;
-    static_assert(NS >= 3 && NS <= 5, "ring depth");
+    static_assert(NS >= 3, "ring depth");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     auto xs = [&](int i) -> char* { return smem + i * STAGE; };
     auto ws = [&](int i) -> char* { return smem + i * STAGE + XBYTES; };
@@ -1331,7 +1209,6 @@ __global__ __launch_bounds__(256) void gemm_ring64_kernel(GemmArgs a) {
         const int younger = min(NS - 2, nsteps - 1 - s);
         if (younger >= NS - 2) wait_vmcnt<(NS - 2) * LPS>();
         else if (younger == NS - 3) wait_vmcnt<(NS - 3) * LPS>();
-        else if (NS >= 5 && younger == NS - 4) wait_vmcnt<(NS >= 5 ? NS - 4 : 0) * LPS>();
         else wait_vmcnt<0>();
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
@@ -1377,14 +1254,14 @@ int launch_ring64(const GemmArgs& a, hipStream_t st) {
 // MFMA pipe (1.5 us of MFMA per 21 us tile).  A 256 x 256 tile does four times the products on twice the bytes: wave w (of 8,
 // two per SIMD) owns 128 rows (m) x 64 columns (n) = 32 accumulator tiles (128 VGPRs), a K chunk is 12 fragment reads for 32 MFMAs
 // (16 for 32 before).  Same ring discipline as gemm_ring_kernel (LDS-DMA from inline asm, counted vmcnt, one raw barrier per stage):
-//   KT = 64: 2 stages x 64 KB (128-byte rows);   KT = 32: NS stages x 32 KB (64-byte rows, three stages in flight at NS = 4).
+// 64-deep steps, 2 stages x 64 KB (128-byte rows).  (32-deep steps in 3 or 4 stages of 32 KB lost to it and were removed.)
 // WT: W stored [K][N] (input gradients dX = dY W): its tile is two [KT][128] token-major images read with ds_read_b64_tr_b16.
-template <int KT, int NS, bool WT, bool PLAIN>
+template <bool WT, bool PLAIN>
 __global__ __launch_bounds__(512) void gemm_big_kernel(GemmArgs a) {
     using T = bf16raw;
-    constexpr int WM = 8, BIG = 256;
-    constexpr int XB = BIG * (KT == 64 ? LDS_ROW : ROW64), WB = WT ? 2 * KT * 256 : XB, STAGE = XB + WB;
-    constexpr int NIX = KT == 64 ? 4 : 2, NIW = WT ? KT / 16 : NIX, LPS = NIX + NIW;
+    constexpr int KT = 64, NS = 2, WM = 8, BIG = 256;
+    constexpr int XB = BIG * LDS_ROW, WB = WT ? 2 * KT * 256 : XB, STAGE = XB + WB;
+    constexpr int NIX = 4, NIW = 4, LPS = NIX + NIW;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     auto xs = [&](int i) -> char* { return smem + i * STAGE; };
     auto ws = [&](int i) -> char* { return smem + i * STAGE + XB; };
@@ -1410,32 +1287,18 @@ __global__ __launch_bounds__(512) void gemm_big_kernel(GemmArgs a) {
     long wkstride = 0;
 #pragma unroll
     for (int it = 0; it < NIX; ++it) {
-        if constexpr (KT == 64) {
-            const int R0 = (wave * NIX + it) * 8, r = R0 + (lane >> 3), p = lane & 7;
-            int gr = m_blk + r; if (gr >= a.M) gr = a.M - 1;
-            xsrc[it] = a.X + (long)gr * a.ldx * 2 + ((p ^ (swz(r) >> 4)) << 4);
-            xoff[it] = R0 * LDS_ROW;
-        } else {
-            const int R0 = (wave * NIX + it) * 16, r = R0 + (lane >> 2), p = lane & 3;
-            int gr = m_blk + r; if (gr >= a.M) gr = a.M - 1;
-            xsrc[it] = a.X + (long)gr * a.ldx * 2 + ((p ^ swz64(r)) << 4);
-            xoff[it] = R0 * ROW64;
-        }
+        const int R0 = (wave * NIX + it) * 8, r = R0 + (lane >> 3), p = lane & 7;
+        int gr = m_blk + r; if (gr >= a.M) gr = a.M - 1;
+        xsrc[it] = a.X + (long)gr * a.ldx * 2 + ((p ^ (swz(r) >> 4)) << 4);
+        xoff[it] = R0 * LDS_ROW;
     }
     if constexpr (!WT) {
 #pragma unroll
         for (int it = 0; it < NIW; ++it) {
-            if constexpr (KT == 64) {
-                const int R0 = (wave * NIW + it) * 8, r = R0 + (lane >> 3), p = lane & 7;
-                int gr = n_blk + r; if (gr >= a.N) gr = a.N - 1;
-                wsrc[it] = a.W + (long)gr * a.ldw * 2 + ((p ^ (swz(r) >> 4)) << 4);
-                woff[it] = R0 * LDS_ROW;
-            } else {
-                const int R0 = (wave * NIW + it) * 16, r = R0 + (lane >> 2), p = lane & 3;
-                int gr = n_blk + r; if (gr >= a.N) gr = a.N - 1;
-                wsrc[it] = a.W + (long)gr * a.ldw * 2 + ((p ^ swz64(r)) << 4);
-                woff[it] = R0 * ROW64;
-            }
+            const int R0 = (wave * NIW + it) * 8, r = R0 + (lane >> 3), p = lane & 7;
+            int gr = n_blk + r; if (gr >= a.N) gr = a.N - 1;
+            wsrc[it] = a.W + (long)gr * a.ldw * 2 + ((p ^ (swz(r) >> 4)) << 4);
+            woff[it] = R0 * LDS_ROW;
         }
     } else {
         // waves 0-3 fill the [KT][128] image of columns n_blk .. +127, waves 4-7 that of n_blk + 128 .. +255 (4 token rows per instruction)
@@ -1467,7 +1330,6 @@ __global__ __launch_bounds__(512) void gemm_big_kernel(GemmArgs a) {
     for (int s = 0; s < nsteps; ++s) {
         const int younger = min(NS - 2, nsteps - 1 - s);
         if (younger >= NS - 2) wait_vmcnt<(NS - 2) * LPS>();
-        else if (NS >= 4 && younger == NS - 3) wait_vmcnt<(NS >= 4 ? NS - 3 : 0) * LPS>();
         else wait_vmcnt<0>();
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
@@ -1479,10 +1341,10 @@ __global__ __launch_bounds__(512) void gemm_big_kernel(GemmArgs a) {
 #pragma unroll
             for (int m = 0; m < 4; ++m) {
                 if constexpr (WT) af[m] = frag_tr256(wt + (wn0 >> 7) * KT * 256, (wn0 & 127) + 16 * m, c);
-                else af[m] = KT == 64 ? frag_sw(wt, wn0 + 16 * m, c) : frag_sw64(wt, wn0 + 16 * m);
+                else af[m] = frag_sw(wt, wn0 + 16 * m, c);
             }
 #pragma unroll
-            for (int n = 0; n < WM; ++n) bfr[n] = KT == 64 ? frag_sw(xt, wm0 + 16 * n, c) : frag_sw64(xt, wm0 + 16 * n);
+            for (int n = 0; n < WM; ++n) bfr[n] = frag_sw(xt, wm0 + 16 * n, c);
 #pragma unroll
             for (int m = 0; m < 4; ++m)
 #pragma unroll
@@ -1505,10 +1367,10 @@ __global__ __launch_bounds__(512) void gemm_big_kernel(GemmArgs a) {
 // runs on the CU while a tile drains.  Same wave tile here (128 rows x 64 columns, 32 accumulator tiles, 12 fragment reads per 32
 // MFMAs), but the workgroup is 4 waves = 128 x 256 outputs on a 3-stage ring of 32-deep steps (72 KB): two workgroups share a CU, and
 // one's store phase runs under the other's K loop.  X tile [128][64 B], W tile [256][64 B] (or two [32][128] token-major images).
-template <int NS, bool WT, bool PLAIN>
+template <bool WT, bool PLAIN>
 __global__ __launch_bounds__(256, 2) void gemm_wide_kernel(GemmArgs a) {
     using T = bf16raw;
-    constexpr int KT = 32, WM = 8, TM = 128, TN = 256;
+    constexpr int KT = 32, NS = 3, WM = 8, TM = 128, TN = 256;
     constexpr int XB = TM * ROW64, WB = WT ? 2 * KT * 256 : TN * ROW64, STAGE = XB + WB;
     constexpr int NIX = 2, NIW = 4, LPS = NIX + NIW;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1575,7 +1437,6 @@ __global__ __launch_bounds__(256, 2) void gemm_wide_kernel(GemmArgs a) {
     for (int s = 0; s < nsteps; ++s) {
         const int younger = min(NS - 2, nsteps - 1 - s);
         if (younger >= NS - 2) wait_vmcnt<(NS - 2) * LPS>();
-        else if (NS >= 4 && younger == NS - 3) wait_vmcnt<(NS >= 4 ? NS - 3 : 0) * LPS>();
         else wait_vmcnt<0>();
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
@@ -1602,48 +1463,33 @@ __global__ __launch_bounds__(256, 2) void gemm_wide_kernel(GemmArgs a) {
     }
     tile_epilogue<T, WM, PLAIN>(a, acc, m_blk, n_blk, wm0, wn0, 0);
 }
-template <int NS, bool WT, bool PLAIN>
+template <bool WT, bool PLAIN>
 int launch_wide_p(const GemmArgs& a, hipStream_t st) {
-    size_t lds = (size_t)NS * (128 * ROW64 + (WT ? 2 * 32 * 256 : 256 * ROW64));
+    size_t lds = (size_t)3 * (128 * ROW64 + (WT ? 2 * 32 * 256 : 256 * ROW64));
     if (lds < (size_t)4 * 128 * EPI_LD) lds = (size_t)4 * 128 * EPI_LD;
-    FW_SET_LDS_ONCE((gemm_wide_kernel<NS, WT, PLAIN>), lds);
-    FW_KNAME("gemm_wide_kernel<%d,%s,%s>", NS, FW_B(WT), FW_B(PLAIN));
-    hipLaunchKernelGGL((gemm_wide_kernel<NS, WT, PLAIN>), dim3(fw_cdiv(a.M, 128), fw_cdiv(a.N, 256), 1), dim3(256), lds, st, a);
+    FW_SET_LDS_ONCE((gemm_wide_kernel<WT, PLAIN>), lds);
+    FW_KNAME("gemm_wide_kernel<%s,%s>", FW_B(WT), FW_B(PLAIN));
+    hipLaunchKernelGGL((gemm_wide_kernel<WT, PLAIN>), dim3(fw_cdiv(a.M, 128), fw_cdiv(a.N, 256), 1), dim3(256), lds, st, a);
     FW_LAUNCH_RET();
 }
 
-template <int KT, int NS, bool WT, bool PLAIN>
+template <bool WT, bool PLAIN>
 int launch_big_p(const GemmArgs& a, hipStream_t st) {
-    size_t lds = (size_t)NS * (256 * (KT == 64 ? LDS_ROW : ROW64) + (WT ? 2 * KT * 256 : 256 * (KT == 64 ? LDS_ROW : ROW64)));
+    size_t lds = (size_t)2 * (256 * LDS_ROW + (WT ? 2 * 64 * 256 : 256 * LDS_ROW));
     if (lds < (size_t)8 * 128 * EPI_LD) lds = (size_t)8 * 128 * EPI_LD;       // the staged epilogue's 8 x [128][136 B] regions
-    FW_SET_LDS_ONCE((gemm_big_kernel<KT, NS, WT, PLAIN>), lds);
-    FW_KNAME("gemm_big_kernel<%d,%d,%s,%s>", KT, NS, FW_B(WT), FW_B(PLAIN));
-    hipLaunchKernelGGL((gemm_big_kernel<KT, NS, WT, PLAIN>), dim3(fw_cdiv(a.M, 256), fw_cdiv(a.N, 256), 1), dim3(512), lds, st, a);
+    FW_SET_LDS_ONCE((gemm_big_kernel<WT, PLAIN>), lds);
+    FW_KNAME("gemm_big_kernel<%s,%s>", FW_B(WT), FW_B(PLAIN));
+    hipLaunchKernelGGL((gemm_big_kernel<WT, PLAIN>), dim3(fw_cdiv(a.M, 256), fw_cdiv(a.N, 256), 1), dim3(512), lds, st, a);
     FW_LAUNCH_RET();
 }
 template <bool WT>
 int launch_big(const GemmArgs& a, hipStream_t st) {
-    // FW_GEMM_BIG: 0 off, 1 = 256 x 256, 64-deep steps / 2 stages, 2 = 32-deep / 4 stages, 3 = 32-deep / 3 stages;
-    //              4 = 128 x 256 tiles at two workgroups per CU (gemm_wide_kernel, 3 stages), 5 = the same with 4 stages (one per CU)
-    // default (mode 6): 128 x 256 tiles at two workgroups per CU, except the 65 536-wide encoder heads (N >= 16384: 1 024 tiles of
-    // 256 x 256 -- 95 us against 106 us).  Measured per shape with tools/big_gemm_bench.py (gpurun_out/bgm*.txt of round 3).
-    static const int mode_env = getenv("FW_GEMM_BIG") ? atoi(getenv("FW_GEMM_BIG")) : 6;
-    const int mode = mode_env == 6 ? (a.N >= 16384 ? 1 : 4) : mode_env;
+    // 128 x 256 tiles at two workgroups per CU, except the 65 536-wide encoder heads: 1 024 tiles of 256 x 256 -- 95 us against 106 us
+    // (measured per shape with tools/big_gemm_bench.py)
+    constexpr int BIG_MIN_N = 16384;
     const bool pl = plain_epilogue(a);
-    if (mode == 4) return pl ? launch_wide_p<3, WT, true>(a, st) : launch_wide_p<3, WT, false>(a, st);
-    if (mode == 5) return pl ? launch_wide_p<4, WT, true>(a, st) : launch_wide_p<4, WT, false>(a, st);
-    if (mode == 2) return pl ? launch_big_p<32, 4, WT, true>(a, st) : launch_big_p<32, 4, WT, false>(a, st);
-    if (mode == 3) return pl ? launch_big_p<32, 3, WT, true>(a, st) : launch_big_p<32, 3, WT, false>(a, st);
-    return pl ? launch_big_p<64, 2, WT, true>(a, st) : launch_big_p<64, 2, WT, false>(a, st);
-}
-
-template <bool XT>
-int launch_tr(const GemmArgs& a, hipStream_t st) {
-    const size_t lds = 4 * 64 * 256;
-    FW_SET_LDS_ONCE(gemm_tr_kernel<XT>, lds);
-    FW_KNAME("gemm_tr_kernel<%s>", FW_B(XT));
-    hipLaunchKernelGGL(gemm_tr_kernel<XT>, dim3(fw_cdiv(a.M, 128), fw_cdiv(a.N, 128), a.splitk), dim3(256), lds, st, a);
-    FW_LAUNCH_RET();
+    if (a.N >= BIG_MIN_N) return pl ? launch_big_p<WT, true>(a, st) : launch_big_p<WT, false>(a, st);
+    return pl ? launch_wide_p<WT, true>(a, st) : launch_wide_p<WT, false>(a, st);
 }
 
 // =====================================================================================================
@@ -1959,34 +1805,30 @@ int launch(const GemmArgs& a, hipStream_t st) {
 template <typename T, int BN>
 int dispatch_trans(const GemmArgs& a, int xt, int wt, hipStream_t st) {
     // direct global->LDS staging for k-contiguous operands whose K range is a whole number of 128-byte steps
+    // (a.kper is a multiple of the 128-byte step by construction, so a split-K slice is whole steps whenever K is)
     const int kt = 128 / TT<T>::SZ;
     const bool whole = a.K % kt == 0;
     const bool gx = !xt && whole && a.x_op == 0, gw = !wt && whole && a.w_op == 0;
     if (!xt && !wt) {
         // 64-byte K steps: for K that is not a whole number of 128-byte steps (K = 224, 672 in bf16: the round-1 tile kernel took
         // those with register staging: 28.5 -> 19.5 us at 16384 x 672 x 224).  On whole-step shapes it measured 5-10 % SLOWER than the
-        // two-stage 128-byte ring at BN = 128 (FW_GEMM_RING64=2 forces it everywhere, 0 disables it).
-        static const int ring64 = getenv("FW_GEMM_RING64") ? atoi(getenv("FW_GEMM_RING64")) : 1;
+        // two-stage 128-byte ring at BN = 128, so it is not used there.  Three 16 KB stages = 48 KB: THREE workgroups per CU (160 VGPRs
+        // allow it) -- 19.4 -> 17.3 us against four stages at two
         const int kt64 = 64 / TT<T>::SZ;
-        if (ring64 && a.x_op == 0 && a.w_op == 0 && a.K % kt64 == 0 && a.kper % kt64 == 0 && (ring64 == 2 || (!whole && BN == 128)))
-        {
-            // three 16 KB stages = 48 KB: THREE workgroups per CU (160 VGPRs allow it) -- 19.4 -> 17.3 us against four stages at two
-            static const int ns64 = getenv("FW_GEMM_RING64_NS") ? atoi(getenv("FW_GEMM_RING64_NS")) : 3;
-            if (ns64 == 4) return launch_ring64<T, BN, 4>(a, st);
-            return launch_ring64<T, BN, 3>(a, st);
+        if constexpr (BN == 128) {
+            if (a.x_op == 0 && a.w_op == 0 && a.K % kt64 == 0 && !whole) return launch_ring64<T, BN, 3>(a, st);
         }
-        static const int ring = getenv("FW_GEMM_RING") ? atoi(getenv("FW_GEMM_RING")) : 1;        // 0: gemm_kernel (one stage in flight)
-        if (gx && gw && ring && a.kper % kt == 0) {
-            // LDS per workgroup decides the residency: 2 stages of 128 x 128 = 64 KB -> 2 workgroups per CU (ring 1, default);
+        if (gx && gw) {
+            // LDS per workgroup decides the residency: 2 stages of 128 x 128 = 64 KB -> 2 workgroups per CU;
             // deeper rings of one resident workgroup measured SLOWER (tools/probe/glds_probe.hip: 28 -> 42 us)
-            if (ring == 2) return BN == 128 ? launch_ring<T, BN, 3>(a, st) : launch_ring<T, BN, 3>(a, st);
-            if (ring == 3) return BN == 128 ? launch_ring<T, BN, 4>(a, st) : launch_ring<T, BN, 4>(a, st);
             // BN = 64: 3 x 24 KB = 72 KB still leaves two workgroups per CU -- pays on long K loops (3072 x 448 x 3584: 48.6 -> 34.2 us,
             // 1024 x 896 x 7168: 88.7 -> 62.1), costs 10-20 % on 7-step ones
-            if ((ring == 1 || ring == 4) && BN == 64 && a.kper >= 28 * kt) return launch_ring<T, BN, 3>(a, st);
+            constexpr int RING3_MIN_STEPS = 28;
+            if constexpr (BN == 64) {
+                if (a.kper >= RING3_MIN_STEPS * kt) return launch_ring<T, BN, 3>(a, st);
+            }
             return launch_ring<T, BN, 2>(a, st);
         }
-        if (gx && gw) return launch<T, BN, false, false, true, true>(a, st);
         if (gx) return launch<T, BN, false, false, true, false>(a, st);
         if (gw) return launch<T, BN, false, false, false, true>(a, st);
         return launch<T, BN, false, false, false, false>(a, st);
@@ -2000,10 +1842,7 @@ int dispatch_trans(const GemmArgs& a, int xt, int wt, hipStream_t st) {
 
 // C-ABI.  Declared in include/fwair.h.
 // Which kernel the last fw_gemm call of this thread was dispatched to (measurement aid: bench.py labels its per-launch timings
-// with it so that they line up with the rocprofv3 kernel names): family * 100000 + BN * 100 + xT * 10 + wT,
-// family 0 = gemm_kernel (BN = 64 / 128), 1 = gemm_tr_kernel, 2 = gemm_stream_kernel.
-static thread_local int g_last_variant = 0;
-extern "C" int fw_gemm_last_variant(void) { return g_last_variant; }
+// with it so that they line up with the rocprofv3 kernel names)
 extern "C" int fw_gemm_last_kernel(char* buf, int n) {
     if (!buf || n <= 0) return -1;
     snprintf(buf, (size_t)n, "%s", g_last_kernel);
@@ -2087,81 +1926,51 @@ extern "C" int fw_gemm(int dtype, const void* X, long ldx, int x_trans, int x_op
     FW_CHECK_ARG(!C2 || (((uintptr_t)C2 & (4 * sz - 1)) == 0 && ldc2 % 4 == 0));
     a.kper = fw_cdiv(fw_cdiv(K, kt), splitk) * kt;
     a.alpha = alpha;
-    static const int use_staged = getenv("FW_GEMM_STAGED") ? atoi(getenv("FW_GEMM_STAGED")) : 1;
-    a.staged = use_staged ? staged_mode(a) : -1;
-    static const int dbg = getenv("FW_GEMM_BIG_DBG") ? atoi(getenv("FW_GEMM_BIG_DBG")) : 0;
+    a.staged = staged_mode(a);
+    static const int dbg = getenv("FW_GEMM_BIG_DBG") ? atoi(getenv("FW_GEMM_BIG_DBG")) : 0;      // measurement aid, see GemmArgs::dbg
     a.dbg = dbg;
     hipStream_t st = (hipStream_t)stream;
+    const bool bf16 = dtype == FW_DT_BF16, no_ops = x_op == 0 && w_op == 0;
+    const bool pl = plain_epilogue(a);
+    const long tiles128 = (long)fw_cdiv(M, 128) * fw_cdiv(N, 128) * splitk;
     // tall-skinny products stream X past a W panel held in LDS (gemm_stream_kernel)
-    static const long stream_min_m = getenv("FW_GEMM_STREAM_MIN_M") ? atol(getenv("FW_GEMM_STREAM_MIN_M")) : 32768;
-    if (!x_trans && splitk == 1 && !accumulate && x_op == 0 && w_op == 0 && !xsum && K * sz <= 512 && M >= stream_min_m) {
-        g_last_variant = 200000 + (w_trans ? 1 : 0);
-        return dtype == FW_DT_BF16 ? dispatch_stream<bf16raw>(a, w_trans, st) : dispatch_stream<float>(a, w_trans, st);
-    }
+    constexpr int STREAM_MIN_M = 32768;
+    if (!x_trans && splitk == 1 && !accumulate && no_ops && !xsum && K * sz <= 512 && M >= STREAM_MIN_M)
+        return bf16 ? dispatch_stream<bf16raw>(a, w_trans, st) : dispatch_stream<float>(a, w_trans, st);
     // compute-bound shapes on 256 x 256 tiles: at least 160 tiles (most of the 256 CUs busy in the only or last round)
-    static const int big = getenv("FW_GEMM_BIG") ? atoi(getenv("FW_GEMM_BIG")) : 6;
-    static const long big_min_tiles = getenv("FW_GEMM_BIG_MIN_TILES") ? atol(getenv("FW_GEMM_BIG_MIN_TILES")) : 160;
-    if (big && dtype == FW_DT_BF16 && !x_trans && x_op == 0 && w_op == 0 && !xsum && splitk == 1 && !accumulate && K % 64 == 0 && K >= 256 &&
-        ldx % 8 == 0 && ldw % 8 == 0 && (long)fw_cdiv(M, 256) * fw_cdiv(N, 256) >= big_min_tiles) {
-        g_last_variant = 300000 + (w_trans ? 1 : 0);
+    constexpr long BIG_MIN_TILES = 160;
+    if (bf16 && !x_trans && no_ops && !xsum && splitk == 1 && !accumulate && K % 64 == 0 && K >= 256 &&
+        ldx % 8 == 0 && ldw % 8 == 0 && (long)fw_cdiv(M, 256) * fw_cdiv(N, 256) >= BIG_MIN_TILES)
         return w_trans ? launch_big<true>(a, st) : launch_big<false>(a, st);
-    }
     // bf16 products whose W is stored [K][N] (weight gradients: X token-major too; input gradients: X k-contiguous), whole
-    // 64-deep K steps: W (and X) tiles go to LDS as they are and are read with transposing LDS reads (gemm_tr_kernel)
-    static const int use_tr = getenv("FW_GEMM_TR") ? atoi(getenv("FW_GEMM_TR")) : 3;
-    // weight gradients with N <= 64 (the C = 28 / 56 stages: 56 x 28 x 786432, ...) on the ring kernel too: its 128 x 128 tile is mostly
+    // 64-deep K steps: W (and X) tiles go to LDS as they are and are read with transposing LDS reads (gemm_tr_ring_kernel).
+    // Weight gradients with N <= 64 (the C = 28 / 56 stages: 56 x 28 x 786432, ...) take it too: the 128 x 128 tile is mostly
     // masked there, but the long reduction is what costs -- 62.3 -> 48.2, 57.3 -> 34.7, 28.2 -> 17.4 us against the 128 x 64 tile kernel
-    static const int tr_small_n = getenv("FW_GEMM_TR_SMALL_N") ? atoi(getenv("FW_GEMM_TR_SMALL_N")) : 1;
-    if (dtype == FW_DT_BF16 && w_trans && x_op == 0 && w_op == 0 && (N > 64 || (tr_small_n && x_trans && N >= 8)) && K % 64 == 0 && a.kper % 64 == 0 && ldw % 8 == 0) {
-        static const int ring = getenv("FW_GEMM_TR_RING") ? atoi(getenv("FW_GEMM_TR_RING")) : 1;     // 0: one stage in flight (gemm_tr_kernel)
-        if (x_trans && (use_tr & 1) && ldx % 8 == 0) {
-            g_last_variant = 100011;
-            // three 16 KB stages and a 3-waves-per-SIMD register budget (141 VGPRs, no spills): THREE workgroups per CU.  265.6 -> 266.9
-            // images/s against four stages at two workgroups (ring == 6 keeps that form); 155 -> 138 us at 65536 x 448 x 1024
-            if (ring == 1) return launch_tr_ring<true, 32, 3>(a, st);
-            if (ring == 6) return launch_tr_ring<true, 32, 4>(a, st);
-            if (ring == 5) return launch_tr_ring<true, 64, 2>(a, st);
-            if (ring == 2) return launch_tr_ring<true, 64, 3>(a, st);
-            if (ring == 3) return launch_tr_ring<true, 64, 4>(a, st);
-            if (ring == 4) return launch_tr_ring<true, 32, 5>(a, st);
-            return launch_tr<true>(a, st);
-        }
-        static const long tr_min_tiles = getenv("FW_GEMM_TR_MIN_TILES") ? atol(getenv("FW_GEMM_TR_MIN_TILES")) : 200;   // 200..383 tiles: 77 -> 47 us at 4096 x 896 x 3584; below 200 the old kernel's 128 x 64 tiles fill more CUs
-        if (!x_trans && (use_tr & 2) && !xsum && (long)fw_cdiv(M, 128) * fw_cdiv(N, 128) * splitk >= tr_min_tiles) {
-            g_last_variant = 100001;
-            // plain store and MORE blocks than CUs: the 32-deep form (48 KB, 126 VGPRs: three workgroups per CU) -- co-residency pays
-            // once a CU has more than one block to run (16384 x 448 x 1792: 53.1 -> 45.1 us, 512 blocks); with at most one block per
-            // CU the 64-deep three-stage ring stays ahead (4096 x 896 x 3584: 49.3 vs 54.4 us, 224 blocks).  0: never, 2: always
-            static const int dx32 = getenv("FW_GEMM_TR_DX32") ? atoi(getenv("FW_GEMM_TR_DX32")) : 1;
-            if (dx32 && plain_epilogue(a) && (dx32 == 2 || (long)fw_cdiv(M, 128) * fw_cdiv(N, 128) * splitk > 256))
-                return launch_tr_ring<false, 32, 3>(a, st);
-            if (ring == 5) return launch_tr_ring<false, 64, 2>(a, st);
-            // 3 stages = 96 KB = ONE workgroup per CU: fastest while the epilogue is a plain store.  An epilogue with an operand of its
-            // own (GELU' input) keeps the CU's only 4 waves off the MFMAs for as long as the K loop took; 2 stages = 64 KB lets a
-            // second workgroup's K loop run under it: 135 -> 105 us at 16384 x 1792 x 448, 101 -> 71 us at 4096 x 3584 x 896.
-            static const int np2 = getenv("FW_GEMM_TR_NP2") ? atoi(getenv("FW_GEMM_TR_NP2")) : 1;
-            if (ring == 1 && np2 && !plain_epilogue(a)) return launch_tr_ring<false, 64, 2>(a, st);
-            if (ring == 2 || ring == 1) return launch_tr_ring<false, 64, 3>(a, st);
-            if (ring == 3 || ring == 4) return launch_tr_ring<false, 64, 4>(a, st);
-            return launch_tr<false>(a, st);
-        }
+    const bool tr = bf16 && w_trans && no_ops && (N > 64 || (x_trans && N >= 8)) && K % 64 == 0 && a.kper % 64 == 0 && ldw % 8 == 0;
+    // weight gradients: three 16 KB stages and a 3-waves-per-SIMD register budget (141 VGPRs, no spills): THREE workgroups per CU.
+    // 265.6 -> 266.9 images/s against four stages at two workgroups; 155 -> 138 us at 65536 x 448 x 1024
+    if (tr && x_trans && ldx % 8 == 0) return launch_tr_ring<true, 32, 3>(a, st);
+    // input gradients: 200..383 tiles: 77 -> 47 us at 4096 x 896 x 3584; below 200 the tile kernel's 128 x 64 tiles fill more CUs
+    constexpr long TR_MIN_TILES = 200;
+    if (tr && !x_trans && !xsum && tiles128 >= TR_MIN_TILES) {
+        // plain store and MORE blocks than CUs: the 32-deep form (48 KB, 126 VGPRs: three workgroups per CU) -- co-residency pays
+        // once a CU has more than one block to run (16384 x 448 x 1792: 53.1 -> 45.1 us, 512 blocks); with at most one block per
+        // CU the 64-deep three-stage ring stays ahead (4096 x 896 x 3584: 49.3 vs 54.4 us, 224 blocks)
+        if (pl && tiles128 > 256) return launch_tr_ring<false, 32, 3>(a, st);
+        // 3 stages = 96 KB = ONE workgroup per CU: fastest while the epilogue is a plain store.  An epilogue with an operand of its
+        // own (GELU' input) keeps the CU's only 4 waves off the MFMAs for as long as the K loop took; 2 stages = 64 KB lets a
+        // second workgroup's K loop run under it: 135 -> 105 us at 16384 x 1792 x 448, 101 -> 71 us at 4096 x 3584 x 896.
+        return pl ? launch_tr_ring<false, 64, 3>(a, st) : launch_tr_ring<false, 64, 2>(a, st);
     }
-    // the same input-gradient product with K a multiple of 32 only (K = 224, 336 is not): 32-deep steps, X in 64-byte rows
-    if (dtype == FW_DT_BF16 && w_trans && !x_trans && x_op == 0 && w_op == 0 && N > 64 && K % 64 != 0 && K % 32 == 0 && ldw % 8 == 0 && !xsum
-        && splitk == 1 && (long)fw_cdiv(M, 128) * fw_cdiv(N, 128) >= 200) {
-        static const int r32 = getenv("FW_GEMM_TR_K32") ? atoi(getenv("FW_GEMM_TR_K32")) : 2;     // 1: plain epilogues only
-        if (r32 && (r32 == 2 || plain_epilogue(a))) {          // with the lean GELU' epilogue: 44.4 -> 34.2 us at 16384 x 896 x 224 against the round-1 tile kernel
-            g_last_variant = 100001;
-            return launch_tr_ring<false, 32, 3>(a, st);
-        }
-    }
+    // the same input-gradient product with K a multiple of 32 only (K = 224, 336 is not): 32-deep steps, X in 64-byte rows.
+    // With the lean GELU' epilogue: 44.4 -> 34.2 us at 16384 x 896 x 224 against the round-1 tile kernel
+    constexpr long TR_K32_MIN_TILES = 200;
+    if (bf16 && w_trans && !x_trans && no_ops && N > 64 && K % 64 != 0 && K % 32 == 0 && ldw % 8 == 0 && !xsum
+        && splitk == 1 && tiles128 >= TR_K32_MIN_TILES)
+        return launch_tr_ring<false, 32, 3>(a, st);
     // 128x64 tiles when N is narrow or when 128x128 tiles would leave most of the 256 CUs (2 blocks each) idle
-    const bool small_n = N <= 64 || (long)fw_cdiv(M, 128) * fw_cdiv(N, 128) * splitk < 384;
-    g_last_variant = (small_n ? 64 : 128) * 100 + (x_trans ? 10 : 0) + (w_trans ? 1 : 0);
-    if (dtype == FW_DT_BF16) {
-        return small_n ? dispatch_trans<bf16raw, 64>(a, x_trans, w_trans, st)
-                       : dispatch_trans<bf16raw, 128>(a, x_trans, w_trans, st);
-    }
-    return small_n ? dispatch_trans<float, 64>(a, x_trans, w_trans, st)
-                   : dispatch_trans<float, 128>(a, x_trans, w_trans, st);
+    constexpr long BN128_MIN_TILES = 384;
+    const bool small_n = N <= 64 || tiles128 < BN128_MIN_TILES;
+    if (bf16) return small_n ? dispatch_trans<bf16raw, 64>(a, x_trans, w_trans, st) : dispatch_trans<bf16raw, 128>(a, x_trans, w_trans, st);
+    return small_n ? dispatch_trans<float, 64>(a, x_trans, w_trans, st) : dispatch_trans<float, 128>(a, x_trans, w_trans, st);
 }

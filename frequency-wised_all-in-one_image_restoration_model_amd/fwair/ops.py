@@ -45,7 +45,7 @@ _DGRAD_SPLIT_ROWS = int(_os.environ.get('FW_DGRAD_SPLIT_ROWS', '512'))   # reduc
 
 def pick_splitk(M, N, K, dtype):
     """Split factor of a weight-gradient GEMM (small M x N output, long reduction K = tokens).  Rule fitted to sweeps on MI355X
-    (tools/splitk_sweep.py, tools/wgrad_probe.py): as many blocks as fit ONE round of the chip (256 CUs x 2 workgroups = 512) and
+    (split-factor sweeps of round 2): as many blocks as fit ONE round of the chip (256 CUs x 2 workgroups = 512) and
     never more -- 528 blocks ran 77 us where 440 ran 56 (a second round for 16 stragglers) --, with at least 512 reduction rows
     (8 K-steps) per block.  (fw_gemm deals contiguous shares of the tile order to the 8 XCDs for ANY block count.)"""
     tiles = ((M + 127) // 128) * ((N + 63) // 64 if N <= 64 else (N + 127) // 128)

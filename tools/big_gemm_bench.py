@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""A/B of the compute-bound GEMM shapes of the B = 16 step: FW_GEMM_BIG=0 (128 x 128 rings) vs 1 / 2 / 3 (256 x 256 tiles, 8 waves).
-Each shape is timed as 8 launches on 8 separate operand sets inside a captured graph (cold L2 / MALL like in the step)."""
+"""Times the compute-bound GEMM shapes of the B = 16 step (gemm_wide_kernel / gemm_big_kernel; FW_GEMM_BIG_DBG=1 / 2 / 3 in the
+environment skips their stores / operand loads / both: measurement only, wrong results).  Each shape is timed as 8 launches on 8 separate operand sets inside a captured graph (cold L2 / MALL like in the step)."""
 import os
 import sys
 
@@ -55,7 +55,7 @@ def run(M, N, K, kind, reps=8):
 
 
 if __name__ == '__main__':
-    print('FW_GEMM_BIG =', os.environ.get('FW_GEMM_BIG', '(default 1)'))
+    print('FW_GEMM_BIG_DBG =', os.environ.get('FW_GEMM_BIG_DBG', '(unset)'))
     tot = 0.0
     for M, N, K, kind in SHAPES:
         t = run(M, N, K, kind)
