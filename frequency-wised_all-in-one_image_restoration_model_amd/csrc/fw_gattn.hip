@@ -21,6 +21,8 @@
 // Backward (flash style, deterministic, no atomics on activations): workgroup (image, head, tile t) first acts for QUERY tile t
 // (loops over the key tiles: dQ), then for KEY tile t (loops over the query tiles: dK, dV), recomputing P from the saved
 // log-sum-exp; with NT = 1 both roles share one pass.
+// Any other N = 64 nt up to 1024 (N = 576 at 384x384, 1024 at 512x512; plain attention + Dropout, no lamb): gattn_stream_fwd_kernel
+// walks the key tiles with an online softmax, and the backward body runs with a run-time tile count (NT = 0).
 #include "fw_common.h"
 
 namespace {
@@ -326,6 +328,134 @@ __global__ __launch_bounds__(NTH) void gattn_probs_kernel(GAttnArgs a) { gattn_f
 template <typename T>
 __global__ __launch_bounds__(NTH) void gattn_apply_kernel(GAttnArgs a) { gattn_fwd_body<T, 4, false, V_APPLY>(a); }
 
+// ---- streaming forward: any N = 64 * nt, plain attention + Dropout (no lamb) ---------------------------------------------------
+// Same grid and ownership as above (one workgroup per (image, head, 64 queries), a lane owns the query 16 w + (l & 15)), but the
+// keys pass by in 64-row tiles and the softmax is the online one: per query a running maximum m and a running sum l of
+// e_j = exp(s_j - m); when a tile raises m, l AND the four O^T accumulators take the same factor exp(m_old - m_new) before the
+// tile's e_j (exponentiated against m_new only) enter either.  l sums every e_j, dropped or not; Dropout scales the e_j that go
+// into P V.  After the last tile O /= l and lse = m + log(l): what the register kernel stores, so the backward pass is shared.
+// K / V of tile t + 1 are requested into registers before tile t is computed and written to the other LDS buffer after it (one
+// barrier per tile); the last tile, peeled off the loop, requests nothing.
+// LDS: Q, 2 K tiles, 2 V tiles, the four waves' P strips = 6 * GG<T>::TILE: 55 296 B in bf16 (two workgroups per CU), 104 448 B in
+// f32 (one per CU); O leaves through the Q rows of the own strip.
+typedef unsigned __attribute__((ext_vector_type(4))) u32x4;            // native vector: the in-flight tile stays in registers
+template <typename T> struct StageRegs { u32x4 k[64 * GG<T>::GR / NTH], v[64 * GG<T>::GR / NTH]; };
+template <typename T> FW_DEV void stage_request(StageRegs<T>& s, const char* gk, const char* gv, long ldb) {
+    constexpr int GR = GG<T>::GR;
+#pragma unroll
+    for (int i = 0; i < 64 * GR / NTH; ++i) {
+        const int idx = threadIdx.x + i * NTH, r = idx / GR, c = idx % GR;
+        s.k[i] = *reinterpret_cast<const u32x4*>(gk + r * ldb + c * 16);
+        s.v[i] = *reinterpret_cast<const u32x4*>(gv + r * ldb + c * 16);
+    }
+}
+template <typename T> FW_DEV void stage_write(const StageRegs<T>& s, char* Kt, char* Vt) {
+    constexpr int GR = GG<T>::GR, LDR = GG<T>::LDR;
+#pragma unroll
+    for (int i = 0; i < 64 * GR / NTH; ++i) {
+        const int idx = threadIdx.x + i * NTH, r = idx / GR, c = idx % GR;
+        *reinterpret_cast<u32x4*>(Kt + r * LDR + c * 16) = s.k[i];
+        *reinterpret_cast<u32x4*>(Vt + r * LDR + c * 16) = s.v[i];
+    }
+}
+// one key tile of the online softmax: the lane's (m, l) and O^T accumulators take tile t from the LDS tiles Ks / Vs
+template <typename T>
+FW_DEV void stream_tile(const GAttnArgs& a, const char* Ks, const char* Vs, char* Ps, const uint4 (&qf)[GG<T>::KC], unsigned key,
+                        unsigned long long base, float& m, float& lsum, f32x4 (&o)[4]) {
+    constexpr int LDR = GG<T>::LDR, KC = GG<T>::KC;
+    // S^T tile: s[mt][r] = score(query 16 w + (l & 15), key 64 t + 16 mt + 4 (l >> 4) + r)
+    f32x4 s[4];
+    float mx = -3.0e38f;
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt) {
+        s[mt] = zero4();
+#pragma unroll
+        for (int c = 0; c < KC; ++c) mma_chunk<T>(s[mt], frag_kc(Ks, LDR, 16 * mt, c), qf[c]);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) { s[mt][r] *= a.scale; mx = fmaxf(mx, s[mt][r]); }
+    }
+    const float mn = fmaxf(m, col_max(mx));
+    const float alpha = __expf(m - mn);                                // 0 at the first tile (l = 0, O = 0), 1 when m stays
+    m = mn;
+    float sum = 0.f;
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) { s[mt][r] = __expf(s[mt][r] - mn); sum += s[mt][r]; }
+    lsum = lsum * alpha + col_sum(sum);                                // l and O take the same factor; every e_j enters l
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) o[dt] *= alpha;
+    if (a.thresh) {
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) s[mt][r] = fw_keep(key, base + 16 * mt + r, a.thresh) ? s[mt][r] * a.inv_keep : 0.f;
+    }
+#pragma unroll
+    for (int mt = 0; mt < 4; ++mt) store_acc_T<T>(Ps, LDR, 16 * mt, 0, s[mt]);
+    wave_fence();
+    // O^T[d][i] += sum_j V[j][d] e[i][j]
+#pragma unroll
+    for (int c = 0; c < KC; ++c) {
+        const uint4 pf = frag_kc(Ps, LDR, 0, c);
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt) mma_chunk<T>(o[dt], frag_km<T>(Vs, LDR, 16 * dt, c), pf);
+    }
+}
+template <typename T>
+__global__ __launch_bounds__(NTH) void gattn_stream_fwd_kernel(GAttnArgs a) {
+    using G = GG<T>;
+    constexpr int SZ = G::SZ, LDR = G::LDR, KC = G::KC, TILE = G::TILE;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    char* Qs = smem;
+    char* Kb = Qs + TILE;                                              // K tiles 0 / 1
+    char* Vb = Kb + 2 * TILE;                                          // V tiles 0 / 1
+    char* Ps = Vb + 2 * TILE + wave_id() * 16 * LDR;                   // the wave's [16 queries][64 keys] of T
+    const int w = wave_id(), l = lane_id();
+    const int N = a.N, nt = N >> 6;
+    int item = blockIdx.x;
+    const int qt = item % nt; item /= nt;
+    const int h = item % a.heads, b = item / a.heads;
+    const long ldb = a.ld * SZ;
+    const char* gk = a.k + ((long)b * N * a.ld + h * 64) * SZ;
+    const char* gv = a.v + ((long)b * N * a.ld + h * 64) * SZ;
+    load_tile<T, 64>(Qs, a.q + (((long)b * N + qt * 64) * a.ld + h * 64) * SZ, ldb);
+    load_tile<T, 64>(Kb, gk, ldb);
+    load_tile<T, 64>(Vb, gv, ldb);
+    __syncthreads();
+    uint4 qf[KC];
+#pragma unroll
+    for (int c = 0; c < KC; ++c) qf[c] = frag_kc(Qs, LDR, 16 * w, c);
+    const int iq = qt * 64 + 16 * w + (l & 15);                        // the lane's query
+    // flat index of (b, h, iq, key 4 (l >> 4)) in the [B][heads][N][N] map: what the backward derives (pair_grads)
+    const unsigned long long row = (unsigned long long)((long)(b * a.heads + h) * N + iq) * (unsigned long long)N + 4 * (l >> 4);
+    const unsigned key = a.thresh ? fw_site_key(a.seed[0], a.site) : 0u;
+    float m = -3.0e38f, lsum = 0.f;
+    f32x4 o[4];
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) o[dt] = zero4();
+    for (int t = 0; t + 1 < nt; ++t) {                                 // every tile but the last: tile t + 1 is in flight under tile t
+        StageRegs<T> nx;
+        stage_request<T>(nx, gk + (long)(t + 1) * 64 * ldb, gv + (long)(t + 1) * 64 * ldb, ldb);
+        stream_tile<T>(a, Kb + (t & 1) * TILE, Vb + (t & 1) * TILE, Ps, qf, key, row + (unsigned long long)t * 64, m, lsum, o);
+        stage_write<T>(nx, Kb + ((t + 1) & 1) * TILE, Vb + ((t + 1) & 1) * TILE);               // last read before the previous barrier
+        __syncthreads();
+    }
+    {   // the last tile requests nothing
+        const int t = nt - 1;
+        stream_tile<T>(a, Kb + (t & 1) * TILE, Vb + (t & 1) * TILE, Ps, qf, key, row + (unsigned long long)t * 64, m, lsum, o);
+    }
+    const float inv = 1.0f / lsum;
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) o[dt] *= inv;
+    if ((l >> 4) == 0) a.lse[(long)(b * a.heads + h) * N + iq] = m + __logf(lsum);
+    char* Os = Qs + 16 * w * LDR;                                      // rows of Q only this wave ever read (qf is in registers)
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) store_acc_T<T>(Os, LDR, 16 * dt, 0, o[dt]);
+    wave_fence();
+    store_rows16<T>(Os, a.out + (((long)b * N + qt * 64 + 16 * w) * a.ldo + h * 64) * SZ, a.ldo * SZ);
+}
+
 // ================================================================================================================ backward
 // dvec[b][h][i] = sum_d dO[i][d] O[i][d]
 template <typename T>
@@ -362,7 +492,8 @@ FW_DEV void pair_grads(const GAttnArgs& a, int b, int h, int qi, int kj, const c
                        char* arena, f32x4 (&p2)[4], f32x4 (&ds)[4]) {
     constexpr bool DC = VAR == V_DC, MAPS = VAR == V_MAPS;
     using G = GG<T>;
-    constexpr int LDR = G::LDR, KC = G::KC, N = 64 * NT;
+    constexpr int LDR = G::LDR, KC = G::KC;
+    const int N = NT ? 64 * NT : a.N;                                 // NT = 0: the tile count is a run-time value (streaming sizes)
     const int w = wave_id(), l = lane_id();
     const int iq = qi * 64 + 16 * w + (l & 15);
     const long rowid = (long)(b * a.heads + h) * N + iq;
@@ -459,7 +590,8 @@ FW_DEV void pair_grads(const GAttnArgs& a, int b, int h, int qi, int kj, const c
 template <typename T, int NT, bool LAMB, int DC>                        // DC: V_NONE | V_DC | V_MAPS, handed to pair_grads
 FW_DEV void gattn_bwd_body(const GAttnArgs& a) {
     using G = GG<T>;
-    constexpr int SZ = G::SZ, LDR = G::LDR, KC = G::KC, N = 64 * NT, TILE = G::TILE;
+    constexpr int SZ = G::SZ, LDR = G::LDR, KC = G::KC, TILE = G::TILE;
+    const int nt = NT ? NT : a.N >> 6, N = 64 * nt;                    // NT = 0: run-time tile count, every N = 64 nt without lamb
     static_assert(!LAMB || NT == 1, "the 64x64 transform is defined for N = 64 only");
     static_assert(DC == V_NONE || (NT == 4 && !LAMB), "the N x N band grid has kernels at N = 256 only");
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -472,7 +604,7 @@ FW_DEV void gattn_bwd_body(const GAttnArgs& a) {
     char* dSs = LAMB ? arena + SLOT : Ps + TILE;
     const int w = wave_id();
     int item = blockIdx.x;
-    const int t = item % NT; item /= NT;
+    const int t = item % nt; item /= nt;
     const int h = item % a.heads, b = item / a.heads;
     const long ldb = a.ld * SZ, lddob = a.lddo * SZ, lddb = a.ldd * SZ;
     const long col = (long)h * 64 * SZ;
@@ -484,7 +616,7 @@ FW_DEV void gattn_bwd_body(const GAttnArgs& a) {
     // ---- role Q: queries of tile t against every key tile (NT == 1: the one pair also feeds dK / dV)
     load_tile<T, 64>(Qs, rows(a.q, ldb, t), ldb);
     load_tile<T, 64>(dOs, rows(a.dout, lddob, t), lddob);
-    for (int kj = 0; kj < NT; ++kj) {
+    for (int kj = 0; kj < nt; ++kj) {
         load_tile<T, 64>(Ks, rows(a.k, ldb, kj), ldb);
         load_tile<T, 64>(Vs, rows(a.v, ldb, kj), ldb);
         __syncthreads();
@@ -538,12 +670,12 @@ FW_DEV void gattn_bwd_body(const GAttnArgs& a) {
             store_rows16<T>(Vs + 16 * w * LDR, const_cast<char*>(rows(a.dv, lddb, t)) + (long)16 * w * lddb, lddb);
         }
     }
-    if constexpr (NT > 1) {
+    if constexpr (NT != 1) {
         // ---- role K: keys of tile t against every query tile
         __syncthreads();
         load_tile<T, 64>(Ks, rows(a.k, ldb, t), ldb);
         load_tile<T, 64>(Vs, rows(a.v, ldb, t), ldb);
-        for (int qi = 0; qi < NT; ++qi) {
+        for (int qi = 0; qi < nt; ++qi) {
             load_tile<T, 64>(Qs, rows(a.q, ldb, qi), ldb);
             load_tile<T, 64>(dOs, rows(a.dout, lddob, qi), lddob);
             __syncthreads();
@@ -670,6 +802,21 @@ template <typename T, int NT, bool LAMB> static void launch_bwd(const GAttnArgs&
     const size_t lds = bwd_lds<T>(LAMB);
     FW_SET_LDS_ONCE((gattn_bwd_kernel<T, NT, LAMB>), lds);
     hipLaunchKernelGGL((gattn_bwd_kernel<T, NT, LAMB>), dim3(a.B * a.heads * NT), dim3(NTH), lds, st, a);
+}
+// N = 64 nt, 128 <= N <= 1024, N != 256: the streaming forward, and the backward body with a run-time tile count (NT = 0)
+template <typename T> static void launch_stream(const GAttnArgs& a, bool bwd, hipStream_t st) {
+    const int nt = a.N / 64;
+    if (!bwd) {
+        const size_t lds = (size_t)6 * GG<T>::TILE;
+        FW_SET_LDS_ONCE((gattn_stream_fwd_kernel<T>), lds);
+        hipLaunchKernelGGL((gattn_stream_fwd_kernel<T>), dim3(a.B * a.heads * nt), dim3(NTH), lds, st, a);
+        return;
+    }
+    const long n = (long)a.B * a.N * a.heads;
+    hipLaunchKernelGGL((gattn_dvec_kernel<T>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a);
+    const size_t lds = bwd_lds<T>(false);
+    FW_SET_LDS_ONCE((gattn_bwd_kernel<T, 0, false>), lds);
+    hipLaunchKernelGGL((gattn_bwd_kernel<T, 0, false>), dim3(a.B * a.heads * nt), dim3(NTH), lds, st, a);
 }
 // 'DC' at N = 256: the flash-form kernels with the affine re-weighting, no tables and no scratch
 template <typename T> static void launch_dc_fwd(const GAttnArgs& a, hipStream_t st) {
@@ -943,6 +1090,8 @@ template <typename T> static int dispatch(const GAttnArgs& a, bool bwd, hipStrea
     if (a.N == 64) {
         if (lamb) bwd ? launch_bwd<T, 1, true>(a, st) : launch_fwd<T, 1, true>(a, st);
         else bwd ? launch_bwd<T, 1, false>(a, st) : launch_fwd<T, 1, false>(a, st);
+    } else if (a.N != 256) {
+        launch_stream<T>(a, bwd, st);                                  // common_ok: no lamb here
     } else if (lamb) {
         bwd ? launch_dc_bwd<T>(a, st) : launch_dc_fwd<T>(a, st);
     } else {
@@ -951,9 +1100,11 @@ template <typename T> static int dispatch(const GAttnArgs& a, bool bwd, hipStrea
     FW_LAUNCH_RET();
 }
 // lamb: N = 64 with the 64x64 tables (any nb), or N = 256 in the 'DC' form (nb = 2, band 0 = bin (0, 0): no tables); nothing else has a kernel
+// N: 64 and 256 (register kernels), or any other multiple of 64 in [128, 1024] without lamb (streaming forward)
 static bool common_ok(const GAttnArgs& a, int dtype) {
     const int sz = dtype == FW_DT_BF16 ? 2 : 4;
-    if (!(a.q && a.k && a.v && a.lse && a.B > 0 && a.heads > 0 && (a.N == 64 || a.N == 256))) return false;
+    const bool stream_n = a.N % 64 == 0 && a.N >= 128 && a.N <= 1024 && !a.lamb;
+    if (!(a.q && a.k && a.v && a.lse && a.B > 0 && a.heads > 0 && (a.N == 64 || a.N == 256 || stream_n))) return false;
     if ((a.ld * sz) % 16 || ((uintptr_t)a.q | (uintptr_t)a.k | (uintptr_t)a.v) % 16) return false;
     if (a.thresh && !a.seed) return false;
     if (a.lamb) {

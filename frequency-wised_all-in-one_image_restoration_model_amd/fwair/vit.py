@@ -4,7 +4,8 @@ kernels: same class / attribute names (`to_patch_embedding`, `pos_embedding`, `t
 `vit_uformer`, dumped from the reference).
 
 Token stream: f32 [B*N, 768] (the residual stream, as in the Uformer blocks); GEMM / attention operands T.  N = (S/16)^2 tokens per
-image attend globally (csrc/fw_gattn.hip): N = 64 at 128x128, N = 256 at 256x256 (BASELINE configs[4]).  The image side follows
+image attend globally (csrc/fw_gattn.hip): N = 64 at 128x128, N = 256 at 256x256 (BASELINE configs[4]) with the score block in
+registers, N = 576 at 384x384 and N = 1024 at 512x512 through the streaming (online-softmax) forward.  The image side follows
 `opt.patch_size` like the Uformer classes (the reference's seam passes only `opt` and so always builds for 128, net/model.py:31).
 
 Train mode applies every nn.Dropout of the reference (p = 0.1: embedding, attention map, to_out, FeedForward hidden and output;
@@ -17,6 +18,7 @@ the attention kernel (64x64 2-D DFT on the f32 MFMA).  Like the reference it nee
 are dim_head x dim_head, :56,60); at any other size both raise.  `opt.vit_band_grid = 'tokens'` sizes the masks by the attention
 map instead (N x N; identical at N = 64): at N = 256 'DC' then runs as an affine map of the softmax (csrc/fw_gattn.hip dc_coef)
 and '<n>_bands' as a multi-pass 256x256 2-D DFT on the f32 MFMA between a probabilities and an apply kernel (fw_gattn_bands_fwd / bwd).
+At N = 576 / 1024 the attention is plain softmax + Dropout: a band re-weighting there has no kernel and raises.
 """
 import math
 import zlib
@@ -287,6 +289,9 @@ class Transformer(nn.Module):
                 if N != 64 and self.band_grid != 'tokens':
                     raise NotImplementedError('the band re-weighting needs N = dim_head = 64 tokens (128x128 inputs): the reference sizes '
                                               'its masks dim_head x dim_head (encoder_ViT.py:56,60) and fails otherwise too')
+                if N not in (64, 256):
+                    raise NotImplementedError(f'the band re-weighting has kernels at N = 64 and N = 256 tokens only, not N = {N}: the streaming '
+                                              'attention of the larger inputs is plain softmax + Dropout (frequency_decompose_type none)')
                 if a.lamb.shape[1] not in (1, B):
                     raise NotImplementedError(f'batch-wise lamb was built for batch {a.lamb.shape[1]}, got {B}')
                 # N = 256 'DC': band 0 is the mean of the map, 1 / N for softmax rows -- an affine map, no tables (csrc/fw_gattn.hip dc_coef)
@@ -320,8 +325,9 @@ class ViTEncoder(nn.Module):
         dim_head = dim // heads
         if image_size is None:                                           # the seam passes only `opt` (net/model.py:31): follow --patch_size
             image_size = int(getattr(opt, 'patch_size', None) or 128)
-        if image_size not in (128, 256):
-            raise NotImplementedError(f'ViTEncoder: image_size {image_size}: the global-attention kernel holds N = (S/16)^2 in {{64, 256}} keys per head')
+        if image_size not in (128, 256, 384, 512):
+            raise NotImplementedError(f'ViTEncoder: image_size {image_size}: the accepted sides are 128, 256, 384 and 512 '
+                                      '(N = (S/16)^2 = 64, 256, 576, 1024 keys per head in the global-attention kernels)')
         self.image_height = self.image_width = image_size
         self.patch = patch_size
         num_patches = (image_size // patch_size) ** 2

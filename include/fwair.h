@@ -263,21 +263,24 @@ int fw_small_linear_bwd(const float* dy, const float* y, const float* x, const f
                         int K, float slope, void* stream);
 
 /* ---- ViT global attention (net/encoder_ViT.py:76-98 `Attention.forward`; BASELINE configs[4]: N = 256 tokens at 256x256) -----
- * q | k | v: T [B*N][ld], head h at column h * 64 (head_dim 64); N in {64, 256}.  out: T [B*N][heads*64]; lse: f32 [B][heads][N].
+ * q | k | v: T [B*N][ld], head h at column h * 64 (head_dim 64); N in {64, 256}, or -- with lamb = NULL -- any other multiple of
+ * 64 from 128 to 1024 (576 at 384x384, 1024 at 512x512).  out: T [B*N][heads*64]; lse: f32 [B][heads][N].
  * attn = softmax(q k^T scale) [+ sum_i lamb[i] band_i(attn)] -> dropout(p) -> attn v, one workgroup per (image, head, 64 queries),
- * the 64 x N score block in registers.  Dropout (encoder_ViT.py:67,94): counter-based mask of (seed[0], site, flat index of the
+ * the 64 x N score block in registers at N in {64, 256}; at the other N the key tiles stream past with an online softmax (same lse,
+ * same mask indices, plain attention + Dropout only).  Dropout (encoder_ViT.py:67,94): counter-based mask of (seed[0], site, flat index of the
  * [B][heads][N][N] map), re-derived by the backward pass; drop_p = 0 or eval: off.  lamb (optional, N = 64 only -- the reference's
  * masks are dim_head x dim_head, encoder_ViT.py:56,60): f32 [nb][lamb_batch (1 | B)][heads] of encoder_ViT.py:62-66,85-92, evaluated
  * as a 64x64 2-D DFT on the f32 MFMA; bandidx: u8 [64][64] band of every un-shifted spectrum bin; panels: f32 cos[64][64], sin[64][64].
  * N = 256 with lamb: only the 'DC' decomposition on the N x N grid (encoder_ViT.py:59-60 'frequency_decompose_dc' with masks sized
  * by the map): nb = 2, bandidx = panels = NULL; band 0 is the mean of the map, 1 / N for softmax rows, so the kernel evaluates
  * attn' = (1 + lamb[1]) attn + (lamb[0] - lamb[1]) / N without a transform; `<n>_bands` at N = 256 is fw_gattn_bands_fwd / bwd, which
- * require the tables.  Every other lamb / N combination is an argument error. */
+ * require the tables.  Every other lamb / N combination (any lamb at N not in {64, 256} included) and every other N is an argument
+ * error. */
 int fw_gattn_fwd(int dtype, const void* q, const void* k, const void* v, long ld, void* out, long ldo, float* lse, int B, int heads, int N,
                  float scale, const void* seed, int site, float drop_p, const float* lamb, int nb, int lamb_batch, const void* bandidx,
                  const float* panels, void* stream);
-/* dq, dk, dv: T, same layout as q / k / v (row stride ldd); dvec: f32 [B][heads][N] scratch (rowsum(dO . O); unused with lamb at
- * N = 64, required with lamb at N = 256, where it receives rowsum(P . dP));
+/* Same domain as fw_gattn_fwd.  dq, dk, dv: T, same layout as q / k / v (row stride ldd); dvec: f32 [B][heads][N] scratch
+ * (rowsum(dO . O); unused with lamb at N = 64, required with lamb at N = 256, where it receives rowsum(P . dP));
  * dlamb: accumulated (atomics), same layout as lamb. */
 int fw_gattn_bwd(int dtype, const void* q, const void* k, const void* v, long ld, const void* o, long ldo, const void* dout, long lddo,
                  const float* lse, float* dvec, void* dq, void* dk, void* dv, long ldd, int B, int heads, int N, float scale,
