@@ -1581,12 +1581,12 @@ extern "C" int fw_adam(int shadow_dtype, float* p, const float* g, float* m, flo
                        float b1, float b2, float eps, void* stream) {
     FW_CHECK_ARG(p && g && m && v && hyper && n > 0);
     if (shadow_dtype == FW_DT_BF16 && shadow) LAUNCH((adam_kernel<bf16raw>), n, p, g, m, v, (bf16raw*)shadow, n, hyper, b1, b2, eps);
-    LAUNCH((adam_kernel<float>), n, p, g, m, v, (float*)nullptr, n, hyper, b1, b2, eps);
+    LAUNCH((adam_kernel<float>), n, p, g, m, v, (float*)shadow, n, hyper, b1, b2, eps);      // f32 shadow (or none)
 }
 extern "C" int fw_ema(int shadow_dtype, float* pk, const float* pq, void* shadow, long n, float momentum, void* stream) {
     FW_CHECK_ARG(pk && pq && n > 0);
     if (shadow_dtype == FW_DT_BF16 && shadow) LAUNCH((ema_kernel<bf16raw>), n, pk, pq, (bf16raw*)shadow, n, momentum);
-    LAUNCH((ema_kernel<float>), n, pk, pq, (float*)nullptr, n, momentum);
+    LAUNCH((ema_kernel<float>), n, pk, pq, (float*)shadow, n, momentum);                     // f32 shadow (or none)
 }
 extern "C" int fw_lrelu_fwd(int dtype, const float* x, void* y, long n, float slope, void* stream) {
     FW_CHECK_ARG(x && y && n > 0);

@@ -266,3 +266,194 @@ def check_gemm(ref, dtype, outputs, what, min_rejected=GEMM_MIN_REJECTED, **epi)
                                                    f'the sum on (asked: {GEMM_MIN_SELECTED}); the missing-term check would cover too few')
             assert share >= min_rejected, (f'{what} [{key}]: the bound tells the output from a reference without the k = {k0} term at '
                                            f'{share:.4f} of the {selected:.4f} of the elements it is asked at (asked: {min_rejected})')
+
+
+# ------------------------------------------------------------------------------------------------ per-step kernels (csrc/fw_elem.hip)
+# Guarded buffers: every output is allocated GUARD elements larger on both sides and pre-filled with SENTINEL, the kernel gets the
+# inner view, and the whole buffer is compared bit for bit with what it must hold afterwards.  GUARD = 8 keeps an f32 or bf16 view
+# that starts right behind it 16-byte aligned; an extra offset k then makes the base pointer as unaligned as the case asks.
+SENTINEL = 7.0
+GUARD = 8
+F32_TINY = 2.0 ** -126            # smallest normal f32: a result below it may be flushed or lose bits, |error| <= F32_TINY per operation
+
+
+def guarded(n, dtype, device, k=0):
+    """-> (buf, view): buf = SENTINEL everywhere, GUARD + k elements before and GUARD after view = buf[GUARD + k : GUARD + k + n]"""
+    buf = torch.full((GUARD + k + n + GUARD,), SENTINEL, dtype=dtype, device=device)
+    return buf, buf[GUARD + k:GUARD + k + n]
+
+
+def guarded_like(values, device, k=0):
+    """guarded buffer whose inner view holds `values` (1-D host tensor)"""
+    buf, view = guarded(values.numel(), values.dtype, device, k)
+    view.copy_(values)
+    return buf, view
+
+
+def bits(t):
+    """integer view of a tensor's storage bits (host copy)"""
+    t = t.detach().contiguous().cpu()
+    return t.view({1: torch.int8, 2: torch.int16, 4: torch.int32, 8: torch.int64}[t.element_size()])
+
+
+def assert_bits(got, want, what=''):
+    """bit-for-bit equality (so -0.0 != 0.0, and a NaN is equal to the same NaN)"""
+    assert got.shape == want.shape and got.dtype == want.dtype, f'{what}: {tuple(got.shape)} {got.dtype} vs {tuple(want.shape)} {want.dtype}'
+    a, b = bits(got), bits(want)
+    bad = a != b
+    if bool(bad.any()):
+        i = int(bad.reshape(-1).nonzero()[0])
+        raise AssertionError(f'{what}: {int(bad.sum())} of {bad.numel()} elements differ in their bits; first at flat index {i}: '
+                             f'got {got.detach().cpu().reshape(-1)[i].item()!r}, want {want.detach().cpu().reshape(-1)[i].item()!r}')
+
+
+def assert_guarded(buf, inner, k=0, what=''):
+    """buf (from guarded(.., k)) holds `inner` in its view and SENTINEL everywhere else, bit for bit"""
+    want = torch.full(buf.shape, SENTINEL, dtype=buf.dtype)
+    want[GUARD + k:GUARD + k + inner.numel()] = inner.detach().cpu().reshape(-1).to(buf.dtype)
+    assert_bits(buf, want, what)
+
+
+def assert_bound_1d(y, value, tol, what=''):
+    """every element of y within tol of value (f64 host tensors of any shape; non-finite y fails)"""
+    y = y.detach().cpu().double().reshape(-1)
+    value, tol = value.reshape(-1), tol.reshape(-1)
+    bad = ~((y - value).abs() <= tol)
+    if bool(bad.any()):
+        ratio = torch.where(bad, torch.nan_to_num((y - value).abs() / tol, nan=float('inf'), posinf=float('inf')), torch.zeros_like(tol))
+        i = int(ratio.argmax())
+        raise AssertionError(f'{what}: {int(bad.sum())} of {bad.numel()} elements outside the derived bound; worst at [{i}]: '
+                             f'got {float(y[i]):.9g}, reference {float(value[i]):.9g}, bound {float(tol[i]):.3e}')
+
+
+def outside_share(y, value, tol):
+    """share of the elements of y that the bound rejects against this reference"""
+    y = torch.as_tensor(y).detach().cpu().double().reshape(-1)
+    return float((~((y - value.reshape(-1)).abs() <= tol.reshape(-1))).double().mean())
+
+
+# ---- Adam.  adam_kernel evaluates, in f32 and per element,
+#     mi = m * b1 + g * (1 - b1);  vi = v * b2 + g * g * (1 - b2);  denom = sqrtf(vi) / sqrtf(1 - hyper[2]) + eps;
+#     p' = p - (hyper[0] / (1 - hyper[1])) * (mi / denom)
+# The reference evaluates the same expression in f64 from the f32 inputs (b1, b2, eps as the f32 values the ABI receives).  The bound
+# counts the kernel's roundings, u = 2^-24 each; contracting a product and a sum into one fma only removes roundings.
+ADAM_M_ROUNDINGS = 4              # 1 - b1, the two products, their sum
+ADAM_V_ROUNDINGS = 5              # 1 - b2, g * g, times (1 - b2), v * b2, their sum (all terms >= 0: relative to vi itself)
+SQRTF_ERR = 2 * U32               # sqrtf: 1 ulp (HIP's documented bound; the default build rounds it correctly, 0.5 ulp)
+DIV_ERR = 2 * U32                 # f32 division: 1 ulp (same remark); there are two: hyper[0] / bc1 and mi / denom
+ADAM_BC_ROUNDINGS = 1             # 1 - hyper[1] and 1 - hyper[2]: one rounding each (halved by the square root for the latter)
+ADAM_EPS_SUM_ROUNDINGS = 1        # ... + eps
+ADAM_SCALE_ROUNDINGS = 1          # (lr / bc1) * (mi / denom)
+ADAM_P_ROUNDINGS = 1              # the final rounding of p - update, relative to the result
+SECOND_ORDER = 1 + 2.0 ** -10     # the products of two error terms the first-order count drops are below 2^-20 of it
+
+
+def f32c(x):
+    """the f32 value a C float argument receives, as a Python float"""
+    return float(np.float32(x))
+
+
+def adam_reference(p, g, m, v, hyper, b1, b2, eps):
+    """p, g, m, v: f64 tensors holding f32 values; hyper: the four f32 values {lr, beta1^t, beta2^t, t} the kernel reads.
+    -> dict m, v, p (the f64 results) and tol_m, tol_v, tol_p (element-wise bounds of the kernel's deviation from them)."""
+    b1, b2, eps = f32c(b1), f32c(b2), f32c(eps)
+    lr, h1, h2 = (float(hyper[i]) for i in range(3))
+    am, bm = m * b1, g * (1 - b1)
+    m1 = am + bm
+    tol_m = ADAM_M_ROUNDINGS * U32 * (am.abs() + bm.abs()) + 3 * F32_TINY
+    v1 = v * b2 + g * g * (1 - b2)
+    tol_v = ADAM_V_ROUNDINGS * U32 * v1 + 4 * F32_TINY
+    s = v1.sqrt()
+    s_hi, s_lo = (v1 + tol_v).sqrt(), (v1 - tol_v).clamp(min=0).sqrt()
+    ds = torch.maximum(s_hi - s, s - s_lo) + SQRTF_ERR * s_hi
+    bc2s = (1 - h2) ** 0.5
+    e_bc2s = 0.5 * ADAM_BC_ROUNDINGS * U32 + SQRTF_ERR
+    q = s / bc2s
+    dq = ds / bc2s + (s + ds) / bc2s * (e_bc2s + DIV_ERR)
+    denom = q + eps
+    dden = dq + ADAM_EPS_SUM_ROUNDINGS * U32 * (denom + dq)
+    r = m1 / denom
+    dr = tol_m / (denom - dden) + m1.abs() * dden / (denom * (denom - dden)) + DIV_ERR * (m1.abs() + tol_m) / (denom - dden) + F32_TINY
+    c = lr / (1 - h1)
+    e_c = ADAM_BC_ROUNDINGS * U32 + DIV_ERR
+    upd = c * r
+    dupd = abs(c) * (1 + e_c) * dr + upd.abs() * (e_c + ADAM_SCALE_ROUNDINGS * U32) + F32_TINY
+    p1 = p - upd
+    tol_p = (dupd + ADAM_P_ROUNDINGS * U32 * (p1.abs() + dupd)) * SECOND_ORDER
+    return dict(m=m1, v=v1, p=p1, tol_m=tol_m * SECOND_ORDER, tol_v=tol_v * SECOND_ORDER, tol_p=tol_p)
+
+
+def adam_f32(p, g, m, v, hyper, b1, b2, eps, mutation=None):
+    """numpy f32 restatement of adam_kernel's expression (one rounding per operation), or of one of the wrong kernels the bound must
+    reject: 'eps_in_sqrt', 'bc2_no_sqrt', 'b2_for_m', 'lr_no_bc1'.  Inputs: f32 numpy arrays.  -> (p', m', v') f32."""
+    f = np.float32
+    b1, b2, eps, one = f(b1), f(b2), f(eps), f(1)
+    lr, bc1, bc2 = f(hyper[0]), one - f(hyper[1]), one - f(hyper[2])
+    bc2_sqrt = bc2 if mutation == 'bc2_no_sqrt' else np.sqrt(bc2)
+    bm = b2 if mutation == 'b2_for_m' else b1
+    mi = m * bm + g * (one - bm)
+    vi = v * b2 + g * g * (one - b2)
+    denom = np.sqrt(vi + eps) / bc2_sqrt if mutation == 'eps_in_sqrt' else np.sqrt(vi) / bc2_sqrt + eps
+    scale = lr if mutation == 'lr_no_bc1' else lr / bc1
+    pi = p - scale * (mi / denom)
+    assert pi.dtype == np.float32 and mi.dtype == np.float32 and vi.dtype == np.float32
+    return pi, mi, vi
+
+
+ADAM_SPECIAL = 24                 # elements at the front of adam_case that carry the edge values
+
+
+def adam_case(n, seed, scale=1e-6):
+    """Seeded f32 inputs (p, g, m, v) of n elements.  |g| in [1, 2) scale, |m| in [0.25, 0.75) scale, v in [0.5, 1.5) scale^2, random
+    signs, |p| in [0.25, 1): at scale 1e-6 sqrt(v) is of the order of eps = 1e-8 / its bias correction, so eps inside the root, a
+    missing root of bc2 or a missing 1 / bc1 all move the update by a multiple of itself, and |m - g| >= scale / 4 keeps
+    (b2 - b1)(m - g) -- what b2 in place of b1 changes -- away from zero: every one of those wrong kernels moves p by far more than
+    u |p| (tests/test_step_bounds_cpu.py checks it).  The first min(n, ADAM_SPECIAL) elements cycle through the edges instead:
+    g == 0, |g| = 1e-20 (g * g underflows), and m = v = 0 with each of them and with an ordinary g."""
+    gen = torch.Generator().manual_seed(1000 * seed + n % 997)
+    u = lambda lo, hi: lo + (hi - lo) * torch.rand(n, generator=gen, dtype=torch.float64)
+    sg = lambda: torch.randint(0, 2, (n,), generator=gen).double() * 2 - 1
+    p, g, m, v = u(0.25, 1) * sg(), u(1, 2) * scale * sg(), u(0.25, 0.75) * scale * sg(), u(0.5, 1.5) * scale * scale
+    for i in range(min(n, ADAM_SPECIAL)):
+        kind = i % 6
+        if kind in (0, 3):
+            g[i] = 0.0
+        elif kind in (1, 4):
+            g[i] = 1e-20 * (1 if i % 4 < 2 else -1)
+        if kind >= 3:
+            m[i] = 0.0; v[i] = 0.0
+    return tuple(t.float().numpy() for t in (p, g, m, v))
+
+
+# ---- EMA.  ema_kernel: x = pk * mom + pq * (1 - mom) in f32.  1 - mom is exact for mom in [0.5, 1] (Sterbenz); the reference takes
+# its f32 value, so three roundings are left: the two products and the sum.
+EMA_ROUNDINGS = 3
+
+
+def ema_reference(pk, pq, mom):
+    """pk, pq: f64 tensors of f32 values -> (x, tol)"""
+    momf = np.float32(mom)
+    a, b = pk * float(momf), pq * float(np.float32(1) - momf)
+    x = a + b
+    per_rounding = (a.abs(), b.abs(), x.abs())                    # each rounding is relative to the value it produces
+    assert len(per_rounding) == EMA_ROUNDINGS
+    return x, (U32 * sum(per_rounding) + EMA_ROUNDINGS * F32_TINY) * SECOND_ORDER
+
+
+# ---- L1 loss.  l1_loss_kernel: a grid of min(ceil(n / 256), 1024) blocks of 256 threads; a thread adds |a - b| over its grid-stride
+# elements, the 64 lanes of a wave are folded by 6 shuffle steps, the wave sum is divided by n and added to *loss with one atomic.
+def l1_chain_length(n):
+    """longest chain of f32 additions (and the other roundings on the way) between one |a - b| and the loss"""
+    threads = min((n + 255) // 256, 1024) * 256
+    per_thread = (n + threads - 1) // threads               # additions into the thread's partial sum
+    wave_fold = 6
+    atomics = threads // 64                                 # one atomicAdd per wave, in any order
+    subtraction, division = 1, 1
+    return subtraction + per_thread + wave_fold + division + atomics
+
+
+def l1_loss_bound(a, b):
+    """a, b: f64 host tensors of f32 values -> (loss, tol)"""
+    n = a.numel()
+    mag = float((a - b).abs().sum()) / n
+    return mag, l1_chain_length(n) * U32 * mag * SECOND_ORDER
