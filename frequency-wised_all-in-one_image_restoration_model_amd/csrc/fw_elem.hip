@@ -88,6 +88,51 @@ __global__ void permute3_kernel(const TI* __restrict__ in, TO* __restrict__ out,
     }
 }
 
+// The transposing form: the output's unit-stride index is d0 or d1, not the input's d2 (the weight-gradient re-layouts of the k4s2 and
+// k2s2 convolutions, the forward k4s2 weight copy).  The two outer indices are walked as ONE row index m = o * U + u in the OUTPUT's
+// order (u = the unit-stride index of extent U, o = the other one); a workgroup moves a tile of 32 rows x 32 channels through LDS, so
+// a row is read as 32 contiguous input elements and a channel is written (or read-modify-written) as 32 rows whose addresses are
+// contiguous wherever the destination is.  The (o, u) split costs one division per row of a tile, kept in LDS; every element is still
+// moved by one scalar load and one scalar store to exactly the word the statement names, with the arithmetic of permute3_kernel.
+constexpr int PT = 32;
+template <typename TI, typename TO>
+__global__ __launch_bounds__(256) void permute3_tile_kernel(const TI* __restrict__ in, TO* __restrict__ out, int d0, int d1, int d2, long s0, long s1,
+                                                            long s2, int acc, int unit0, int ctiles) {
+    __shared__ float tile[PT][PT + 1];
+    __shared__ long row_in[PT], row_out[PT];
+    const int U = unit0 ? d0 : d1, M = d0 * d1;
+    const int mt = blockIdx.x / ctiles, ct = blockIdx.x - mt * ctiles;
+    const int m0 = mt * PT, c0 = ct * PT;
+    if (threadIdx.x < PT) {
+        const int m = min(m0 + (int)threadIdx.x, M - 1);
+        const int o = m / U, u = m - o * U;
+        const int a = unit0 ? u : o, b = unit0 ? o : u;
+        row_in[threadIdx.x] = ((long)a * d1 + b) * d2;
+        row_out[threadIdx.x] = a * s0 + b * s1;
+    }
+    __syncthreads();
+    const int lo = threadIdx.x & (PT - 1), hi = threadIdx.x >> 5;              // 32 x 8
+#pragma unroll
+    for (int k = 0; k < PT; k += 8) {
+        const int r = hi + k;
+        if (m0 + r < M && c0 + lo < d2) tile[r][lo] = TT<TI>::ld(in + row_in[r] + c0 + lo);
+    }
+    __syncthreads();
+    if (m0 + lo < M) {
+        const long ro = row_out[lo];
+#pragma unroll
+        for (int k = 0; k < PT; k += 8) {
+            const int c = c0 + hi + k;
+            if (c < d2) {
+                TO* d = out + ro + c * s2;
+                float v = tile[lo][hi + k];
+                if (acc) v += TT<TO>::ld(d);
+                TT<TO>::st(d, v);
+            }
+        }
+    }
+}
+
 // Many small f32 -> (f32 | bf16) re-layouts in ONE launch: the per-step operand copies of parameters whose stored layout no GEMM /
 // stencil kernel reads directly (depthwise taps -> tap-major, k4s2 / k2s2 convolution weights -> [Cout][K], rows that are not 16-byte
 // aligned in bf16).  ~170 launches of 5-8 us each per training step otherwise.
@@ -799,6 +844,73 @@ __global__ void col2im4_kernel(const T* __restrict__ dcol, float* __restrict__ d
     }
 }
 
+// The forms the model runs (4 * C / 4 <= 1024 vector slots, fewer than 2^31 tokens).  A thread keeps ONE slot for its whole life: its
+// place (kx, 4 channels) in the 4 * C run that one (output token, ky) reads and writes, or its 4 channels of an input token, so
+// the only index arithmetic left is the (b, y, x) split of a token, once per token.  All loads of a token are issued first, from
+// clamped coordinates, and the borders are applied by select afterwards.
+// im2col4: blockDim = ipb * 4 * C/4 rounded up to a wave; item = output token, ky = 0..3 unrolled: source pixels 2ox-1 .. 2ox+2 of
+// row 2oy-1+ky (contiguous when ldx == C) -> col[(t*16 + ky*4) * C ...], 4 * C contiguous elements.
+template <typename T>
+__global__ __launch_bounds__(1024) void im2col4_run_kernel(const float* __restrict__ x, long ldx, T* __restrict__ col, int B, int H, int W, int C,
+                                                           int ipb) {
+    const int Ho = H / 2, Wo = W / 2, c4n = C >> 2, Q = 4 * c4n;
+    const int il = threadIdx.x / Q, q = threadIdx.x - il * Q;
+    if (il >= ipb) return;
+    const int kx = q / c4n, c = (q - kx * c4n) * 4;
+    const unsigned ntok = (unsigned)B * Ho * Wo;
+    for (unsigned t = blockIdx.x * ipb + il; t < ntok; t += gridDim.x * ipb) {
+        const unsigned ox = t % Wo, t2 = t / Wo, oy = t2 % Ho, b = t2 / Ho;
+        const int ix = 2 * (int)ox - 1 + kx, iy0 = 2 * (int)oy - 1;
+        const bool okx = ix >= 0 && ix < W;
+        const float* px = x + (((long)b * H) * W + min(max(ix, 0), W - 1)) * ldx + c;
+        f32x4 v[4];
+#pragma unroll
+        for (int ky = 0; ky < 4; ++ky) v[ky] = *reinterpret_cast<const f32x4*>(px + (long)min(max(iy0 + ky, 0), H - 1) * W * ldx);
+        T* d = col + ((long)t * 16 + kx) * C + c;
+#pragma unroll
+        for (int ky = 0; ky < 4; ++ky) {
+            const bool ok = okx && iy0 + ky >= 0 && iy0 + ky < H;
+            const f32x4 u = ok ? v[ky] : f32x4{0.f, 0.f, 0.f, 0.f};
+            if (sizeof(T) == 4) *reinterpret_cast<f32x4*>(d + (long)ky * 4 * C) = u;
+            else *reinterpret_cast<uint2*>(d + (long)ky * 4 * C) = make_uint2(pack_bf2(u[0], u[1]), pack_bf2(u[2], u[3]));
+        }
+    }
+}
+// col2im4: item = input token, slot = 4 channels.  The (up to) four contributions are loaded together as 16-byte (f32) or 8-byte (bf16)
+// vectors and added in the order of col2im4_kernel: dres, then ky ascending, kx ascending; an absent tap is skipped, not added as 0.
+template <typename T>
+__global__ __launch_bounds__(1024) void col2im4_run_kernel(const T* __restrict__ dcol, float* __restrict__ dx, long lddx, const float* __restrict__ dres,
+                                                           long ldr, int B, int H, int W, int C, int ipb) {
+    const int Ho = H / 2, Wo = W / 2, c4n = C >> 2;
+    const int il = threadIdx.x / c4n, c = (threadIdx.x - il * c4n) * 4;
+    if (il >= ipb) return;
+    const unsigned ntok = (unsigned)B * H * W;
+    for (unsigned tok = blockIdx.x * ipb + il; tok < ntok; tok += gridDim.x * ipb) {
+        const unsigned xx = tok % W, t2 = tok / W, yy = t2 % H, b = t2 / H;
+        const int x = (int)xx, y = (int)yy;
+        const int ky0 = (y + 1) & 1, kx0 = (x + 1) & 1;
+        float f[4][4];
+        bool ok[4];
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const int ky = ky0 + 2 * i, kx = kx0 + 2 * j;
+                const int ny = y + 1 - ky, nx = x + 1 - kx;                 // even; the output pixel is (ny / 2, nx / 2)
+                ok[i * 2 + j] = ny >= 0 && ny < 2 * Ho && nx >= 0 && nx < 2 * Wo;
+                const int oy = min(max(ny, 0) >> 1, Ho - 1), ox = min(max(nx, 0) >> 1, Wo - 1);
+                ldvec4<T>(dcol + ((((long)b * Ho + oy) * Wo + ox) * 16 + ky * 4 + kx) * (long)C + c, f[i * 2 + j]);
+            }
+        f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (dres) acc = *reinterpret_cast<const f32x4*>(dres + (long)tok * ldr + c);
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+#pragma unroll
+            for (int e = 0; e < 4; ++e) acc[e] = ok[k] ? acc[e] + f[k][e] : acc[e];
+        *reinterpret_cast<f32x4*>(dx + (long)tok * lddx + c) = acc;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // k2 s2 transposed convolution = Linear(Cin -> 4*Cout) + depth-to-space
 // ------------------------------------------------------------------------------------------------
@@ -1142,17 +1254,33 @@ __global__ __launch_bounds__(256) void outproj_fwd_mfma_kernel(const float* __re
 // ------------------------------------------------------------------------------------------------
 // losses
 // ------------------------------------------------------------------------------------------------
-// loss += mean |a - b| ; dA = sign(a - b) * gscale / n
-__global__ void l1_loss_kernel(const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ da, long n, float gscale,
-                               float* __restrict__ loss) {
+// loss += mean |a - b| ; dA = sign(a - b) * gscale / n.  16-byte loads and stores when vec (all three pointers 16-byte aligned),
+// the n % 4 tail and unaligned calls one element at a time; a workgroup folds its four waves through LDS and adds ONE word.
+FW_DEV float l1_sign(float d, float gscale, long n) { return (d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f)) * gscale / n; }
+__global__ __launch_bounds__(TPB) void l1_loss_kernel(const float* __restrict__ a, const float* __restrict__ b, float* __restrict__ da, long n,
+                                                      float gscale, float* __restrict__ loss, int vec) {
+    __shared__ float red[TPB / 64];
     float s = 0.f;
-    for (long i = gtid(); i < n; i += gstride()) {
+    const long n4 = vec ? n >> 2 : 0;
+    for (long i = gtid(); i < n4; i += gstride()) {
+        const f32x4 d = *reinterpret_cast<const f32x4*>(a + 4 * i) - *reinterpret_cast<const f32x4*>(b + 4 * i);
+        s += (fabsf(d[0]) + fabsf(d[1])) + (fabsf(d[2]) + fabsf(d[3]));
+        if (da) *reinterpret_cast<f32x4*>(da + 4 * i) = f32x4{l1_sign(d[0], gscale, n), l1_sign(d[1], gscale, n), l1_sign(d[2], gscale, n), l1_sign(d[3], gscale, n)};
+    }
+    for (long i = 4 * n4 + gtid(); i < n; i += gstride()) {
         const float d = a[i] - b[i];
         s += fabsf(d);
-        if (da) da[i] = (d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f)) * gscale / n;
+        if (da) da[i] = l1_sign(d, gscale, n);
     }
     s = wave_sum(s);
-    if (lane_id() == 0) atomicAdd(loss, s / n);
+    if (lane_id() == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float t = red[0];
+#pragma unroll
+        for (int k = 1; k < TPB / 64; ++k) t += red[k];
+        atomicAdd(loss, t / n);
+    }
 }
 // cross entropy with label 0 over rows of logits[R][N]: loss += mean_r (lse - logit0); dlogits = (softmax - onehot0) * gscale / R
 __global__ void ce0_loss_kernel(const float* __restrict__ logits, float* __restrict__ dlogits, int R, int N, float gscale, float* __restrict__ loss) {
@@ -1341,6 +1469,8 @@ static int dwconv_tile_launch(const T* in, long ldi, const float* w, const float
         hipLaunchKernelGGL(kern, dim3(grid_for(n)), dim3(TPB), 0, ST, __VA_ARGS__);    \
         FW_LAUNCH_RET();                                                               \
     } while (0)
+// workgroups of the *_run_kernel forms: `ipb` tokens per workgroup pass, at most 8192 workgroups
+static inline long run_grid(long ntok, int ipb) { const long g = (ntok + ipb - 1) / ipb; return g > 8192 ? 8192 : g; }
 #define BYT(dtype, expr_bf, expr_f) return (dtype) == FW_DT_BF16 ? (expr_bf) : (expr_f)
 
 extern "C" int fw_cast_rows(int dtype, const float* src, long lds_, void* dst, long ldd, long rows, int cols,
@@ -1368,6 +1498,22 @@ extern "C" int fw_permute3(int in_dtype, int out_dtype, const void* in, void* ou
                            long s2, int accumulate, void* stream) {
     FW_CHECK_ARG(in && out && d0 > 0 && d1 > 0 && d2 > 0);
     const long n = (long)d0 * d1 * d2;
+    // unit stride on d0 or d1, all strides positive: the LDS-tiled transposing form; everything else (negative, zero, gaps) as before
+    const bool unit0 = s0 == 1 && s1 > 1 && s2 > 1, unit1 = s1 == 1 && s0 > 1 && s2 > 1;
+    const long tiles = (((long)d0 * d1 + PT - 1) / PT) * ((d2 + PT - 1) / PT);
+    if ((unit0 || unit1) && (long)d0 * d1 < (1L << 30) && tiles < (1L << 31)) {
+        const dim3 g((unsigned)tiles), b(256);
+        const int ct = (d2 + PT - 1) / PT, u0 = unit0 ? 1 : 0;
+        if (in_dtype == 0 && out_dtype == 0)
+            hipLaunchKernelGGL((permute3_tile_kernel<float, float>), g, b, 0, ST, (const float*)in, (float*)out, d0, d1, d2, s0, s1, s2, accumulate, u0, ct);
+        else if (in_dtype == 0 && out_dtype == 1)
+            hipLaunchKernelGGL((permute3_tile_kernel<float, bf16raw>), g, b, 0, ST, (const float*)in, (bf16raw*)out, d0, d1, d2, s0, s1, s2, accumulate, u0, ct);
+        else if (in_dtype == 1 && out_dtype == 0)
+            hipLaunchKernelGGL((permute3_tile_kernel<bf16raw, float>), g, b, 0, ST, (const bf16raw*)in, (float*)out, d0, d1, d2, s0, s1, s2, accumulate, u0, ct);
+        else
+            return -1;
+        FW_LAUNCH_RET();
+    }
     if (in_dtype == 0 && out_dtype == 0) LAUNCH((permute3_kernel<float, float>), n, (const float*)in, (float*)out, d0, d1, d2, s0, s1, s2, accumulate);
     if (in_dtype == 0 && out_dtype == 1) LAUNCH((permute3_kernel<float, bf16raw>), n, (const float*)in, (bf16raw*)out, d0, d1, d2, s0, s1, s2, accumulate);
     if (in_dtype == 1 && out_dtype == 0) LAUNCH((permute3_kernel<bf16raw, float>), n, (const bf16raw*)in, (float*)out, d0, d1, d2, s0, s1, s2, accumulate);
@@ -1471,6 +1617,15 @@ extern "C" int fw_dwconv_bwd(int dtype, const void* dh2, long ldg, const void* g
 extern "C" int fw_im2col4(int dtype, const float* x, long ldx, void* col, int B, int H, int W, int C, void* stream) {
     FW_CHECK_ARG(x && col && C % 4 == 0 && ldx % 4 == 0 && H % 2 == 0 && W % 2 == 0);
     const long n = (long)B * (H / 2) * (W / 2) * 16 * (C / 4);
+    const long ntok = (long)B * (H / 2) * (W / 2);
+    if (C >= 4 && C <= 1024 && ntok > 0 && ntok < (1L << 31) - (1L << 24) && ((uintptr_t)x & 15) == 0 &&
+        ((uintptr_t)col & (dtype == FW_DT_BF16 ? 7 : 15)) == 0) {
+        const int ipb = C >= 256 ? 1 : 256 / C;                                   // tokens per workgroup pass: about 256 threads
+        const dim3 g((unsigned)run_grid(ntok, ipb)), b((unsigned)((ipb * C + 63) / 64 * 64));
+        if (dtype == FW_DT_BF16) hipLaunchKernelGGL((im2col4_run_kernel<bf16raw>), g, b, 0, ST, x, ldx, (bf16raw*)col, B, H, W, C, ipb);
+        else hipLaunchKernelGGL((im2col4_run_kernel<float>), g, b, 0, ST, x, ldx, (float*)col, B, H, W, C, ipb);
+        FW_LAUNCH_RET();
+    }
     if (dtype == FW_DT_BF16) LAUNCH((im2col4_kernel<bf16raw>), n, x, ldx, (bf16raw*)col, B, H, W, C);
     LAUNCH((im2col4_kernel<float>), n, x, ldx, (float*)col, B, H, W, C);
 }
@@ -1478,6 +1633,15 @@ extern "C" int fw_col2im4(int dtype, const void* dcol, float* dx, long lddx, con
                           void* stream) {
     FW_CHECK_ARG(dcol && dx && C % 4 == 0 && lddx % 4 == 0 && H % 2 == 0 && W % 2 == 0 && (!dres || ldr % 4 == 0));
     const long n = (long)B * H * W * (C / 4);
+    const long ntok = (long)B * H * W;
+    if (C >= 4 && C <= 4096 && ntok > 0 && ntok < (1L << 31) - (1L << 24) && (((uintptr_t)dx | (uintptr_t)dres) & 15) == 0 &&
+        ((uintptr_t)dcol & (dtype == FW_DT_BF16 ? 7 : 15)) == 0) {
+        const int c4n = C / 4, ipb = c4n >= 256 ? 1 : 256 / c4n;
+        const dim3 g((unsigned)run_grid(ntok, ipb)), b((unsigned)((ipb * c4n + 63) / 64 * 64));
+        if (dtype == FW_DT_BF16) hipLaunchKernelGGL((col2im4_run_kernel<bf16raw>), g, b, 0, ST, (const bf16raw*)dcol, dx, lddx, dres, ldr, B, H, W, C, ipb);
+        else hipLaunchKernelGGL((col2im4_run_kernel<float>), g, b, 0, ST, (const float*)dcol, dx, lddx, dres, ldr, B, H, W, C, ipb);
+        FW_LAUNCH_RET();
+    }
     if (dtype == FW_DT_BF16) LAUNCH((col2im4_kernel<bf16raw>), n, (const bf16raw*)dcol, dx, lddx, dres, ldr, B, H, W, C);
     LAUNCH((col2im4_kernel<float>), n, (const float*)dcol, dx, lddx, dres, ldr, B, H, W, C);
 }
@@ -1563,7 +1727,8 @@ extern "C" int fw_outproj_bwd(const float* dout, const float* fea, long ldf, con
 }
 extern "C" int fw_l1_loss(const float* a, const float* b, float* da, long n, float gscale, float* loss, void* stream) {
     FW_CHECK_ARG(a && b && loss && n > 0);
-    hipLaunchKernelGGL(l1_loss_kernel, dim3(grid_for(n, 1024)), dim3(TPB), 0, ST, a, b, da, n, gscale, loss);
+    const int vec = (((uintptr_t)a | (uintptr_t)b | (uintptr_t)da) & 15) == 0;
+    hipLaunchKernelGGL(l1_loss_kernel, dim3(grid_for(vec ? (n + 3) / 4 : n, 512)), dim3(TPB), 0, ST, a, b, da, n, gscale, loss, vec);
     FW_LAUNCH_RET();
 }
 extern "C" int fw_ce0_loss(const float* logits, float* dlogits, int R, int N, float gscale, float* loss, void* stream) {

@@ -632,6 +632,245 @@ __global__ __launch_bounds__(64) void lfs_lambda_bwd_kernel(const float* __restr
     }
 }
 
+// ---- the forms the model runs (C a multiple of 4 up to LFS_ROWC, 16-byte aligned rows; the kernels above take every other call).
+// A lane owns two 16-byte channel vectors of a row (vector l and l + 64), so a wave holds a whole row in registers: every load of a
+// wave's rows is issued before the first reduction, mean and variance come from the registers (same two-pass arithmetic as above),
+// and nothing is read twice.  Lanes past the row load a clamped vector and select zero.
+constexpr int LFS_ROWC = 512;
+constexpr int LFS_FW = 16, LFS_FT = 4;      // forward: 16 waves per (band, image), 4 rows in flight per wave
+constexpr int LFS_BT = 2;                   // backward: 4 waves x 2 rows per workgroup
+FW_DEV float sum4(const f32x4& v) { return (v[0] + v[1]) + (v[2] + v[3]); }
+
+// One workgroup per (band, image): its NT x C tile (115 KB at the model's size) is read once; the column mean is folded from the
+// per-wave register sums through LDS in a fixed order, so xbar needs no second sweep, no atomics and no zero fill.
+__global__ __launch_bounds__(64 * LFS_FW) void lfs_xbar_rows_kernel(const float* __restrict__ inter, float* __restrict__ xbar,
+                                                                    float* __restrict__ stats, int NT, int C, float eps) {
+    __shared__ float part[LFS_FW][LFS_ROWC];
+    const size_t blk = (size_t)blockIdx.x;
+    const float* x = inter + blk * NT * C;
+    const int w = threadIdx.x >> 6, l = lane_id(), c4n = C >> 2;
+    const bool h0 = l < c4n, h1 = l + 64 < c4n;
+    const int i0 = 4 * min(l, c4n - 1), i1 = 4 * min(l + 64, c4n - 1);
+    const f32x4 zero = f32x4{0.f, 0.f, 0.f, 0.f};
+    f32x4 a0 = zero, a1 = zero;
+    for (int t0 = w * LFS_FT; t0 < NT; t0 += LFS_FW * LFS_FT) {
+        f32x4 v0[LFS_FT], v1[LFS_FT];
+#pragma unroll
+        for (int k = 0; k < LFS_FT; ++k) {
+            const float* row = x + (size_t)min(t0 + k, NT - 1) * C;
+            v0[k] = *reinterpret_cast<const f32x4*>(row + i0);
+            v1[k] = *reinterpret_cast<const f32x4*>(row + i1);
+        }
+#pragma unroll
+        for (int k = 0; k < LFS_FT; ++k) {
+            if (t0 + k >= NT) break;                                           // wave-uniform
+            const f32x4 u0 = h0 ? v0[k] : zero, u1 = h1 ? v1[k] : zero;
+            const float m = wave_sum(sum4(u0) + sum4(u1)) / C;
+            const f32x4 d0 = h0 ? u0 - m : zero, d1 = h1 ? u1 - m : zero;
+            const float r = rsqrtf(wave_sum(sum4(d0 * d0) + sum4(d1 * d1)) / C + eps);
+            if (l == 0) *reinterpret_cast<float2*>(stats + (blk * NT + t0 + k) * 2) = make_float2(m, r);
+            a0 += d0 * r; a1 += d1 * r;
+        }
+    }
+    if (h0) *reinterpret_cast<f32x4*>(&part[w][i0]) = a0;
+    if (h1) *reinterpret_cast<f32x4*>(&part[w][i1]) = a1;
+    __syncthreads();
+    for (int c = threadIdx.x; c < C; c += 64 * LFS_FW) {
+        float s = 0.f;
+#pragma unroll
+        for (int k = 0; k < LFS_FW; ++k) s += part[k][c];
+        xbar[blk * C + c] = s / NT;
+    }
+}
+// grid (ceil(NT / (4 LFS_BT)), nb1 * B), 256 threads: a wave owns LFS_BT rows; g = dxbar is fetched once per lane and each row of
+// inter and of dinter once, all requested before the first reduction.
+__global__ __launch_bounds__(256) void lfs_xbar_bwd_rows_kernel(const float* __restrict__ inter, const float* __restrict__ stats,
+                                                                const float* __restrict__ dxbar, float* __restrict__ dinter, int NT, int C) {
+    const size_t blk = (size_t)blockIdx.y;
+    const float* x = inter + blk * NT * C; float* dx = dinter + blk * NT * C;
+    const int w = threadIdx.x >> 6, l = lane_id(), c4n = C >> 2;
+    const bool h0 = l < c4n, h1 = l + 64 < c4n;
+    const int i0 = 4 * min(l, c4n - 1), i1 = 4 * min(l + 64, c4n - 1);
+    const f32x4 zero = f32x4{0.f, 0.f, 0.f, 0.f};
+    const int t0 = (blockIdx.x * 4 + w) * LFS_BT;
+    if (t0 >= NT) return;
+    f32x4 g0 = *reinterpret_cast<const f32x4*>(dxbar + blk * C + i0), g1 = *reinterpret_cast<const f32x4*>(dxbar + blk * C + i1);
+    f32x4 v0[LFS_BT], v1[LFS_BT], o0[LFS_BT], o1[LFS_BT];
+    float2 st[LFS_BT];
+#pragma unroll
+    for (int k = 0; k < LFS_BT; ++k) {
+        const size_t t = (size_t)min(t0 + k, NT - 1);
+        st[k] = *reinterpret_cast<const float2*>(stats + (blk * NT + t) * 2);
+        v0[k] = *reinterpret_cast<const f32x4*>(x + t * C + i0); v1[k] = *reinterpret_cast<const f32x4*>(x + t * C + i1);
+        o0[k] = *reinterpret_cast<const f32x4*>(dx + t * C + i0); o1[k] = *reinterpret_cast<const f32x4*>(dx + t * C + i1);
+    }
+    g0 = h0 ? g0 : zero; g1 = h1 ? g1 : zero;
+    const float m1 = wave_sum(sum4(g0) + sum4(g1)) / C / NT;
+    g0 = g0 / (float)NT; g1 = g1 / (float)NT;
+#pragma unroll
+    for (int k = 0; k < LFS_BT; ++k) {
+        if (t0 + k >= NT) break;                                               // wave-uniform
+        const float m = st[k].x, r = st[k].y;
+        const f32x4 xh0 = h0 ? (v0[k] - m) * r : zero, xh1 = h1 ? (v1[k] - m) * r : zero;
+        const float m2 = wave_sum(sum4(g0 * xh0) + sum4(g1 * xh1)) / C;
+        float* d = dx + (size_t)(t0 + k) * C;
+        if (h0) *reinterpret_cast<f32x4*>(d + i0) = o0[k] + r * (g0 - m1 - xh0 * m2);
+        if (h1) *reinterpret_cast<f32x4*>(d + i1) = o1[k] + r * (g1 - m1 - xh1 * m2);
+    }
+}
+
+// grid (nblk, B), one wave per band.  z = lnw * xbar + lnb is formed once in registers (8 channels per lane); the rows of W are taken
+// eight at a time with every load requested before the first reduction (rows past h re-read row h - 1 and are dropped); lane j ends
+// up holding u[j], and the two h x h layers read each other's values by lane exchange: no LDS and no barrier until the two bands meet.
+constexpr int LFS_ZK = LFS_ROWC / 64;
+__global__ __launch_bounds__(128) void lfs_lambda_wave_kernel(const float* __restrict__ xbar, const unsigned long long* __restrict__ ptab,
+                                                              const int* __restrict__ heads, const long long* __restrict__ coef_off,
+                                                              float* __restrict__ coef, float* __restrict__ save, int B, int C, int nb1) {
+    __shared__ float lam[2][16];
+    const int blk = blockIdx.x, b = blockIdx.y, h = heads[blk], l = lane_id(), band = threadIdx.x >> 6;
+    const unsigned long long* pt = ptab + ((size_t)blk * 2 + band) * 8;
+    const float* lnw = (const float*)pt[0]; const float* lnb = (const float*)pt[1];
+    const float* W = (const float*)pt[2]; const float* bl = (const float*)pt[3];
+    const float* W1 = (const float*)pt[4]; const float* b1 = (const float*)pt[5];
+    const float* W2 = (const float*)pt[6]; const float* b2 = (const float*)pt[7];
+    const float* xb = xbar + ((size_t)band * B + b) * C;
+    if (h <= 0) return;
+    const int lh = min(l, h - 1);
+    float z[LFS_ZK];
+#pragma unroll
+    for (int k = 0; k < LFS_ZK; ++k) {
+        const int c = min(l + 64 * k, C - 1);
+        const float v = lnw[c] * xb[c] + lnb[c];
+        z[k] = l + 64 * k < C ? v : 0.f;
+    }
+    float w1[16], w2[16];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) { w1[j] = W1[lh * h + min(j, h - 1)]; w2[j] = W2[lh * h + min(j, h - 1)]; }
+    const float bu = bl[lh], ba = b1[lh], bo = b2[lh];
+    float u = 0.f;
+    for (int h0 = 0; h0 < h; h0 += 8) {
+        float s[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const float* row = W + (size_t)min(h0 + j, h - 1) * C;
+            s[j] = 0.f;
+#pragma unroll
+            for (int k = 0; k < LFS_ZK; ++k) s[j] += row[min(l + 64 * k, C - 1)] * z[k];
+        }
+#pragma unroll
+        for (int j = 0; j < 8; ++j) { const float t = wave_sum(s[j]); u = l == h0 + j ? t : u; }
+    }
+    u += bu;
+    float a = ba;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) { const float uj = __shfl(u, j, 64); a += j < h ? w1[j] * uj : 0.f; }
+    const float s1 = lrelu_f(a, 0.1f);
+    float o = bo;
+#pragma unroll
+    for (int j = 0; j < 16; ++j) { const float sj = __shfl(s1, j, 64); o += j < h ? w2[j] * sj : 0.f; }
+    if (l < h) {
+        float* sv = save + ((((size_t)blk * 2 + band) * B + b) * 16) * 3;
+        sv[l * 3] = u; sv[l * 3 + 1] = a; sv[l * 3 + 2] = s1;
+        lam[band][l] = o;
+    }
+    __syncthreads();
+    if (band == 0 && l < h) {
+        float* cf = coef + coef_off[blk] + ((size_t)b * h + l) * 3;
+        if (nb1 == 2) { const float l1 = lam[0][l], l2 = lam[1][l]; cf[0] = 1.f + l2; cf[1] = -l2 * (1.f / 64.f); cf[2] = l1 - l2; }
+        else { const float l1 = lam[0][l]; cf[0] = 1.f + l1; cf[1] = -l1 * (1.f / 64.f); cf[2] = 0.f; }
+    }
+}
+// grid (nblk, nb1), 256 threads, dynamic LDS 3 x [B][16] floats: ONE workgroup owns the parameters of a (block, band) and walks all
+// B images, so every gradient word is summed in registers and added to memory once with a plain read-modify-write (it still ADDS:
+// the engine passes live .grad views).  Only dxbar, which all blocks share, keeps its atomics (nb1 * B * C words).
+__global__ __launch_bounds__(256) void lfs_lambda_bwd_block_kernel(const float* __restrict__ xbar, const unsigned long long* __restrict__ ptab,
+                                                                   const unsigned long long* __restrict__ gtab, const int* __restrict__ heads,
+                                                                   const long long* __restrict__ coef_off, const float* __restrict__ dcoef,
+                                                                   const float* __restrict__ save, float* __restrict__ dxbar, int B, int C, int nb1) {
+    extern __shared__ float lfs_sm[];
+    float* dl = lfs_sm; float* da1 = dl + B * 16; float* du = da1 + B * 16;      // [B][16] each
+    const int blk = blockIdx.x, band = blockIdx.y, h = heads[blk], tid = threadIdx.x;
+    const unsigned long long* pt = ptab + ((size_t)blk * 2 + band) * 8;
+    const unsigned long long* gt = gtab + ((size_t)blk * 2 + band) * 8;
+    const float* lnw = (const float*)pt[0]; const float* lnb = (const float*)pt[1];
+    const float* W = (const float*)pt[2]; const float* W1 = (const float*)pt[4]; const float* W2 = (const float*)pt[6];
+    float* g_lnw = (float*)gt[0]; float* g_lnb = (float*)gt[1]; float* gW = (float*)gt[2]; float* gbl = (float*)gt[3];
+    float* gW1 = (float*)gt[4]; float* gb1 = (float*)gt[5]; float* gW2 = (float*)gt[6]; float* gb2 = (float*)gt[7];
+    const float* xb = xbar + (size_t)band * B * C;
+    const float* sv = save + (((size_t)blk * 2 + band) * B * 16) * 3;           // [B][16][3] = u, a1, s
+    const int n = B * 16;
+    if (h <= 0) return;
+    // the h x h backward of every image: item (b, l)
+    for (int i = tid; i < n; i += 256) {
+        const int b = i >> 4, l = i & 15;
+        float d = 0.f;
+        if (l < h) {
+            const float* dc = dcoef + coef_off[blk] + ((size_t)b * h + l) * 3;
+            if (nb1 == 2) d = band == 0 ? dc[2] : (dc[0] - dc[1] * (1.f / 64.f) - dc[2]);
+            else d = dc[0] - dc[1] * (1.f / 64.f);
+        }
+        dl[i] = d;
+    }
+    __syncthreads();
+    for (int i = tid; i < n; i += 256) {
+        const int b = i >> 4, l = i & 15;
+        float ds = 0.f;
+        if (l < h) {
+            for (int j = 0; j < h; ++j) ds += W2[j * h + l] * dl[b * 16 + j];
+            ds = sv[i * 3 + 1] > 0.f ? ds : ds * 0.1f;
+        }
+        da1[i] = ds;
+    }
+    __syncthreads();
+    for (int i = tid; i < n; i += 256) {
+        const int b = i >> 4, l = i & 15;
+        float d = 0.f;
+        if (l < h)
+            for (int j = 0; j < h; ++j) d += W1[j * h + l] * da1[b * 16 + j];
+        du[i] = d;
+    }
+    __syncthreads();
+    // the h x h weights and the three h-vectors: item (l, j) sums its word over the images
+    for (int i = tid; i < h * h; i += 256) {
+        const int l = i / h, j = i - l * h;
+        float s2 = 0.f, s1 = 0.f;
+        for (int b = 0; b < B; ++b) {
+            s2 += dl[b * 16 + l] * sv[(b * 16 + j) * 3 + 2];
+            s1 += da1[b * 16 + l] * sv[(b * 16 + j) * 3];
+        }
+        gW2[i] += s2; gW1[i] += s1;
+    }
+    if (tid < h) {
+        float s2 = 0.f, s1 = 0.f, s0 = 0.f;
+        for (int b = 0; b < B; ++b) { s2 += dl[b * 16 + tid]; s1 += da1[b * 16 + tid]; s0 += du[b * 16 + tid]; }
+        gb2[tid] += s2; gb1[tid] += s1; gbl[tid] += s0;
+    }
+    // the channels: a thread owns c, keeps its h words of W and of gW in registers and walks the images
+    for (int c = tid; c < C; c += 256) {
+        const float lw = lnw[c], lb = lnb[c];
+        float wc[16], gw[16];
+#pragma unroll
+        for (int hh = 0; hh < 16; ++hh) { wc[hh] = W[(size_t)min(hh, h - 1) * C + c]; gw[hh] = 0.f; }
+        float glw = 0.f, glb = 0.f;
+        for (int b = 0; b < B; ++b) {
+            const float xv = xb[(size_t)b * C + c];
+            const float z = lw * xv + lb;
+            float dz = 0.f;
+#pragma unroll
+            for (int hh = 0; hh < 16; ++hh) {
+                const float d = du[b * 16 + hh];                              // 0 for hh >= h
+                gw[hh] += d * z; dz += wc[hh] * d;
+            }
+            glw += dz * xv; glb += dz;
+            atomicAdd(dxbar + ((size_t)band * B + b) * C + c, dz * lw);
+        }
+#pragma unroll
+        for (int hh = 0; hh < 16; ++hh)
+            if (hh < h) gW[(size_t)hh * C + c] += gw[hh];
+        g_lnw[c] += glw; g_lnb[c] += glb;
+    }
+}
+
 }  // namespace
 
 #define ST ((hipStream_t)stream)
@@ -732,26 +971,42 @@ extern "C" int fw_moco_enqueue(float* queue, const float* khat, long long* ptr, 
 }
 
 // inter: f32 [nb1*B][NT][C] (bands 1.. of the encoder output, contiguous).  stats: f32 [nb1*B][NT][2].
+static bool lfs_rows_ok(int C, const void* a, const void* b, const void* c, const void* d) {
+    return C >= 4 && C % 4 == 0 && C <= LFS_ROWC && (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)d) & 15) == 0;
+}
 extern "C" int fw_lfs_xbar(const float* inter, float* xbar, float* stats, int nb1, int B, int NT, int C, float eps, void* stream) {
     FW_CHECK_ARG(inter && xbar && stats && NT <= LFS_MAXT && NT > 0);
-    hipLaunchKernelGGL(lfs_xbar_kernel, dim3(nb1 * B), dim3(256), 0, ST, inter, xbar, stats, NT, C, eps);
+    if (lfs_rows_ok(C, inter, xbar, stats, nullptr))
+        hipLaunchKernelGGL(lfs_xbar_rows_kernel, dim3(nb1 * B), dim3(64 * LFS_FW), 0, ST, inter, xbar, stats, NT, C, eps);
+    else
+        hipLaunchKernelGGL(lfs_xbar_kernel, dim3(nb1 * B), dim3(256), 0, ST, inter, xbar, stats, NT, C, eps);
     FW_LAUNCH_RET();
 }
 extern "C" int fw_lfs_xbar_bwd(const float* inter, const float* stats, const float* dxbar, float* dinter, int nb1, int B, int NT, int C, void* stream) {
     FW_CHECK_ARG(inter && stats && dxbar && dinter);
-    hipLaunchKernelGGL(lfs_xbar_bwd_kernel, dim3(nb1 * B), dim3(256), 0, ST, inter, stats, dxbar, dinter, NT, C);
+    if (lfs_rows_ok(C, inter, stats, dxbar, dinter) && NT > 0)
+        hipLaunchKernelGGL(lfs_xbar_bwd_rows_kernel, dim3(fw_cdiv(NT, 4 * LFS_BT), nb1 * B), dim3(256), 0, ST, inter, stats, dxbar, dinter, NT, C);
+    else
+        hipLaunchKernelGGL(lfs_xbar_bwd_kernel, dim3(nb1 * B), dim3(256), 0, ST, inter, stats, dxbar, dinter, NT, C);
     FW_LAUNCH_RET();
 }
 extern "C" int fw_lfs_lambda(const float* xbar, const unsigned long long* ptab, const int* heads, const long long* coef_off, float* coef,
                              float* save, int nblk, int B, int C, int nb1, void* stream) {
     FW_CHECK_ARG(xbar && ptab && heads && coef_off && coef && save && nblk > 0 && (nb1 == 1 || nb1 == 2));
-    hipLaunchKernelGGL(lfs_lambda_kernel, dim3(nblk, B), dim3(64), 0, ST, xbar, ptab, heads, coef_off, coef, save, B, C, nb1);
+    if (C > 0 && C <= LFS_ROWC)
+        hipLaunchKernelGGL(lfs_lambda_wave_kernel, dim3(nblk, B), dim3(64 * nb1), 0, ST, xbar, ptab, heads, coef_off, coef, save, B, C, nb1);
+    else
+        hipLaunchKernelGGL(lfs_lambda_kernel, dim3(nblk, B), dim3(64), 0, ST, xbar, ptab, heads, coef_off, coef, save, B, C, nb1);
     FW_LAUNCH_RET();
 }
 extern "C" int fw_lfs_lambda_bwd(const float* xbar, const unsigned long long* ptab, const unsigned long long* gtab, const int* heads,
                                  const long long* coef_off, const float* dcoef, const float* save, float* dxbar, int nblk, int B, int C,
                                  int nb1, void* stream) {
     FW_CHECK_ARG(xbar && ptab && gtab && heads && coef_off && dcoef && save && dxbar && (nb1 == 1 || nb1 == 2));
-    hipLaunchKernelGGL(lfs_lambda_bwd_kernel, dim3(nblk, B), dim3(64), 0, ST, xbar, ptab, gtab, heads, coef_off, dcoef, save, dxbar, B, C, nb1);
+    if (B > 0 && B <= 256)                  // 3 x [B][16] floats of LDS: 48 KB at most
+        hipLaunchKernelGGL(lfs_lambda_bwd_block_kernel, dim3(nblk, nb1), dim3(256), (size_t)B * 16 * 3 * sizeof(float), ST, xbar, ptab, gtab, heads,
+                           coef_off, dcoef, save, dxbar, B, C, nb1);
+    else
+        hipLaunchKernelGGL(lfs_lambda_bwd_kernel, dim3(nblk, B), dim3(64), 0, ST, xbar, ptab, gtab, heads, coef_off, dcoef, save, dxbar, B, C, nb1);
     FW_LAUNCH_RET();
 }

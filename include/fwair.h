@@ -190,7 +190,10 @@ int fw_moco_logits_bwd(const float* q, const float* khat, const float* queue, co
                        int ED, int K, float invT, void* stream);
 int fw_moco_enqueue(float* queue, const float* khat, long long* ptr, int L, int B, int ED, int K, void* stream);
 
-/* ---- learned-frequency-selection lambda heads of all decoder blocks (decoder_Uformer.py:178-193,279-284) -- */
+/* ---- learned-frequency-selection lambda heads of all decoder blocks (decoder_Uformer.py:178-193,279-284) --
+ * fw_lfs_lambda_bwd ADDS into the tensors gtab names, each word once with a plain read-modify-write by the workgroup that owns its
+ * (block, band): two entries of gtab must not name the same memory, and nothing else may write it while the launch runs.  dxbar,
+ * shared by all blocks, is added with atomics. */
 int fw_lfs_xbar(const float* inter, float* xbar, float* stats, int nb1, int B, int NT, int C, float eps, void* stream);
 int fw_lfs_xbar_bwd(const float* inter, const float* stats, const float* dxbar, float* dinter, int nb1, int B, int NT, int C,
                     void* stream);
