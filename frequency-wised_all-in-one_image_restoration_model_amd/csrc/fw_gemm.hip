@@ -1501,16 +1501,255 @@ int launch_big(const GemmArgs& a, hipStream_t st) {
 //     memory into registers (16 B per lane, k-contiguous rows -- no LDS, no barrier), X is read exactly once for
 //     all columns of the panel, and the strip after next is requested before the epilogue of the current one.
 // 2 workgroups = 16 independent waves per CU keep loads, MFMAs and stores of different strips in flight together.
+// K > 256 bytes with a row-dependent operand: two X sets (128 registers) and two operand sets do not fit 256 VGPRs -- no hot loop
+#define STREAM_HOT(NCH, EXT) (!((NCH) == 8 && (EXT) != 0))
 #define STREAM_MTS(NCH, EXT) 2          /* 64-row strips (4) for the K <= 64 plain variant measured no gain: 71.7 vs 77.5 us at 786 432 x 88 x 28, slower elsewhere */
+
+// ---- the FULL strips of the three epilogues a training step uses (bf16 operands), decided once per launch on the host --------
+//   EXT 0  C (bf16) = acc + bias, through the wave's LDS region as whole row segments (staged mode 0)
+//   EXT 1  C (bf16) = (acc + bias) * GELU'(aux)
+//   EXT 2  C (f32)  = residual + rowscale * (acc + bias)
+// vmcnt retires loads AND stores in issue order, so a wave that waits for a load also waits for every store issued before it.
+// Here nothing is fetched behind a store that is about to be needed: strip s + 1's X (and the operands of its first column block,
+// and its row scales) are requested before the first store of strip s, the operands of column block j + 1 before the stores of
+// block j, and the body is straight-line -- NB column blocks unrolled, no row test (full strips only), no store under a lane
+// test, no branch on the epilogue's form -- so that every s_waitcnt the compiler places is a COUNTED one that leaves the younger
+// stores outstanding (the listing facts: profiles/r09_stream_kernel_meta.txt; check them again after any edit here).
+// The ragged last strip, and every launch in another form, takes the generic loop of the kernel below.
+// Same arithmetic in the same order as epi_apply (alpha == 1: fma(acc, 1, bias) == acc + bias): the outputs are bit-identical.
+template <int NCH, int EXT, int NB>
+FW_DEV int stream_hot_strips(const GemmArgs& a, char* smem, const int bnp, const int n_blk, int strip, const int stride, const int full) {
+    using T = bf16raw;
+    constexpr int MTS = 2, RL = NCH * 64, ROWS = 16 * MTS;
+    constexpr int ESZ = EXT == 2 ? 4 : 2;                 // bytes per element of the row-dependent operand and of C (EXT 2: f32)
+    static_assert(STREAM_MTS(NCH, EXT) == MTS, "strip height");
+    const int l = lane_id(), wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    strip = __builtin_amdgcn_readfirstlane(strip);        // wave-uniform: the loop and the row part of every address stay scalar
+    const int kbytes = a.K * 2;
+    const float* sbias = reinterpret_cast<const float*>(smem + (size_t)bnp * RL);
+    struct XSet { uint4 v[MTS][NCH]; };
+    struct ESet { uint4 v[MTS][4]; float rs[MTS]; };     // EXT 1 fills .x .y only; rs: the strip's row scales (first block's set)
+    const int ncols = min(bnp, a.N - n_blk);              // > (NB - 1) * 64: the caller switches on the block count
+    // addresses = wave-uniform row / block part (scalar) + a lane offset that does not change from strip to strip (launch_stream
+    // keeps the leading dimensions of a hot launch below 2^24 elements: the lane offsets fit 32 bits)
+    unsigned xoff[NCH];
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+        const int kb = c * 64 + ((l >> 4) << 4);
+        xoff[c] = (unsigned)(l & 15) * (unsigned)a.ldx * 2u + (unsigned)(kb < kbytes ? kb : 0);
+    }
+    auto issue_x = [&](XSet& x, int s) {
+#pragma unroll
+        for (int mt = 0; mt < MTS; ++mt) {
+            const char* src = a.X + (long)(s * ROWS + mt * 16) * a.ldx * 2;
+#pragma unroll
+            for (int c = 0; c < NCH; ++c) x.v[mt][c] = *reinterpret_cast<const uint4*>(src + xoff[c]);
+        }
+    };
+    auto mask_x = [&](XSet& x) {                          // zero what lies past K
+#pragma unroll
+        for (int mt = 0; mt < MTS; ++mt) {
+#pragma unroll
+            for (int c = 0; c < NCH; ++c) {
+                const int valid = kbytes - (c * 64 + ((l >> 4) << 4));
+                uint4 v = x.v[mt][c];
+                v.x = valid > 0 ? v.x : 0u; v.y = valid > 4 ? v.y : 0u; v.z = valid > 8 ? v.z : 0u; v.w = valid > 12 ? v.w : 0u;
+                x.v[mt][c] = v;
+            }
+        }
+    };
+    // the lane's quad i of a column block: columns i * 16 + (l >> 4) * 4 ..+3 of row l & 15
+    const long lde = EXT == 1 ? a.ldaux : a.ldr;
+    const char* ebase = EXT == 1 ? a.aux : reinterpret_cast<const char*>(a.residual);
+    auto quad_ok = [&](int j, int i, int l) { return j < NB - 1 || j * 64 + i * 16 + ((l >> 4) << 2) < ncols; };
+    auto fetch_e = [&](ESet& e, int s, int j) {           // row-dependent operand of column block j (a quad past N reads the block's first)
+#pragma unroll
+        for (int mt = 0; mt < MTS; ++mt) {
+            const char* src = ebase + ((long)(s * ROWS + mt * 16) * lde + n_blk + j * 64) * ESZ;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const unsigned off = ((unsigned)(l & 15) * (unsigned)lde + (quad_ok(j, i, l) ? (unsigned)(i * 16 + ((l >> 4) << 2)) : 0u)) * ESZ;
+                if constexpr (EXT == 1) {
+                    const uint2 t = *reinterpret_cast<const uint2*>(src + off);
+                    e.v[mt][i].x = t.x; e.v[mt][i].y = t.y;
+                } else {
+                    e.v[mt][i] = *reinterpret_cast<const uint4*>(src + off);
+                }
+            }
+        }
+    };
+    // Row scales: ONE unconditional load per 16 rows whether the launch has row scales or not (without them it reads the first
+    // residual word, and 1.0 is selected where the value is used) -- a load under a test of a.rowscale is waited for at the join.
+    const bool has_rs = a.rowscale != nullptr;
+    const float* rsp = has_rs ? a.rowscale : a.residual;
+    const unsigned rs_div = has_rs ? (unsigned)max(a.rows_per_scale, 1) : 0x80000000u;
+    auto fetch_rs = [&](ESet& e, int s) {
+#pragma unroll
+        for (int mt = 0; mt < MTS; ++mt) e.rs[mt] = rsp[(unsigned)(s * ROWS + mt * 16 + (l & 15)) / rs_div];
+    };
+    // pin: what was requested has arrived HERE -- behind the strip's stores ("memory": the statement stays below them), not at a
+    // first use that the loop's entry path shares or that the scheduler is free to lift above the stores
+    auto pin_x = [&](XSet& x) {
+#pragma unroll
+        for (int mt = 0; mt < MTS; ++mt) {
+#pragma unroll
+            for (int c = 0; c < NCH; ++c) asm volatile("" : "+v"(x.v[mt][c].x), "+v"(x.v[mt][c].y), "+v"(x.v[mt][c].z), "+v"(x.v[mt][c].w) : : "memory");
+        }
+    };
+    auto pin_e = [&](ESet& e) {
+#pragma unroll
+        for (int mt = 0; mt < MTS; ++mt) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                if constexpr (EXT == 1) asm volatile("" : "+v"(e.v[mt][i].x), "+v"(e.v[mt][i].y) : : "memory");
+                else asm volatile("" : "+v"(e.v[mt][i].x), "+v"(e.v[mt][i].y), "+v"(e.v[mt][i].z), "+v"(e.v[mt][i].w) : : "memory");
+            }
+            if constexpr (EXT == 2) asm volatile("" : "+v"(e.rs[mt]) : : "memory");
+        }
+    };
+    // l (block_mma, block_out): the lane number behind a per-block compiler barrier -- the LDS addresses of a block (one per
+    // fragment: the swizzle is not affine in the block) are a few VALU operations each, and hoisted out of the strip loop for
+    // all NB blocks they cost more registers than the kernel has
+    auto block_mma = [&](f32x4 (&acc)[4][MTS], const XSet& x, int j, int l) {
+        zero_acc(acc);
+#pragma unroll
+        for (int c = 0; c < NCH; ++c) {
+            uint4 af[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int row = j * 64 + i * 16 + (l & 15);
+                af[i] = *reinterpret_cast<const uint4*>(smem + row * RL + ((c * 64 + ((l >> 4) << 4)) ^ swz(row)));
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+#pragma unroll
+                for (int mt = 0; mt < MTS; ++mt) mma_chunk<T>(acc[i][mt], af[i], x.v[mt][c]);
+            }
+        }
+    };
+    auto block_out = [&](const f32x4 (&acc)[4][MTS], const ESet& e, int s, int j, int l) {
+        if constexpr (EXT == 0) {
+            // 16 x 64 sub-tiles through the wave's own LDS region, out as 128-byte row segments.  In the panel's last block a lane
+            // whose 8 columns lie past N takes the last valid 16-byte chunk instead: it repeats a neighbour's store (same address,
+            // same bytes), so the store needs no lane test and the compiler's count of the stores in flight stays exact.
+            char* mine = smem + (size_t)bnp * RL + (size_t)bnp * 4 + wave * (16 * EPI_LD);
+            const int chunk = j == NB - 1 ? min(l & 7, ((ncols - j * 64) >> 3) - 1) : (l & 7);
+            const int rsub = l >> 3, cb = chunk * 16;
+            const unsigned coff = ((unsigned)rsub * (unsigned)a.ldc + (unsigned)chunk * 8u) * 2u;
+#pragma unroll
+            for (int mt = 0; mt < MTS; ++mt) {
+                char* rowp = mine + (l & 15) * EPI_LD + ((l >> 4) << 3);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const f32x4 v = acc[i][mt] + *reinterpret_cast<const f32x4*>(sbias + j * 64 + i * 16 + ((l >> 4) << 2));
+                    *reinterpret_cast<uint2*>(rowp + i * 32) = make_uint2(pack_bf2(v[0], v[1]), pack_bf2(v[2], v[3]));
+                }
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll
+                for (int it = 0; it < 2; ++it) {
+                    const uint4 v = *reinterpret_cast<const uint4*>(mine + (it * 8 + rsub) * EPI_LD + cb);
+                    char* cp = a.C + ((long)(s * ROWS + mt * 16 + it * 8) * a.ldc + n_blk + j * 64) * 2;
+                    *reinterpret_cast<uint4*>(cp + coff) = v;
+                }
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");          // the region is rewritten by the next 16 rows
+                __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+            }
+        } else {
+#pragma unroll
+            // A quad past N (last block only) repeats the lane's own first quad of the block -- same address, same bytes; launch_stream
+            // sees to it that the last block has 16 columns -- so that no store stands under a lane test (see EXT 0 above).
+            for (int mt = 0; mt < MTS; ++mt) {
+                char* cp = a.C + ((long)(s * ROWS + mt * 16) * a.ldc + n_blk + j * 64) * ESZ;
+                unsigned coff0 = 0;
+                uint2 pk0 = make_uint2(0u, 0u);
+                float v0[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const int nq = j * 64 + i * 16 + ((l >> 4) << 2);
+                    unsigned coff = ((unsigned)(l & 15) * (unsigned)a.ldc + (unsigned)(i * 16 + ((l >> 4) << 2))) * ESZ;
+                    const bool ok = j < NB - 1 || i == 0 || quad_ok(j, i, l);
+                    const f32x4 b = *reinterpret_cast<const f32x4*>(sbias + nq);
+                    const uint4 ex = e.v[mt][i];
+                    float v[4];
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) v[r] = acc[i][mt][r] + b[r];
+                    if constexpr (EXT == 1) {
+                        v[0] *= gelu_grad_t<T>(__uint_as_float(ex.x << 16)); v[1] *= gelu_grad_t<T>(__uint_as_float(ex.x & 0xffff0000u));
+                        v[2] *= gelu_grad_t<T>(__uint_as_float(ex.y << 16)); v[3] *= gelu_grad_t<T>(__uint_as_float(ex.y & 0xffff0000u));
+                        uint2 pk = make_uint2(pack_bf2(v[0], v[1]), pack_bf2(v[2], v[3]));
+                        if (i == 0) { pk0 = pk; coff0 = coff; }
+                        pk.x = ok ? pk.x : pk0.x; pk.y = ok ? pk.y : pk0.y; coff = ok ? coff : coff0;
+                        *reinterpret_cast<uint2*>(cp + coff) = pk;
+                    } else {
+                        // the product and the sum are rounded separately, as in epi_apply (two statements under their own tests)
+                        const float rr[4] = {__uint_as_float(ex.x), __uint_as_float(ex.y), __uint_as_float(ex.z), __uint_as_float(ex.w)};
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) v[r] = __fadd_rn(__fmul_rn(v[r], has_rs ? e.rs[mt] : 1.0f), rr[r]);
+                        if (i == 0) { coff0 = coff; v0[0] = v[0]; v0[1] = v[1]; v0[2] = v[2]; v0[3] = v[3]; }
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) v[r] = ok ? v[r] : v0[r];
+                        coff = ok ? coff : coff0;
+                        *reinterpret_cast<f32x4*>(cp + coff) = f32x4{v[0], v[1], v[2], v[3]};
+                    }
+                }
+            }
+        }
+    };
+    // Per strip: request strip s + 1 (X, first block's operands, row scales), compute and store strip s, and only then touch what
+    // was requested -- the wait sits BEHIND the stores of strip s, on the one path that issued them.  (At the head of the loop it
+    // would be shared with the entry path, where no store follows the loads, and the compiler would have to emit vmcnt(0).)
+    XSet xc, xn;
+    ESet ec, en;
+    issue_x(xc, strip);
+    if constexpr (EXT != 0) fetch_e(ec, strip, 0);
+    if constexpr (EXT == 2) fetch_rs(ec, strip);
+    mask_x(xc);
+    if constexpr (EXT != 0) pin_e(ec);                    // nothing in flight at the loop's entry: its waits are those of the back edge
+    auto strip_blocks = [&](int s) {
+        asm volatile("" ::: "memory");                    // the W fragments are re-read from LDS every strip, not kept in registers
+#pragma unroll
+        for (int j = 0; j < NB; ++j) {
+            f32x4 acc[4][MTS];
+            int lj = l;
+            asm volatile("" : "+v"(lj));
+            block_mma(acc, xc, j, lj);
+            ESet ea;
+            if constexpr (EXT != 0) { if (j + 1 < NB) fetch_e(ea, s, j + 1); }
+            if constexpr (EXT == 2) { ea.rs[0] = ec.rs[0]; ea.rs[1] = ec.rs[1]; }
+            block_out(acc, ec, s, j, lj);
+            if constexpr (EXT != 0) { if (j + 1 < NB) ec = ea; }
+        }
+    };
+#pragma unroll 1
+    for (; strip + stride < full; strip += stride) {
+        issue_x(xn, strip + stride);
+        if constexpr (EXT != 0) fetch_e(en, strip + stride, 0);
+        if constexpr (EXT == 2) fetch_rs(en, strip + stride);
+        strip_blocks(strip);
+        __builtin_amdgcn_sched_barrier(0);                // the scheduler would lift the masking -- and with it the wait -- above the last block's stores
+        pin_x(xn);
+        xc = xn;
+        mask_x(xc);
+        if constexpr (EXT != 0) { ec = en; pin_e(ec); }
+    }
+    strip_blocks(strip);                                  // the wave's last full strip: nothing left to request
+    return strip + stride;
+}
+
+// hot: launch_stream found one of the three forms above; the wave's full strips go through stream_hot_strips
 template <typename T, int NCH, bool WT, int EXT>        // EXT: 0 no row-dependent epilogue operand, 1 GELU' input (T), 2 f32 residual
-__global__ __launch_bounds__(512, (NCH == 2 && !EXT) ? 4 : 2) void gemm_stream_kernel(GemmArgs a, int bnp) {   // 2nd argument: waves per SIMD (2 workgroups per CU = 4)
+__global__ __launch_bounds__(512, (NCH == 2 && !EXT) ? 4 : 2) void gemm_stream_kernel(GemmArgs a, int bnp, int hot) {   // 2nd argument: waves per SIMD (2 workgroups per CU = 4)
     constexpr int SZ = TT<T>::SZ, E = TT<T>::E16;
     constexpr int RL = NCH * 64;                          // bytes of K per LDS row (NCH even: whole 128-byte swizzle groups)
     // rows per strip = 16 * MTS.  A wave has ONE strip's loads in flight: 32-row strips of a K <= 128 operand are 2-8 KB per wave, and with
     // the stores removed the kernel still read at only 2.2 TB/s (tools/stream_gemm_bench.py) -- 64-row strips double the bytes in flight
     constexpr int MTS = STREAM_MTS(NCH, EXT);
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int l = lane_id(), wave = threadIdx.x >> 6;
+    int l = lane_id();
+    const int wave = threadIdx.x >> 6;
     const int n_blk = blockIdx.y * bnp;
     const int kbytes = a.K * SZ;
 
@@ -1607,8 +1846,24 @@ __global__ __launch_bounds__(512, (NCH == 2 && !EXT) ? 4 : 2) void gemm_stream_k
     // operand (EXT) the epilogue issues no global load at all and its stores never block the wave.
     const float* sbias = reinterpret_cast<const float*>(smem + (size_t)bnp * RL);
     int strip = blockIdx.x * 8 + wave;
+    if constexpr (sizeof(T) == 2 && STREAM_HOT(NCH, EXT)) {
+        const int full = a.M / (16 * MTS);                // strips with every row inside M
+        if (hot && strip < full) {
+            switch (nnb) {                                // column blocks of this panel: unrolled in the hot loop
+            case 1: strip = stream_hot_strips<NCH, EXT, 1>(a, smem, bnp, n_blk, strip, stride, full); break;
+            case 2: strip = stream_hot_strips<NCH, EXT, 2>(a, smem, bnp, n_blk, strip, stride, full); break;
+            case 3: strip = stream_hot_strips<NCH, EXT, 3>(a, smem, bnp, n_blk, strip, stride, full); break;
+            case 4: strip = stream_hot_strips<NCH, EXT, 4>(a, smem, bnp, n_blk, strip, stride, full); break;
+            default: break;                               // wider panels keep the generic loop
+            }
+        }
+        // what the generic loop derives from the lane number is computed from here on, not held in registers across the hot loop
+        asm volatile("" : "+v"(l));
+    }
+    // ---- the generic loop: every other epilogue form, the f32 instantiations, and the ragged last strip of a hot launch -------
     if (strip < strips) issue_x(strip);
     for (; strip < strips; strip += stride) {
+        asm volatile("" : "+v"(l));                       // per-lane offsets: a few VALU operations per strip, not registers held (and spilt) around the loop
         mask_x(strip);
         const int m_lane = strip * (16 * MTS) + (l & 15);
         float rs[MTS];
@@ -1617,7 +1872,9 @@ __global__ __launch_bounds__(512, (NCH == 2 && !EXT) ? 4 : 2) void gemm_stream_k
             const int m = m_lane + mt * 16;
             rs[mt] = a.rowscale ? a.rowscale[(m < a.M ? m : a.M - 1) / a.rows_per_scale] : 1.0f;
         }
-        if constexpr (EXT == 1 && NCH <= 4) {
+        if constexpr (EXT == 1 && NCH <= 4 && sizeof(T) == 4) {
+            // (f32 operands only: the bf16 launches of a training step take stream_hot_strips, what is left of them comes through the plain
+            // loop below, and this form's two operand sets cost the bf16 instantiations 32 bytes of scratch per lane)
             // GELU' input of the fc2 input gradients: its loads for column block nb + 1 are issued BEFORE block nb is applied and
             // stored (two register sets, two blocks per loop trip).  Fetched and consumed inside the same block, every (block,
             // 16-row group) exposed one full memory latency -- 14 per strip at N = 448 -- and the waves of this variant sat in
@@ -1721,7 +1978,9 @@ __global__ __launch_bounds__(512, (NCH == 2 && !EXT) ? 4 : 2) void gemm_stream_k
                             for (int it = 0; it < 2; ++it) {
                                 const int r = it * 8 + rsub, m = strip * (16 * MTS) + mt * 16 + r;
                                 const uint4 v = *reinterpret_cast<const uint4*>(mine + r * EPI_LD + cb);
-                                if ((a.dbg & 1) && v.x != 0x12345678u) continue;
+#ifdef FW_STREAM_DBG
+                                if ((a.dbg & 1) && v.x != 0x12345678u) continue;                       // measurement only: no stores
+#endif
                                 if (m < a.M && ncol < a.N) *reinterpret_cast<uint4*>(a.C + ((long)m * a.ldc + ncol) * 2) = v;
                             }
                             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
@@ -1748,7 +2007,9 @@ __global__ __launch_bounds__(512, (NCH == 2 && !EXT) ? 4 : 2) void gemm_stream_k
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
                         const int n0 = n_blk + nb * 64 + i * 16 + ((l >> 4) << 2);
+#ifdef FW_STREAM_DBG
                         if ((a.dbg & 1) && acc[i][mt][0] != 12345.678f) continue;          // measurement only: no stores
+#endif
                         if (m < a.M && n0 < a.N) epi_apply<T>(a, *reinterpret_cast<const f32x4*>(sbias + (n0 - n_blk)), ext[i], acc[i][mt], m, n0, rs[mt], 0);
                     }
                 }
@@ -1768,12 +2029,37 @@ int launch_stream(const GemmArgs& a, hipStream_t st) {
     const int bnp = fw_cdiv(fw_cdiv(a.N, ny), 64) * 64;
     const size_t lds = (size_t)bnp * RL + (size_t)bnp * 4 + stage_b;       // W panel + bias of its columns (+ the staging regions)
     FW_SET_LDS_ONCE((gemm_stream_kernel<T, NCH, WT, EXT>), 80 * 1024);
+    // the forms with a loop of their own (stream_hot_strips): what a training step sends here.  NOT hot, i.e. through the generic
+    // loop as before: every f32 launch; <bf16,8,*,1|2> (STREAM_HOT); EXT 0 that cannot take the staged store (N % 8 != 0 -- the N = 28
+    // input gradients --, ldc % 8 != 0, unaligned C, act 1 / 3, a twin output); EXT 1 / 2 whose last column block has fewer than 16
+    // columns (N % 64 in 4 .. 12); act = 2 together with a residual or a row scale or an f32 output; f32 output without a residual;
+    // alpha != 1; a leading dimension >= 2^24; and, decided in the kernel, a panel of more than 4 column blocks (N > 256 at K <= 64).
+    int hot = 0;
+    constexpr long LD_MAX = 1L << 24;                               // the hot loop's 32-bit lane offsets
+    const bool tail16 = a.N % 64 == 0 || a.N % 64 >= 16;             // EXT 1 / 2: what an unconditional store of the last column block needs
+    if (sizeof(T) == 2 && STREAM_HOT(NCH, EXT) && a.alpha == 1.0f && !a.C2 && !a.accumulate && !a.c_zstride && a.ldx < LD_MAX && a.ldc < LD_MAX && a.ldaux < LD_MAX && a.ldr < LD_MAX) {
+        if (EXT == 0) hot = stg;
+        if (EXT == 1) hot = tail16 && a.act == 2 && !a.out_f32 && !a.rowscale && !a.residual;
+        if (EXT == 2) hot = tail16 && a.act == 0 && a.out_f32 && a.residual != nullptr;
+    }
+#ifdef FW_STREAM_DBG
+    if (a.dbg) hot = 0;                                             // the measurement switches live in the generic loop
+#endif
     const int strips = fw_cdiv(a.M, 16 * STREAM_MTS(NCH, EXT));
     int gx = fw_cdiv(strips, 8);
-    const int cap = 512 / ny > 0 ? 512 / ny : 1;                    // 256 CUs x 2 workgroups
+    // every launched workgroup is resident: workgroups per CU as the compiled instantiation allows.  Asked once, with the 80 KB of
+    // dynamic LDS the kernel is set up for and not this launch's (smaller) `lds`: never more workgroups than fit, at most too few
+    static const int resident = [] {
+        int per_cu = 0, dev = 0;
+        hipDeviceProp_t prop;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, gemm_stream_kernel<T, NCH, WT, EXT>, 512, 80 * 1024) != hipSuccess || per_cu < 1) per_cu = 1;
+        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return 256 * per_cu;
+        return prop.multiProcessorCount * per_cu;
+    }();
+    const int cap = resident / ny > 0 ? resident / ny : 1;
     if (gx > cap) gx = cap;
     FW_KNAME("gemm_stream_kernel<%s,%d,%s,%d>", tname<T>(), NCH, FW_B(WT), EXT);
-    hipLaunchKernelGGL((gemm_stream_kernel<T, NCH, WT, EXT>), dim3(gx, ny), dim3(512), lds, st, a, bnp);
+    hipLaunchKernelGGL((gemm_stream_kernel<T, NCH, WT, EXT>), dim3(gx, ny), dim3(512), lds, st, a, bnp, hot);
     FW_LAUNCH_RET();
 }
 

@@ -1,13 +1,28 @@
 #!/usr/bin/env python3
 """Tall-skinny GEMM shapes of the C <= 112 stages (gemm_stream_kernel): time per launch on cold operands (8 sets in a captured graph),
-GB/s of algorithmic bytes.  FW_GEMM_BIG_DBG=1 skips the epilogue's stores (what is left is loads + MFMA)."""
+TB/s of algorithmic bytes, and a SHA-256 of the first set's output (seeded operands: two builds that compute the same thing print
+the same hashes).
+
+  --pkg DIR     the package tree whose libfwair_hip.so is measured (default: this checkout's); e.g. a build of the parent commit
+  --json FILE   also write the rows as JSON, labelled --label
+
+The switch that skips the epilogue's stores (FW_GEMM_BIG_DBG=1: what is left is loads + MFMA) is compiled into this kernel only
+with -DFW_STREAM_DBG (HIPCC flags in build.sh); such a build sends every launch through the kernel's generic loop."""
+import argparse
+import hashlib
+import json
 import os
 import sys
 
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, os.path.join(ROOT, 'frequency-wised_all-in-one_image_restoration_model_amd'))
+ap = argparse.ArgumentParser()
+ap.add_argument('--pkg', default=os.path.join(ROOT, 'frequency-wised_all-in-one_image_restoration_model_amd'))
+ap.add_argument('--json', default=None)
+ap.add_argument('--label', default='')
+args = ap.parse_args()
+sys.path.insert(0, os.path.abspath(args.pkg))
 from fwair import ops  # noqa: E402
 
 dev, bf = 'cuda', torch.bfloat16
@@ -21,7 +36,8 @@ def ld8(n):
 
 
 def run(M, N, K, kind, reps=8):
-    sets = []
+    torch.manual_seed(M + 1000 * N + K)
+    sets, outs = [], []
     for _ in range(reps):
         if kind in ('plain', 'res'):
             x = (torch.randn(M, ld8(K), device=dev) * 0.5).to(bf)[:, :K]
@@ -31,15 +47,18 @@ def run(M, N, K, kind, reps=8):
                 res = torch.randn(M, N, device=dev)
                 y = torch.empty(M, N, device=dev)
                 sets.append(lambda x=x, w=w, b=b, y=y, res=res: ops.gemm(x, w, M, N, K, out=y, bias=b, residual=res))
+                outs.append(y)
             else:
                 y = torch.empty(M, ld8(N), device=dev, dtype=bf)[:, :N]
                 sets.append(lambda x=x, w=w, b=b, y=y: ops.gemm(x, w, M, N, K, out=y, bias=b))
+                outs.append(y)
         else:
             dy = (torch.randn(M, ld8(K), device=dev) * 0.5).to(bf)[:, :K]
             w = (torch.randn(K, ld8(N), device=dev) * 0.05).to(bf)[:, :N]
             out = torch.empty(M, ld8(N), device=dev, dtype=bf)[:, :N]
             aux = torch.randn(M, ld8(N), device=dev).to(bf)[:, :N] if kind.startswith('dgelu') else None
             sets.append(lambda dy=dy, w=w, out=out, aux=aux: ops.gemm(dy, w, M, N, K, w_trans=True, out=out, act=2 if aux is not None else 0, aux=aux))
+            outs.append(out)
     side = torch.cuda.Stream()
     with torch.cuda.stream(side):
         for f in sets:
@@ -56,14 +75,19 @@ def run(M, N, K, kind, reps=8):
             g.replay()
         e1.record(side)
         torch.cuda.synchronize()
-    return e0.elapsed_time(e1) * 1e-3 / (3 * reps)
+    digest = hashlib.sha256(outs[0].contiguous().cpu().view(torch.uint8).numpy().tobytes()).hexdigest()
+    return e0.elapsed_time(e1) * 1e-3 / (3 * reps), digest
 
 
 if __name__ == '__main__':
-    tot = 0.0
+    tot, rows = 0.0, []
     for M, N, K, kind in SHAPES:
-        t = run(M, N, K, kind)
+        t, digest = run(M, N, K, kind)
         tot += t
         by = M * K * 2 + (M * N * 4 * 2 if kind == 'res' else M * N * 2) + (M * N * 2 if kind.startswith('dgelu') else 0)
-        print(f'{kind:9s} M={M:7d} N={N:4d} K={K:4d}  {t * 1e6:8.1f} us  {by / t / 1e12:5.2f} TB/s')
+        print(f'{kind:9s} M={M:7d} N={N:4d} K={K:4d}  {t * 1e6:8.1f} us  {by / t / 1e12:5.2f} TB/s  {digest[:16]}', flush=True)
+        rows.append({'kind': kind, 'M': M, 'N': N, 'K': K, 'us': round(t * 1e6, 2), 'tb_per_s': round(by / t / 1e12, 3), 'sha256': digest})
     print(f'sum {tot * 1e6:.1f} us')
+    if args.json:
+        with open(args.json, 'w') as f:
+            json.dump({'label': args.label, 'sum_us': round(tot * 1e6, 1), 'shapes': rows}, f, indent=1)
