@@ -209,6 +209,8 @@ class DecLeWinTransformerBlock(nn.Module):
             raise NotImplementedError('feature maps smaller than one 8x8 window')
         self.debug_mode = bool(debug_mode)
         if self.debug_mode:                                                     # :518-519 (no parameters, no buffers: same state_dict)
+            # stage maps of a 384-pixel model (384, 192, 96, 48, 24): 96 / 48 / 24 are sides FrequencyDecompose does not take and the
+            # constructor raises its NotImplementedError; at 128 / 256 / 512 every stage side is covered
             from net.utils.frequency_decompose import FrequencyDecompose
             self.visual_decompose = FrequencyDecompose('frequency_decompose', 1, input_resolution[0], input_resolution[1], inverse='visual')
         self.norm1 = nn.LayerNorm(dim)
@@ -552,7 +554,7 @@ class UformerEncoder(nn.Module):
         img_size = _resolve_img_size(opt, img_size)
         E = opt.encoder_embed_dim
         self.img_size = img_size
-        if not opt.L == 1:
+        if not opt.L == 1:                                  # 128 / 256: the kernels of fw_heads.hip; 384 / 512: the tiled passes of fw_dft.hip
             self.preprocess_decompose = FrequencyDecompose('frequency_decompose_1', 1. / (opt.L - 1), img_size, img_size)
         self.uformer = Uformer(opt, img_size=img_size, in_chans=in_chans)
         self.mlp_head = nn.ModuleList([nn.Sequential(nn.LayerNorm(E * 16), nn.Linear(E * 16, opt.encoder_dim * 16 * 16))

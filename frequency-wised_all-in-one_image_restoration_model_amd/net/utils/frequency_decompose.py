@@ -1,11 +1,13 @@
 """`FrequencyDecompose(type, size, h, w, inverse)` -- drop-in for the reference module of the same name
-(net/utils/frequency_decompose.py:5-125), computed by the HIP partial-DFT kernels (csrc/fw_heads.hip)
-instead of torch.fft.  Same constructor, same output shapes:
+(net/utils/frequency_decompose.py:5-125), computed by the HIP partial-DFT kernels (csrc/fw_heads.hip, and csrc/fw_dft.hip for
+maps larger than 256x256) instead of torch.fft.  Same constructor, same output shapes:
     'frequency_decompose'   bands [0,s) ... [1-s,1]          -> [nb,   B, C, h, w]
     'frequency_decompose_1' DC, (0,s] ... (1-s,1]            -> [nb+1, B, C, h, w]
     'frequency_decompose_dc' mean / residual                 -> [2,    B, C, h, w]
     inverse=False -> [..., 2] (re, im) of the masked, un-shifted spectrum;  inverse='visual' -> magnitudes.
-Square power-of-two maps up to 256x256 (the model uses 128, or 256 with --patch_size 256); anything else raises NotImplementedError.
+Square maps: a power of two from 8 to 256 (the model uses 128, or 256 with --patch_size 256), or a multiple of 64 from 192 to 512
+on the tiled f32-MFMA passes (384 and 512 with --patch_size 384 / 512; work buffers are allocated per call, which a graph capture
+tolerates).  A power of two up to 256 keeps the kernels of fw_heads.hip.  Anything else raises NotImplementedError.
 """
 import math
 
@@ -28,11 +30,53 @@ def _dft_panels(N, device):
     return _panels[key]
 
 
+ACCEPTED_SIDES = 'a power of two in [8, 256] or a multiple of 64 in [192, 512]'
+
+
+def _pow2_side(N):
+    return 8 <= N <= 256 and N & (N - 1) == 0
+
+
+def _tiled_side(N):
+    """Sides that take the tiled passes of csrc/fw_dft.hip (256 stays on the kernels of fw_heads.hip)."""
+    return N % 64 == 0 and 192 <= N <= 512 and not _pow2_side(N)
+
+
+def _work(x, nfloat):
+    return torch.empty((nfloat,), dtype=torch.float32, device=x.device)
+
+
+def _inverse_tiled(fr, fi, mask, out, n, N, nb, mode):
+    """fw_dft2t_bands with its per-call work buffer (mode 0: 2 * nb * n * N * N floats)."""
+    if mode == 0:
+        call('fw_dft2t_bands', fr, fi, mask, _dft_panels(N, fr.device), _work(fr, 2 * nb * n * N * N), out, n, N, nb, 0)
+    else:
+        call('fw_dft2t_bands', fr, fi, mask, None, None, out, n, N, nb, mode)
+
+
+def _bands_tiled(x, mask, mode, partition, dc_bits):
+    n, N = x.shape[0], x.shape[1]
+    nb = mask.shape[0]
+    panels = _dft_panels(N, x.device)
+    if mode == 0 and partition and nb >= 2:
+        out = torch.empty((nb, n, N, N), dtype=torch.float32, device=x.device)
+        call('fw_dft2t_decompose', x, mask, panels, _work(x, (2 + 2 * nb) * n * N * N), out, n, N, nb, int(dc_bits))
+        return out
+    fr = torch.empty((n, N, N), dtype=torch.float32, device=x.device)
+    fi = torch.empty_like(fr)
+    call('fw_dft2t_fwd', x, panels, _work(x, 2 * n * N * N), fr, fi, n, N)
+    out = torch.empty((nb, n, N, N, 2) if mode == 1 else (nb, n, N, N), dtype=torch.float32, device=x.device)
+    _inverse_tiled(fr, fi, mask, out, n, N, nb, mode)
+    return out
+
+
 def _bands(x, mask, mode, partition=False, dc_bits=0):
     """x: f32 [n, N, N] -> mode 0: Re IDFT2(mask_b * DFT2 x) [nb, n, N, N];  mode 1: (re, im) of mask_b * DFT2 x [nb, n, N, N, 2];
     mode 2: |.| in fftshift-ed coordinates."""
     n, N = x.shape[0], x.shape[1]
     nb = mask.shape[0]
+    if _tiled_side(N):
+        return _bands_tiled(x, mask, mode, partition, dc_bits)
     if mode == 0 and partition and nb >= 2 and N in (64, 128):
         # the band masks partition the spectrum: the whole decomposition in one launch on the f32 MFMA (csrc/fw_heads.hip)
         out = torch.empty((nb, n, N, N), dtype=torch.float32, device=x.device)
@@ -80,7 +124,10 @@ class _BandsFn(torch.autograd.Function):
             gi = (dout[..., 1] * m).sum(0).contiguous()
             ones = torch.ones((1, N, N), dtype=torch.float32, device=dout.device)
             out = torch.empty((1, n, N, N), dtype=torch.float32, device=dout.device)
-            call('fw_dft2_bands', gr, gi, ones, out, n, N, 1, 0)             # Re IDFT2 (already divided by N^2)
+            if _tiled_side(N):
+                _inverse_tiled(gr, gi, ones, out, n, N, 1, 0)
+            else:
+                call('fw_dft2_bands', gr, gi, ones, out, n, N, 1, 0)         # Re IDFT2 (already divided by N^2)
             return out[0] * float(N * N), None, None
         raise NotImplementedError("FrequencyDecompose(inverse='visual') is a magnitude plot, not a differentiable output")
 
@@ -94,8 +141,8 @@ class FrequencyDecompose(nn.Module):
         self._partition = False
         self._dc_bits = 0
         if self.type in ['frequency_decompose', 'frequency_decompose_1']:
-            if h != w or h & (h - 1) or not 8 <= h <= 256:
-                raise NotImplementedError('HIP band decomposition handles square power-of-two maps, 8 <= N <= 256')
+            if h != w or not (_pow2_side(h) or _tiled_side(h)):
+                raise NotImplementedError('HIP band decomposition handles square maps whose side is %s, not %sx%s' % (ACCEPTED_SIDES, h, w))
             self.num_bands = math.floor(1. / self.size + 0.1)
 
     def _mask(self, device):

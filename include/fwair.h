@@ -175,6 +175,20 @@ int fw_dft2_decompose(const float* img, const float* mask, const float* panels, 
  * ([nbands][nimg][N][N], filled by fw_dft2_bands called with nbands-1).  Saves one masked inverse transform per image. */
 int fw_band_residual(const float* img, float* out, int nimg, int N, int nbands, void* stream);
 int fw_dc_split(const float* img, float* out, int nimg, int NN, void* stream);
+/* The same three roles for maps larger than one CU's LDS (--patch_size 384 / 512; frequency_decompose.py:28-118 at those sizes):
+ * square maps, N a multiple of 64 in [192, 512] (256 included, for comparison with the entries above), as passes of tiled f32-MFMA
+ * products over the caller's work buffer.  panels as for fw_dft2_decompose.  No global state; every launch goes to `stream`.
+ *   fw_dft2t_fwd        replaces torch.fft.fft2 (frequency_decompose.py:28-32): the contract of fw_dft2_fwd.
+ *                       work: 2 * nimg * N * N floats.
+ *   fw_dft2t_bands      replaces the mask / ifft2 loop (frequency_decompose.py:47-60,70-118): the contract of fw_dft2_bands.
+ *                       mode 0 work: 2 * nbands * nimg * N * N floats; modes 1 and 2 read neither work nor panels (may be NULL).
+ *   fw_dft2t_decompose  replaces the whole frequency_decompose_1 pre-processing (encoder_Uformer.py:964-966): the contract of
+ *                       fw_dft2_decompose, dc_bits included.  work: (2 + 2 * nbands) * nimg * N * N floats. */
+int fw_dft2t_fwd(const float* img, const float* panels, float* work, float* fr, float* fi, int nimg, int N, void* stream);
+int fw_dft2t_bands(const float* fr, const float* fi, const float* mask_unshifted, const float* panels, float* work, float* out,
+                   int nimg, int N, int nbands, int mode, void* stream);
+int fw_dft2t_decompose(const float* img, const float* mask, const float* panels, float* work, float* out, int nimg, int N,
+                       int nbands, int dc_bits, void* stream);
 
 /* ---- encoder contrastive head: BatchNorm2d + LeakyReLU(0.1) + GAP (encoder_Uformer.py:945-951,978-984) -- */
 int fw_bn_lrelu_gap_fwd(int dtype, const void* fea, const float* gamma, const float* beta, float* rmean, float* rvar,
