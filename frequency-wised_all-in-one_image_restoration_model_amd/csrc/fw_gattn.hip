@@ -21,8 +21,10 @@
 // Backward (flash style, deterministic, no atomics on activations): workgroup (image, head, tile t) first acts for QUERY tile t
 // (loops over the key tiles: dQ), then for KEY tile t (loops over the query tiles: dK, dV), recomputing P from the saved
 // log-sum-exp; with NT = 1 both roles share one pass.
-// Any other N = 64 nt up to 1024 (N = 576 at 384x384, 1024 at 512x512; plain attention + Dropout, no lamb): gattn_stream_fwd_kernel
-// walks the key tiles with an online softmax, and the backward body runs with a run-time tile count (NT = 0).
+// Any other N = 64 nt up to 1024 (N = 576 at 384x384, 1024 at 512x512): gattn_stream_fwd_kernel walks the key tiles with an online
+// softmax, and the backward body runs with a run-time tile count (NT = 0).  The band re-weighting with N x N masks exists there at
+// N = 576 and N = 1024 only: 'DC' as a second, unrescaled accumulator of the streaming forward (the affine form of N = 256), <n>_bands
+// as LDS-free 64x64-tile DFT passes between a probabilities and an apply kernel (bandsn_pass_kernel, fw_gattn_bandsn_fwd / bwd).
 #include "fw_common.h"
 
 namespace {
@@ -359,9 +361,12 @@ template <typename T> FW_DEV void stage_write(const StageRegs<T>& s, char* Kt, c
     }
 }
 // one key tile of the online softmax: the lane's (m, l) and O^T accumulators take tile t from the LDS tiles Ks / Vs
-template <typename T>
+// DC ('DC' on the N x N grid at N = 576 / 1024, dc_coef): A' = gain P + offs, and the constant term offs sum_j keep_ij inv_keep v_j
+// does not depend on the running maximum, so a second O^T accumulator o2 takes V against the 0 / 1 keep strip Ps2 unrescaled
+// (Dropout off: the column sum of V); 0 / 1 is exact in T, inv_keep multiplies in f32 at the end.
+template <typename T, bool DC = false>
 FW_DEV void stream_tile(const GAttnArgs& a, const char* Ks, const char* Vs, char* Ps, const uint4 (&qf)[GG<T>::KC], unsigned key,
-                        unsigned long long base, float& m, float& lsum, f32x4 (&o)[4]) {
+                        unsigned long long base, float& m, float& lsum, f32x4 (&o)[4], char* Ps2 = nullptr, f32x4* o2 = nullptr) {
     constexpr int LDR = GG<T>::LDR, KC = GG<T>::KC;
     // S^T tile: s[mt][r] = score(query 16 w + (l & 15), key 64 t + 16 mt + 4 (l >> 4) + r)
     f32x4 s[4];
@@ -385,11 +390,27 @@ FW_DEV void stream_tile(const GAttnArgs& a, const char* Ks, const char* Vs, char
     lsum = lsum * alpha + col_sum(sum);                                // l and O take the same factor; every e_j enters l
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt) o[dt] *= alpha;
-    if (a.thresh) {
+    if constexpr (!DC) {
+        if (a.thresh) {
 #pragma unroll
-        for (int mt = 0; mt < 4; ++mt)
+            for (int mt = 0; mt < 4; ++mt)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) s[mt][r] = fw_keep(key, base + 16 * mt + r, a.thresh) ? s[mt][r] * a.inv_keep : 0.f;
+                for (int r = 0; r < 4; ++r) s[mt][r] = fw_keep(key, base + 16 * mt + r, a.thresh) ? s[mt][r] * a.inv_keep : 0.f;
+        }
+    } else {
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt) {
+            f32x4 kp = f32x4{1.f, 1.f, 1.f, 1.f};
+            if (a.thresh) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const bool keep = fw_keep(key, base + 16 * mt + r, a.thresh);
+                    s[mt][r] = keep ? s[mt][r] * a.inv_keep : 0.f;
+                    kp[r] = keep ? 1.f : 0.f;
+                }
+            }
+            store_acc_T<T>(Ps2, LDR, 16 * mt, 0, kp);
+        }
     }
 #pragma unroll
     for (int mt = 0; mt < 4; ++mt) store_acc_T<T>(Ps, LDR, 16 * mt, 0, s[mt]);
@@ -398,11 +419,21 @@ FW_DEV void stream_tile(const GAttnArgs& a, const char* Ks, const char* Vs, char
 #pragma unroll
     for (int c = 0; c < KC; ++c) {
         const uint4 pf = frag_kc(Ps, LDR, 0, c);
+        if constexpr (!DC) {
 #pragma unroll
-        for (int dt = 0; dt < 4; ++dt) mma_chunk<T>(o[dt], frag_km<T>(Vs, LDR, 16 * dt, c), pf);
+            for (int dt = 0; dt < 4; ++dt) mma_chunk<T>(o[dt], frag_km<T>(Vs, LDR, 16 * dt, c), pf);
+        } else {
+            const uint4 kf = frag_kc(Ps2, LDR, 0, c);
+#pragma unroll
+            for (int dt = 0; dt < 4; ++dt) {
+                const uint4 vf = frag_km<T>(Vs, LDR, 16 * dt, c);
+                mma_chunk<T>(o[dt], vf, pf);
+                mma_chunk<T>(o2[dt], vf, kf);
+            }
+        }
     }
 }
-template <typename T>
+template <typename T, bool DC = false>
 __global__ __launch_bounds__(NTH) void gattn_stream_fwd_kernel(GAttnArgs a) {
     using G = GG<T>;
     constexpr int SZ = G::SZ, LDR = G::LDR, KC = G::KC, TILE = G::TILE;
@@ -411,6 +442,7 @@ __global__ __launch_bounds__(NTH) void gattn_stream_fwd_kernel(GAttnArgs a) {
     char* Kb = Qs + TILE;                                              // K tiles 0 / 1
     char* Vb = Kb + 2 * TILE;                                          // V tiles 0 / 1
     char* Ps = Vb + 2 * TILE + wave_id() * 16 * LDR;                   // the wave's [16 queries][64 keys] of T
+    char* Ps2 = Ps + TILE;                                             // DC: the wave's keep strip
     const int w = wave_id(), l = lane_id();
     const int N = a.N, nt = N >> 6;
     int item = blockIdx.x;
@@ -431,23 +463,35 @@ __global__ __launch_bounds__(NTH) void gattn_stream_fwd_kernel(GAttnArgs a) {
     const unsigned long long row = (unsigned long long)((long)(b * a.heads + h) * N + iq) * (unsigned long long)N + 4 * (l >> 4);
     const unsigned key = a.thresh ? fw_site_key(a.seed[0], a.site) : 0u;
     float m = -3.0e38f, lsum = 0.f;
-    f32x4 o[4];
+    f32x4 o[4], o2[DC ? 4 : 1];
 #pragma unroll
     for (int dt = 0; dt < 4; ++dt) o[dt] = zero4();
+    if constexpr (DC) {
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt) o2[dt] = zero4();
+    }
     for (int t = 0; t + 1 < nt; ++t) {                                 // every tile but the last: tile t + 1 is in flight under tile t
         StageRegs<T> nx;
         stage_request<T>(nx, gk + (long)(t + 1) * 64 * ldb, gv + (long)(t + 1) * 64 * ldb, ldb);
-        stream_tile<T>(a, Kb + (t & 1) * TILE, Vb + (t & 1) * TILE, Ps, qf, key, row + (unsigned long long)t * 64, m, lsum, o);
+        stream_tile<T, DC>(a, Kb + (t & 1) * TILE, Vb + (t & 1) * TILE, Ps, qf, key, row + (unsigned long long)t * 64, m, lsum, o, Ps2, o2);
         stage_write<T>(nx, Kb + ((t + 1) & 1) * TILE, Vb + ((t + 1) & 1) * TILE);               // last read before the previous barrier
         __syncthreads();
     }
     {   // the last tile requests nothing
         const int t = nt - 1;
-        stream_tile<T>(a, Kb + (t & 1) * TILE, Vb + (t & 1) * TILE, Ps, qf, key, row + (unsigned long long)t * 64, m, lsum, o);
+        stream_tile<T, DC>(a, Kb + (t & 1) * TILE, Vb + (t & 1) * TILE, Ps, qf, key, row + (unsigned long long)t * 64, m, lsum, o, Ps2, o2);
     }
     const float inv = 1.0f / lsum;
+    if constexpr (DC) {                                                // out = gain O / l + offs inv_keep O2
+        float gain, offs;
+        dc_coef(a, b, h, gain, offs);
+        gain *= inv; offs *= a.inv_keep;
 #pragma unroll
-    for (int dt = 0; dt < 4; ++dt) o[dt] *= inv;
+        for (int dt = 0; dt < 4; ++dt) o[dt] = o[dt] * gain + o2[dt] * offs;
+    } else {
+#pragma unroll
+        for (int dt = 0; dt < 4; ++dt) o[dt] *= inv;
+    }
     if ((l >> 4) == 0) a.lse[(long)(b * a.heads + h) * N + iq] = m + __logf(lsum);
     char* Os = Qs + 16 * w * LDR;                                      // rows of Q only this wave ever read (qf is in registers)
 #pragma unroll
@@ -593,7 +637,7 @@ FW_DEV void gattn_bwd_body(const GAttnArgs& a) {
     constexpr int SZ = G::SZ, LDR = G::LDR, KC = G::KC, TILE = G::TILE;
     const int nt = NT ? NT : a.N >> 6, N = 64 * nt;                    // NT = 0: run-time tile count, every N = 64 nt without lamb
     static_assert(!LAMB || NT == 1, "the 64x64 transform is defined for N = 64 only");
-    static_assert(DC == V_NONE || (NT == 4 && !LAMB), "the N x N band grid has kernels at N = 256 only");
+    static_assert(DC == V_NONE || ((NT == 4 || NT == 0) && !LAMB), "the N x N band grid: N = 256, or a run-time tile count (576 / 1024)");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* Qs = smem;
     char* dOs = Qs + TILE;
@@ -709,18 +753,20 @@ FW_DEV void gattn_bwd_body(const GAttnArgs& a) {
 }
 template <typename T, int NT, bool LAMB>
 __global__ __launch_bounds__(NTH) void gattn_bwd_kernel(GAttnArgs a) { gattn_bwd_body<T, NT, LAMB, V_NONE>(a); }
-template <typename T>
-__global__ __launch_bounds__(NTH) void gattn_dc_bwd_kernel(GAttnArgs a) { gattn_bwd_body<T, 4, false, V_DC>(a); }
-template <typename T>
-__global__ __launch_bounds__(NTH) void gattn_maps_bwd_kernel(GAttnArgs a) { gattn_bwd_body<T, 4, false, V_MAPS>(a); }
+template <typename T, int NT = 4>                                      // NT = 0: run-time tile count (N = 576 / 1024)
+__global__ __launch_bounds__(NTH) void gattn_dc_bwd_kernel(GAttnArgs a) { gattn_bwd_body<T, NT, false, V_DC>(a); }
+template <typename T, int NT = 4>
+__global__ __launch_bounds__(NTH) void gattn_maps_bwd_kernel(GAttnArgs a) { gattn_bwd_body<T, NT, false, V_MAPS>(a); }
 
 // 'DC' at N = 256, ahead of gattn_dc_bwd_kernel: one workgroup per (image, head, 64-query tile) walks all keys and leaves
 //   dvec[i] = sum_j P[i][j] G[i][j],  G = dropout'(dO V^T);     d lamb0 += sum(G) / N;     d lamb1 += sum(G . P) - sum(G) / N
 // MAPS (<n>_bands): the same walk writes P -> pmap and G -> map2 (f32) for the filter passes instead of reducing them
-template <typename T, bool MAPS>
+// NT = 4: N = 256;  NT = 0: the tile count is a run-time value (N = 576 / 1024)
+template <typename T, bool MAPS, int NT = 4>
 __global__ __launch_bounds__(NTH) void gattn_dc_rows_kernel(GAttnArgs a) {
     using G = GG<T>;
-    constexpr int SZ = G::SZ, LDR = G::LDR, KC = G::KC, N = 256, TILE = G::TILE;
+    constexpr int SZ = G::SZ, LDR = G::LDR, KC = G::KC, TILE = G::TILE;
+    const int nt = NT ? NT : a.N >> 6, N = 64 * nt;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char* Qs = smem;
     char* dOs = Qs + TILE;
@@ -728,7 +774,7 @@ __global__ __launch_bounds__(NTH) void gattn_dc_rows_kernel(GAttnArgs a) {
     char* Vs = Ks + TILE;
     const int w = wave_id(), l = lane_id();
     int item = blockIdx.x;
-    const int t = item % 4; item /= 4;
+    const int t = item % nt; item /= nt;
     const int h = item % a.heads, b = item / a.heads;
     const long ldb = a.ld * SZ, lddob = a.lddo * SZ;
     const long col = (long)h * 64 * SZ;
@@ -739,7 +785,7 @@ __global__ __launch_bounds__(NTH) void gattn_dc_rows_kernel(GAttnArgs a) {
     const float lse = a.lse[rowid];
     const unsigned key = a.thresh ? fw_site_key(a.seed[0], a.site) : 0u;
     float spg = 0.f, sg = 0.f;
-    for (int kj = 0; kj < 4; ++kj) {
+    for (int kj = 0; kj < nt; ++kj) {
         load_tile<T, 64>(Ks, rows(a.k, ldb, kj), ldb);
         load_tile<T, 64>(Vs, rows(a.v, ldb, kj), ldb);
         __syncthreads();
@@ -779,8 +825,8 @@ __global__ __launch_bounds__(NTH) void gattn_dc_rows_kernel(GAttnArgs a) {
     const float tpg = wave_sum(own ? spg : 0.f), tg = wave_sum(own ? sg : 0.f);
     if (l == 0) {
         float* dl = a.dlamb + (long)(a.lamb_batch > 1 ? b : 0) * a.heads + h;
-        atomicAdd(dl, tg * (1.0f / N));
-        atomicAdd(dl + (long)a.lamb_batch * a.heads, tpg - tg * (1.0f / N));
+        atomicAdd(dl, tg * (1.0f / (float)N));
+        atomicAdd(dl + (long)a.lamb_batch * a.heads, tpg - tg * (1.0f / (float)N));
     }
 }
 
@@ -817,6 +863,22 @@ template <typename T> static void launch_stream(const GAttnArgs& a, bool bwd, hi
     const size_t lds = bwd_lds<T>(false);
     FW_SET_LDS_ONCE((gattn_bwd_kernel<T, 0, false>), lds);
     hipLaunchKernelGGL((gattn_bwd_kernel<T, 0, false>), dim3(a.B * a.heads * nt), dim3(NTH), lds, st, a);
+}
+// 'DC' at N = 576 / 1024: the streaming forward with the second (constant-term) accumulator; the rows and backward kernels of N = 256
+// with a run-time tile count
+template <typename T> static void launch_stream_dc(const GAttnArgs& a, bool bwd, hipStream_t st) {
+    const int nt = a.N / 64;
+    if (!bwd) {
+        const size_t lds = (size_t)7 * GG<T>::TILE;
+        FW_SET_LDS_ONCE((gattn_stream_fwd_kernel<T, true>), lds);
+        hipLaunchKernelGGL((gattn_stream_fwd_kernel<T, true>), dim3(a.B * a.heads * nt), dim3(NTH), lds, st, a);
+        return;
+    }
+    const size_t lds_rows = (size_t)4 * GG<T>::TILE, lds = bwd_lds<T>(false);
+    FW_SET_LDS_ONCE((gattn_dc_rows_kernel<T, false, 0>), lds_rows);
+    hipLaunchKernelGGL((gattn_dc_rows_kernel<T, false, 0>), dim3(a.B * a.heads * nt), dim3(NTH), lds_rows, st, a);
+    FW_SET_LDS_ONCE((gattn_dc_bwd_kernel<T, 0>), lds);
+    hipLaunchKernelGGL((gattn_dc_bwd_kernel<T, 0>), dim3(a.B * a.heads * nt), dim3(NTH), lds, st, a);
 }
 // 'DC' at N = 256: the flash-form kernels with the affine re-weighting, no tables and no scratch
 template <typename T> static void launch_dc_fwd(const GAttnArgs& a, hipStream_t st) {
@@ -1085,13 +1147,319 @@ template <typename T> static int bands_bwd(const GAttnArgs& a, float* work, hipS
     hipLaunchKernelGGL((gattn_maps_bwd_kernel<T>), dim3(maps * 4), dim3(NTH), lds, st, a);
     FW_LAUNCH_RET();
 }
+// ================================================================= <n>_bands on the 576x576 / 1024x1024 map (384x384 / 512x512 inputs)
+// The same statement as at N = 256, map += Re IDFT2( W . DFT2(map) ), but a 64 x N f32 strip (256 KB at N = 1024) no longer fits a
+// CU's LDS, so the filter is the LDS-free tile walk of csrc/fw_dft.hip: one pass is one kernel
+//     out[p][d] = sum_k in[d][k] P[k][p],     P = C - iS or its conjugate (symmetric panels: rows p are read k-contiguous),
+// a workgroup (4 waves, 2 x 2) owns one 64 x 64 output tile of one map, both operands are read as ready-made fragments through L2,
+// every product runs on v_mfma_f32_16x16x4_f32, and the result is stored transposed with 16-byte stores:
+//     row pass      T^t[v][i] = sum_j A[i][j]   W[j][v]                  real in
+//     column pass   X[u][v]   = sum_i T^t[v][i] W[i][u];  Y = lamb[band(u, v)] X on the way out
+//                   (backward: the spectrum of P, taken by the same two passes first, gives d lamb[band] = sum Re(X_P conj X_G) / N^2)
+//     inverse pass  Z^t[c][u] = sum_v Y[u][v]   conj(W)[v][c]
+//     output pass   map[r][c] += Re sum_u Z^t[c][u] conj(W)[u][r] / N^2
+// The four partial sums (re C, im S, im C, re S) keep their own accumulators and meet at the end with the signs of W or conj(W), so
+// the cos | sin panels of the N = 256 passes serve unchanged.  The tile walk is generic in N / 64.
+FW_DEV f32x4 gfrag(const float* P, int N, int row0, int c) {              // fragment of a global k-contiguous f32 [.][N] matrix
+    const int l = lane_id();
+    return *reinterpret_cast<const f32x4*>(P + (size_t)(row0 + (l & 15)) * N + c * 16 + ((l >> 4) << 2));
+}
+struct BnFrags { f32x4 ar[2], ai[2], pc[2], ps[2]; };
+template <bool REAL_IN>
+FW_DEV void bn_load(BnFrags& f, const float* xr, const float* xi, const float* Pc, const float* Ps, int N, int d0, int p0, int c) {
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+        f.ar[t] = gfrag(xr, N, d0 + 16 * t, c);
+        if (!REAL_IN) f.ai[t] = gfrag(xi, N, d0 + 16 * t, c);
+        f.pc[t] = gfrag(Pc, N, p0 + 16 * t, c);
+        f.ps[t] = gfrag(Ps, N, p0 + 16 * t, c);
+    }
+}
+#define BN_MFMA(acc, x, y) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(x, y, acc, 0, 0, 0)
+enum { E_PLAIN = 0, E_WEIGHT = 1, E_WEIGHT_DL = 2 };
+// grid (N/64 panel-row tiles, N/64 data-row tiles, maps); 256 threads.  REAL_OUT adds scale * Re(.) to outr (the map) in place.
+// EPI: E_WEIGHT multiplies the result by lamb[band(p, d)]; E_WEIGHT_DL first reduces d lamb against the spectrum (pr, pi) of P.
+template <bool REAL_IN, bool REAL_OUT, bool CONJ, int EPI>
+__global__ __launch_bounds__(NTH) void bandsn_pass_kernel(const float* __restrict__ inr, const float* __restrict__ ini, const float* __restrict__ panels,
+                                                          float* __restrict__ outr, float* __restrict__ outi, int N, float scale,
+                                                          const unsigned char* __restrict__ bandidx, const float* __restrict__ lamb,
+                                                          const float* __restrict__ pr, const float* __restrict__ pi, float* __restrict__ dlamb,
+                                                          int nb, int lb, int heads) {
+    __shared__ float lw[16];
+    __shared__ float red[4][16];
+    const int w = wave_id(), l = lane_id();
+    const int z = blockIdx.z;
+    const size_t NN = (size_t)N * N;
+    const int d0 = blockIdx.y * 64 + (w >> 1) * 32, p0 = blockIdx.x * 64 + (w & 1) * 32;
+    const int h = z % heads, bsel = lb > 1 ? z / heads : 0;
+    if constexpr (EPI != E_PLAIN) {
+        if (threadIdx.x < nb) lw[threadIdx.x] = lamb[((long)threadIdx.x * lb + bsel) * heads + h];
+        __syncthreads();
+    }
+    const float* xr = inr + (size_t)z * NN;
+    const float* xi = REAL_IN ? nullptr : ini + (size_t)z * NN;
+    const float* Pc = panels;
+    const float* Ps = panels + NN;
+    f32x4 rc[2][2], rs[2][2], ic[2][2], is[2][2];                            // sum ar C, sum ai S, sum ai C, sum ar S
+    zero_acc(rc); zero_acc(rs); zero_acc(ic); zero_acc(is);
+    const int KC = N / 16;
+    BnFrags cur, nxt;
+    bn_load<REAL_IN>(cur, xr, xi, Pc, Ps, N, d0, p0, 0);
+    for (int c = 0; c < KC; ++c) {
+        if (c + 1 < KC) bn_load<REAL_IN>(nxt, xr, xi, Pc, Ps, N, d0, p0, c + 1);   // the next chunk's fragments fly under this chunk's MFMAs
+#pragma unroll
+        for (int s = 0; s < 4; ++s)
+#pragma unroll
+            for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+                for (int nt = 0; nt < 2; ++nt) {
+                    BN_MFMA(rc[mt][nt], cur.ar[mt][s], cur.pc[nt][s]);
+                    if (!REAL_OUT) BN_MFMA(is[mt][nt], cur.ar[mt][s], cur.ps[nt][s]);
+                    if (!REAL_IN) {
+                        BN_MFMA(rs[mt][nt], cur.ai[mt][s], cur.ps[nt][s]);
+                        if (!REAL_OUT) BN_MFMA(ic[mt][nt], cur.ai[mt][s], cur.pc[nt][s]);
+                    }
+                }
+        cur = nxt;
+    }
+    // (ar + i ai)(C -/+ iS): re = rc +/- rs, im = ic -/+ is.  acc element r of lane l is out[p = panel row l & 15][d = data row 4 (l >> 4) + r]
+    float bacc[16];
+    if constexpr (EPI == E_WEIGHT_DL) {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) bacc[i] = 0.f;
+    }
+#pragma unroll
+    for (int nt = 0; nt < 2; ++nt)
+#pragma unroll
+        for (int mt = 0; mt < 2; ++mt) {
+            const size_t o = (size_t)(p0 + 16 * nt + (l & 15)) * N + d0 + 16 * mt + ((l >> 4) << 2);
+            f32x4 re = CONJ ? rc[mt][nt] - rs[mt][nt] : rc[mt][nt] + rs[mt][nt];
+            if constexpr (REAL_OUT) {
+                f32x4* dst = reinterpret_cast<f32x4*>(outr + (size_t)z * NN + o);
+                *dst = *dst + re * scale;
+            } else {
+                f32x4 im = CONJ ? ic[mt][nt] + is[mt][nt] : ic[mt][nt] - is[mt][nt];
+                if constexpr (EPI != E_PLAIN) {
+                    const unsigned idx4 = *reinterpret_cast<const unsigned*>(bandidx + o);   // bands of (p, d .. d + 3)
+                    if constexpr (EPI == E_WEIGHT_DL) {
+                        const f32x4 qr = *reinterpret_cast<const f32x4*>(pr + (size_t)z * NN + o);
+                        const f32x4 qi = *reinterpret_cast<const f32x4*>(pi + (size_t)z * NN + o);
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            const unsigned band = (idx4 >> (8 * r)) & 255u;
+                            const float v = qr[r] * re[r] + qi[r] * im[r];
+#pragma unroll
+                            for (int i = 0; i < 16; ++i) bacc[i] += band == (unsigned)i ? v : 0.f;
+                        }
+                    }
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        const float wgt = lw[(idx4 >> (8 * r)) & 15u];
+                        re[r] *= wgt; im[r] *= wgt;
+                    }
+                }
+                *reinterpret_cast<f32x4*>(outr + (size_t)z * NN + o) = re * scale;
+                *reinterpret_cast<f32x4*>(outi + (size_t)z * NN + o) = im * scale;
+            }
+        }
+    if constexpr (EPI == E_WEIGHT_DL) {
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const float t = wave_sum(bacc[i]);
+            if (l == 0) red[w][i] = t;
+        }
+        __syncthreads();
+        if (threadIdx.x < nb) {                                              // one atomic per workgroup and band
+            const int band = threadIdx.x;
+            atomicAdd(dlamb + ((long)band * lb + bsel) * heads + h,
+                      (red[0][band] + red[1][band] + red[2][band] + red[3][band]) / ((float)N * (float)N));
+        }
+    }
+}
+
+// lse and P = exp(s scale - lse) (f32, -> map) of one (image, head, 64-query tile): the key tiles pass by twice, first under the
+// online maximum / sum of the streaming forward, then against the finished lse -- the expression the backward pass rebuilds P with.
+template <typename T>
+__global__ __launch_bounds__(NTH) void gattn_probsn_kernel(GAttnArgs a) {
+    using G = GG<T>;
+    constexpr int SZ = G::SZ, LDR = G::LDR, KC = G::KC, TILE = G::TILE;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    char* Qs = smem;
+    char* Ks = Qs + TILE;
+    const int w = wave_id(), l = lane_id();
+    const int N = a.N, nt = N >> 6;
+    int item = blockIdx.x;
+    const int qt = item % nt; item /= nt;
+    const int h = item % a.heads, b = item / a.heads;
+    const long ldb = a.ld * SZ;
+    const char* gk = a.k + ((long)b * N * a.ld + h * 64) * SZ;
+    load_tile<T, 64>(Qs, a.q + (((long)b * N + qt * 64) * a.ld + h * 64) * SZ, ldb);
+    const int iq = qt * 64 + 16 * w + (l & 15);                        // the lane's query
+    const long rowid = (long)(b * a.heads + h) * N + iq;
+    float m = -3.0e38f, lsum = 0.f, lse = 0.f;
+    for (int pass = 0; pass < 2; ++pass) {
+        for (int t = 0; t < nt; ++t) {
+            load_tile<T, 64>(Ks, gk + (long)t * 64 * ldb, ldb);
+            __syncthreads();
+            uint4 qf[KC];
+#pragma unroll
+            for (int c = 0; c < KC; ++c) qf[c] = frag_kc(Qs, LDR, 16 * w, c);
+            // S^T tile: s[mt][r] = score(query 16 w + (l & 15), key 64 t + 16 mt + 4 (l >> 4) + r)
+            f32x4 s[4];
+            float mx = -3.0e38f;
+#pragma unroll
+            for (int mt = 0; mt < 4; ++mt) {
+                s[mt] = zero4();
+#pragma unroll
+                for (int c = 0; c < KC; ++c) mma_chunk<T>(s[mt], frag_kc(Ks, LDR, 16 * mt, c), qf[c]);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) { s[mt][r] *= a.scale; mx = fmaxf(mx, s[mt][r]); }
+            }
+            if (pass == 0) {
+                const float mn = fmaxf(m, col_max(mx));
+                float sum = 0.f;
+#pragma unroll
+                for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) sum += __expf(s[mt][r] - mn);
+                lsum = lsum * __expf(m - mn) + col_sum(sum);
+                m = mn;
+            } else {
+                float* dst = a.map + rowid * N + t * 64 + 4 * (l >> 4);
+#pragma unroll
+                for (int mt = 0; mt < 4; ++mt) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) s[mt][r] = __expf(s[mt][r] - lse);
+                    *reinterpret_cast<f32x4*>(dst + 16 * mt) = s[mt];
+                }
+            }
+            __syncthreads();
+        }
+        if (pass == 0) {
+            lse = m + __logf(lsum);
+            if ((l >> 4) == 0) a.lse[rowid] = lse;
+        }
+    }
+}
+
+// A' (map, after the filter) -> Dropout with the counter index (b, h, i, j) the backward derives -> O = A'' V, key tile by key tile
+template <typename T>
+__global__ __launch_bounds__(NTH) void gattn_applyn_kernel(GAttnArgs a) {
+    using G = GG<T>;
+    constexpr int SZ = G::SZ, LDR = G::LDR, KC = G::KC, TILE = G::TILE;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    char* Os = smem + wave_id() * 16 * LDR;                            // the wave's 16 output rows
+    char* Vs = smem + TILE;
+    char* Ps = smem + 2 * TILE + wave_id() * 16 * LDR;                 // the wave's [16 queries][64 keys] of T
+    const int w = wave_id(), l = lane_id();
+    const int N = a.N, nt = N >> 6;
+    int item = blockIdx.x;
+    const int qt = item % nt; item /= nt;
+    const int h = item % a.heads, b = item / a.heads;
+    const long ldb = a.ld * SZ;
+    const char* gv = a.v + ((long)b * N * a.ld + h * 64) * SZ;
+    const int iq = qt * 64 + 16 * w + (l & 15);
+    const long rowid = (long)(b * a.heads + h) * N + iq;
+    const unsigned key = a.thresh ? fw_site_key(a.seed[0], a.site) : 0u;
+    f32x4 o[4];
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) o[dt] = zero4();
+    for (int t = 0; t < nt; ++t) {
+        load_tile<T, 64>(Vs, gv + (long)t * 64 * ldb, ldb);
+        const long off = rowid * N + t * 64 + 4 * (l >> 4);
+        f32x4 s[4];
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt) s[mt] = *reinterpret_cast<const f32x4*>(a.map + off + 16 * mt);
+        if (a.thresh) {
+#pragma unroll
+            for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    s[mt][r] = fw_keep(key, (unsigned long long)off + 16 * mt + r, a.thresh) ? s[mt][r] * a.inv_keep : 0.f;
+        }
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt) store_acc_T<T>(Ps, LDR, 16 * mt, 0, s[mt]);
+        __syncthreads();
+        // O^T[d][i] += sum_j V[j][d] A''[i][j]
+#pragma unroll
+        for (int c = 0; c < KC; ++c) {
+            const uint4 pf = frag_kc(Ps, LDR, 0, c);
+#pragma unroll
+            for (int dt = 0; dt < 4; ++dt) mma_chunk<T>(o[dt], frag_km<T>(Vs, LDR, 16 * dt, c), pf);
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) store_acc_T<T>(Os, LDR, 16 * dt, 0, o[dt]);
+    wave_fence();
+    store_rows16<T>(Os, a.out + (((long)b * N + qt * 64 + 16 * w) * a.ldo + h * 64) * SZ, a.ldo * SZ);
+}
+
+// dvec[row] = sum_j P[row][j] dA[row][j]; one wave per row of N
+__global__ __launch_bounds__(NTH) void gattn_rowdotn_kernel(const float* __restrict__ P, const float* __restrict__ dA, float* __restrict__ dvec, int N) {
+    const long row = (long)blockIdx.x * 4 + wave_id();
+    const int l = lane_id();
+    float s = 0.f;
+    for (int j = 4 * l; j < N; j += 256) {
+        const f32x4 p = *reinterpret_cast<const f32x4*>(P + row * N + j), g = *reinterpret_cast<const f32x4*>(dA + row * N + j);
+        s += p[0] * g[0] + p[1] * g[1] + p[2] * g[2] + p[3] * g[3];
+    }
+    s = wave_sum(s);
+    if (l == 0) dvec[row] = s;
+}
+
+#define BN_PASS(RI, RO, CJ, EP, ...) \
+    hipLaunchKernelGGL((bandsn_pass_kernel<RI, RO, CJ, EP>), dim3(N / 64, N / 64, (unsigned)maps), dim3(NTH), 0, st, __VA_ARGS__)
+// map += filter(map) over B * heads maps; work: 4 planes per map (T^t re | im, X re | im), backward (pmap != nullptr) 6: the
+// spectrum of P (re | im) behind them, against which the column pass reduces d lamb
+static void launch_filtern(float* map, float* work, const float* pmap, const GAttnArgs& a, hipStream_t st) {
+    const int N = a.N, maps = a.B * a.heads;
+    const size_t per = (size_t)maps * N * N;
+    float* Tr = work; float* Ti = work + per; float* Xr = work + 2 * per; float* Xi = work + 3 * per;
+    const float* nf = nullptr;
+    const unsigned char* nu = nullptr;
+    if (pmap) {
+        float* Qr = work + 4 * per; float* Qi = work + 5 * per;
+        BN_PASS(true, false, false, E_PLAIN, pmap, nf, a.panels, Tr, Ti, N, 1.0f, nu, nf, nf, nf, (float*)nullptr, 0, 1, a.heads);
+        BN_PASS(false, false, false, E_PLAIN, (const float*)Tr, (const float*)Ti, a.panels, Qr, Qi, N, 1.0f, nu, nf, nf, nf, (float*)nullptr, 0, 1, a.heads);
+        BN_PASS(true, false, false, E_PLAIN, (const float*)map, nf, a.panels, Tr, Ti, N, 1.0f, nu, nf, nf, nf, (float*)nullptr, 0, 1, a.heads);
+        BN_PASS(false, false, false, E_WEIGHT_DL, (const float*)Tr, (const float*)Ti, a.panels, Xr, Xi, N, 1.0f, a.bandidx, a.lamb, (const float*)Qr,
+                (const float*)Qi, a.dlamb, a.nb, a.lamb_batch, a.heads);
+    } else {
+        BN_PASS(true, false, false, E_PLAIN, (const float*)map, nf, a.panels, Tr, Ti, N, 1.0f, nu, nf, nf, nf, (float*)nullptr, 0, 1, a.heads);
+        BN_PASS(false, false, false, E_WEIGHT, (const float*)Tr, (const float*)Ti, a.panels, Xr, Xi, N, 1.0f, a.bandidx, a.lamb, nf, nf, (float*)nullptr,
+                a.nb, a.lamb_batch, a.heads);
+    }
+    BN_PASS(false, false, true, E_PLAIN, (const float*)Xr, (const float*)Xi, a.panels, Tr, Ti, N, 1.0f, nu, nf, nf, nf, (float*)nullptr, 0, 1, a.heads);
+    BN_PASS(false, true, true, E_PLAIN, (const float*)Tr, (const float*)Ti, a.panels, map, (float*)nullptr, N, 1.0f / ((float)N * (float)N), nu, nf, nf,
+            nf, (float*)nullptr, 0, 1, a.heads);
+}
+template <typename T> static int bandsn_fwd(const GAttnArgs& a, float* work, hipStream_t st) {
+    const int tiles = a.B * a.heads * (a.N / 64);
+    hipLaunchKernelGGL((gattn_probsn_kernel<T>), dim3(tiles), dim3(NTH), (size_t)2 * GG<T>::TILE, st, a);
+    launch_filtern(a.map, work, nullptr, a, st);
+    hipLaunchKernelGGL((gattn_applyn_kernel<T>), dim3(tiles), dim3(NTH), (size_t)3 * GG<T>::TILE, st, a);
+    FW_LAUNCH_RET();
+}
+template <typename T> static int bandsn_bwd(const GAttnArgs& a, float* work, hipStream_t st) {
+    const int maps = a.B * a.heads, tiles = maps * (a.N / 64);
+    const size_t lds_rows = (size_t)4 * GG<T>::TILE, lds = bwd_lds<T>(false);
+    FW_SET_LDS_ONCE((gattn_dc_rows_kernel<T, true, 0>), lds_rows);
+    hipLaunchKernelGGL((gattn_dc_rows_kernel<T, true, 0>), dim3(tiles), dim3(NTH), lds_rows, st, a);
+    launch_filtern(a.map2, work, a.pmap, a, st);
+    hipLaunchKernelGGL(gattn_rowdotn_kernel, dim3(maps * (a.N / 4)), dim3(NTH), 0, st, (const float*)a.pmap, (const float*)a.map2, a.dvec, a.N);
+    FW_SET_LDS_ONCE((gattn_maps_bwd_kernel<T, 0>), lds);
+    hipLaunchKernelGGL((gattn_maps_bwd_kernel<T, 0>), dim3(tiles), dim3(NTH), lds, st, a);
+    FW_LAUNCH_RET();
+}
 template <typename T> static int dispatch(const GAttnArgs& a, bool bwd, hipStream_t st) {
     const bool lamb = a.lamb != nullptr;
     if (a.N == 64) {
         if (lamb) bwd ? launch_bwd<T, 1, true>(a, st) : launch_fwd<T, 1, true>(a, st);
         else bwd ? launch_bwd<T, 1, false>(a, st) : launch_fwd<T, 1, false>(a, st);
     } else if (a.N != 256) {
-        launch_stream<T>(a, bwd, st);                                  // common_ok: no lamb here
+        if (lamb) launch_stream_dc<T>(a, bwd, st);                     // common_ok: 'DC' at N = 576 / 1024 only
+        else launch_stream<T>(a, bwd, st);
     } else if (lamb) {
         bwd ? launch_dc_bwd<T>(a, st) : launch_dc_fwd<T>(a, st);
     } else {
@@ -1099,11 +1467,12 @@ template <typename T> static int dispatch(const GAttnArgs& a, bool bwd, hipStrea
     }
     FW_LAUNCH_RET();
 }
-// lamb: N = 64 with the 64x64 tables (any nb), or N = 256 in the 'DC' form (nb = 2, band 0 = bin (0, 0): no tables); nothing else has a kernel
-// N: 64 and 256 (register kernels), or any other multiple of 64 in [128, 1024] without lamb (streaming forward)
+// lamb: N = 64 with the 64x64 tables (any nb), or N in {256, 576, 1024} in the 'DC' form (nb = 2, band 0 = bin (0, 0): no tables);
+// nothing else has a kernel
+// N: 64 and 256 (register kernels), or any other multiple of 64 in [128, 1024] (streaming forward; lamb at 576 and 1024 only)
 static bool common_ok(const GAttnArgs& a, int dtype) {
     const int sz = dtype == FW_DT_BF16 ? 2 : 4;
-    const bool stream_n = a.N % 64 == 0 && a.N >= 128 && a.N <= 1024 && !a.lamb;
+    const bool stream_n = a.N % 64 == 0 && a.N >= 128 && a.N <= 1024 && (!a.lamb || a.N == 576 || a.N == 1024);
     if (!(a.q && a.k && a.v && a.lse && a.B > 0 && a.heads > 0 && (a.N == 64 || a.N == 256 || stream_n))) return false;
     if ((a.ld * sz) % 16 || ((uintptr_t)a.q | (uintptr_t)a.k | (uintptr_t)a.v) % 16) return false;
     if (a.thresh && !a.seed) return false;
@@ -1154,7 +1523,7 @@ extern "C" int fw_gattn_bwd(int dtype, const void* q, const void* k, const void*
     const int sz = dtype == FW_DT_BF16 ? 2 : 4;
     FW_CHECK_ARG(dtype == FW_DT_BF16 || dtype == FW_DT_F32);
     FW_CHECK_ARG(common_ok(a, dtype) && o && dout && dq && dk && dv && (lamb ? dlamb != nullptr : dvec != nullptr));
-    FW_CHECK_ARG(!(lamb && N == 256) || dvec != nullptr);                  // the DC form keeps rowsum(P G) there
+    FW_CHECK_ARG(!(lamb && N != 64) || dvec != nullptr);                   // the DC form keeps rowsum(P G) there
     FW_CHECK_ARG((ldo * sz) % 16 == 0 && (lddo * sz) % 16 == 0 && (ldd * sz) % 16 == 0 && drop_p >= 0.f && drop_p < 1.f);
     FW_CHECK_ARG(((uintptr_t)o | (uintptr_t)dout | (uintptr_t)dq | (uintptr_t)dk | (uintptr_t)dv) % 16 == 0);
     return dtype == FW_DT_BF16 ? dispatch<bf16raw>(a, true, (hipStream_t)stream) : dispatch<float>(a, true, (hipStream_t)stream);
@@ -1196,4 +1565,45 @@ extern "C" int fw_gattn_bands_bwd(int dtype, const void* q, const void* k, const
     FW_CHECK_ARG((lddo * sz) % 16 == 0 && (ldd * sz) % 16 == 0 && drop_p >= 0.f && drop_p < 1.f);
     FW_CHECK_ARG(((uintptr_t)dout | (uintptr_t)dq | (uintptr_t)dk | (uintptr_t)dv | (uintptr_t)amap | (uintptr_t)pmap | (uintptr_t)gmap | (uintptr_t)work) % 16 == 0);
     return dtype == FW_DT_BF16 ? bands_bwd<bf16raw>(a, work, (hipStream_t)stream) : bands_bwd<float>(a, work, (hipStream_t)stream);
+}
+
+// <n>_bands with N x N masks at N = 576 / 1024 (see fwair.h): probs -> row / column / inverse / output passes -> apply
+static bool bandsn_ok(const GAttnArgs& a, int dtype) {
+    return (a.N == 576 || a.N == 1024) && bands_ok(a, dtype) && (long)a.B * a.heads <= 65535;
+}
+extern "C" int fw_gattn_bandsn_fwd(int dtype, const void* q, const void* k, const void* v, long ld, void* out, long ldo, float* lse, int B, int heads,
+                                   int N, float scale, const void* seed, int site, float drop_p, const float* lamb, int nb, int lamb_batch,
+                                   const void* bandidx, const float* panels, float* amap, float* work, void* stream) {
+    GAttnArgs a{};
+    a.q = (const char*)q; a.k = (const char*)k; a.v = (const char*)v; a.ld = ld; a.out = (char*)out; a.ldo = ldo; a.lse = lse;
+    a.B = B; a.heads = heads; a.N = N; a.scale = scale;
+    a.seed = (const unsigned*)seed; a.site = (unsigned)site; a.thresh = drop_p > 0.f ? fw_drop_thresh(drop_p) : 0u;
+    a.inv_keep = drop_p > 0.f ? 1.0f / (1.0f - drop_p) : 1.0f;
+    a.lamb = lamb; a.nb = nb; a.lamb_batch = lamb_batch; a.bandidx = (const unsigned char*)bandidx; a.panels = panels; a.map = amap;
+    const int sz = dtype == FW_DT_BF16 ? 2 : 4;
+    FW_CHECK_ARG(dtype == FW_DT_BF16 || dtype == FW_DT_F32);
+    FW_CHECK_ARG(bandsn_ok(a, dtype) && out && amap && work && (ldo * sz) % 16 == 0 && drop_p >= 0.f && drop_p < 1.f);
+    FW_CHECK_ARG(((uintptr_t)out | (uintptr_t)amap | (uintptr_t)work) % 16 == 0);
+    return dtype == FW_DT_BF16 ? bandsn_fwd<bf16raw>(a, work, (hipStream_t)stream) : bandsn_fwd<float>(a, work, (hipStream_t)stream);
+}
+
+extern "C" int fw_gattn_bandsn_bwd(int dtype, const void* q, const void* k, const void* v, long ld, const void* dout, long lddo, const float* lse,
+                                   float* dvec, void* dq, void* dk, void* dv, long ldd, int B, int heads, int N, float scale, const void* seed,
+                                   int site, float drop_p, const float* lamb, float* dlamb, int nb, int lamb_batch, const void* bandidx,
+                                   const float* panels, const float* amap, float* pmap, float* gmap, float* work, void* stream) {
+    GAttnArgs a{};
+    a.q = (const char*)q; a.k = (const char*)k; a.v = (const char*)v; a.ld = ld;
+    a.dout = (const char*)dout; a.lddo = lddo; a.lse = const_cast<float*>(lse); a.dvec = dvec;
+    a.dq = (char*)dq; a.dk = (char*)dk; a.dv = (char*)dv; a.ldd = ldd;
+    a.B = B; a.heads = heads; a.N = N; a.scale = scale;
+    a.seed = (const unsigned*)seed; a.site = (unsigned)site; a.thresh = drop_p > 0.f ? fw_drop_thresh(drop_p) : 0u;
+    a.inv_keep = drop_p > 0.f ? 1.0f / (1.0f - drop_p) : 1.0f;
+    a.lamb = lamb; a.dlamb = dlamb; a.nb = nb; a.lamb_batch = lamb_batch; a.bandidx = (const unsigned char*)bandidx; a.panels = panels;
+    a.map = const_cast<float*>(amap); a.pmap = pmap; a.map2 = gmap;
+    const int sz = dtype == FW_DT_BF16 ? 2 : 4;
+    FW_CHECK_ARG(dtype == FW_DT_BF16 || dtype == FW_DT_F32);
+    FW_CHECK_ARG(bandsn_ok(a, dtype) && dout && dq && dk && dv && dvec && dlamb && amap && pmap && gmap && work);
+    FW_CHECK_ARG((lddo * sz) % 16 == 0 && (ldd * sz) % 16 == 0 && drop_p >= 0.f && drop_p < 1.f);
+    FW_CHECK_ARG(((uintptr_t)dout | (uintptr_t)dq | (uintptr_t)dk | (uintptr_t)dv | (uintptr_t)amap | (uintptr_t)pmap | (uintptr_t)gmap | (uintptr_t)work) % 16 == 0);
+    return dtype == FW_DT_BF16 ? bandsn_bwd<bf16raw>(a, work, (hipStream_t)stream) : bandsn_bwd<float>(a, work, (hipStream_t)stream);
 }

@@ -18,7 +18,8 @@ the attention kernel (64x64 2-D DFT on the f32 MFMA).  Like the reference it nee
 are dim_head x dim_head, :56,60); at any other size both raise.  `opt.vit_band_grid = 'tokens'` sizes the masks by the attention
 map instead (N x N; identical at N = 64): at N = 256 'DC' then runs as an affine map of the softmax (csrc/fw_gattn.hip dc_coef)
 and '<n>_bands' as a multi-pass 256x256 2-D DFT on the f32 MFMA between a probabilities and an apply kernel (fw_gattn_bands_fwd / bwd).
-At N = 576 / 1024 the attention is plain softmax + Dropout: a band re-weighting there has no kernel and raises.
+At N = 576 / 1024 (384x384 / 512x512 inputs) 'DC' is the same affine map inside the streaming forward and '<n>_bands' the LDS-free
+tiled N x N DFT passes (fw_gattn_bandsn_fwd / bwd); a band re-weighting at any other streaming N has no kernel and raises.
 """
 import math
 import zlib
@@ -163,11 +164,16 @@ class GlobalAttnFn(torch.autograd.Function):
         nb, lb = (lamb.shape[0], lamb.shape[1]) if lamb is not None else (0, 1)
         lam = lamb.detach().contiguous() if lamb is not None else None
         amap = None
-        if N == 256 and lam is not None and bidx is not None:            # <n>_bands on the N x N grid: the map leaves the workgroup
+        if N != 64 and lam is not None and bidx is not None:             # <n>_bands on the N x N grid: the map leaves the workgroup
             amap = torch.empty((B * heads, N, N), dtype=torch.float32, device=qkv.device)          # P + filter(P): kept for backward
-            work = torch.empty((B * heads, 2, N, N), dtype=torch.float32, device=qkv.device)
-            call('fw_gattn_bands_fwd', dt(qkv.dtype), qkv, qkv[:, inner:], qkv[:, 2 * inner:], qkv.stride(0), out, out.stride(0), lse, B, heads,
-                 64 ** -0.5, seed, site, float(p), lam, nb, lb, bidx, panels, amap, work)
+            if N == 256:
+                work = torch.empty((B * heads, 2, N, N), dtype=torch.float32, device=qkv.device)
+                call('fw_gattn_bands_fwd', dt(qkv.dtype), qkv, qkv[:, inner:], qkv[:, 2 * inner:], qkv.stride(0), out, out.stride(0), lse, B,
+                     heads, 64 ** -0.5, seed, site, float(p), lam, nb, lb, bidx, panels, amap, work)
+            else:                                                        # N = 576 / 1024: the tiled passes
+                work = torch.empty((4, B * heads, N, N), dtype=torch.float32, device=qkv.device)
+                call('fw_gattn_bandsn_fwd', dt(qkv.dtype), qkv, qkv[:, inner:], qkv[:, 2 * inner:], qkv.stride(0), out, out.stride(0), lse, B,
+                     heads, N, 64 ** -0.5, seed, site, float(p), lam, nb, lb, bidx, panels, amap, work)
         else:
             call('fw_gattn_fwd', dt(qkv.dtype), qkv, qkv[:, inner:], qkv[:, 2 * inner:], qkv.stride(0), out, out.stride(0), lse, B, heads, N,
                  64 ** -0.5, seed, site, float(p), lam, nb, lb, bidx, panels)
@@ -188,15 +194,21 @@ class GlobalAttnFn(torch.autograd.Function):
         dvec = None
         if lam is not None:
             dlam, rl = Fn._grad_target(ctx.lamb_param)
-        if lam is None or N == 256:                                      # 'DC' on the N x N grid keeps rowsum(P . dP) there
+        if lam is None or N != 64:                                       # 'DC' on the N x N grid keeps rowsum(P . dP) there
             dvec = torch.empty((B, heads, N), dtype=torch.float32, device=qkv.device)
         nb, lb = (lam.shape[0], lam.shape[1]) if lam is not None else (0, 1)
         if amap is not None:
             pmap, gmap = torch.empty_like(amap), torch.empty_like(amap)
-            work = torch.empty((2, B * heads, 2, N, N), dtype=torch.float32, device=qkv.device)
-            call('fw_gattn_bands_bwd', dt(qkv.dtype), qkv, qkv[:, inner:], qkv[:, 2 * inner:], qkv.stride(0), dout, dout.stride(0), lse, dvec,
-                 dqkv, dqkv[:, inner:], dqkv[:, 2 * inner:], dqkv.stride(0), B, heads, 64 ** -0.5, seed, site, float(p), lam, dlam, nb, lb,
-                 bidx, panels, amap, pmap, gmap, work)
+            if N == 256:
+                work = torch.empty((2, B * heads, 2, N, N), dtype=torch.float32, device=qkv.device)
+                call('fw_gattn_bands_bwd', dt(qkv.dtype), qkv, qkv[:, inner:], qkv[:, 2 * inner:], qkv.stride(0), dout, dout.stride(0), lse, dvec,
+                     dqkv, dqkv[:, inner:], dqkv[:, 2 * inner:], dqkv.stride(0), B, heads, 64 ** -0.5, seed, site, float(p), lam, dlam, nb, lb,
+                     bidx, panels, amap, pmap, gmap, work)
+            else:
+                work = torch.empty((6, B * heads, N, N), dtype=torch.float32, device=qkv.device)
+                call('fw_gattn_bandsn_bwd', dt(qkv.dtype), qkv, qkv[:, inner:], qkv[:, 2 * inner:], qkv.stride(0), dout, dout.stride(0), lse,
+                     dvec, dqkv, dqkv[:, inner:], dqkv[:, 2 * inner:], dqkv.stride(0), B, heads, N, 64 ** -0.5, seed, site, float(p), lam,
+                     dlam, nb, lb, bidx, panels, amap, pmap, gmap, work)
             return dqkv, rl, None
         call('fw_gattn_bwd', dt(qkv.dtype), qkv, qkv[:, inner:], qkv[:, 2 * inner:], qkv.stride(0), out, out.stride(0), dout, dout.stride(0),
              lse, dvec, dqkv, dqkv[:, inner:], dqkv[:, 2 * inner:], dqkv.stride(0), B, heads, N, 64 ** -0.5, seed, site, float(p),
@@ -289,12 +301,12 @@ class Transformer(nn.Module):
                 if N != 64 and self.band_grid != 'tokens':
                     raise NotImplementedError('the band re-weighting needs N = dim_head = 64 tokens (128x128 inputs): the reference sizes '
                                               'its masks dim_head x dim_head (encoder_ViT.py:56,60) and fails otherwise too')
-                if N not in (64, 256):
-                    raise NotImplementedError(f'the band re-weighting has kernels at N = 64 and N = 256 tokens only, not N = {N}: the streaming '
-                                              'attention of the larger inputs is plain softmax + Dropout (frequency_decompose_type none)')
+                if N not in (64, 256, 576, 1024):
+                    raise NotImplementedError(f'the band re-weighting has kernels at N = 64, 256, 576 and 1024 tokens only, not N = {N}: the '
+                                              'streaming attention of any other size is plain softmax + Dropout (frequency_decompose_type none)')
                 if a.lamb.shape[1] not in (1, B):
                     raise NotImplementedError(f'batch-wise lamb was built for batch {a.lamb.shape[1]}, got {B}')
-                # N = 256 'DC': band 0 is the mean of the map, 1 / N for softmax rows -- an affine map, no tables (csrc/fw_gattn.hip dc_coef)
+                # N = 256 / 576 / 1024 'DC': band 0 is the mean of the map, 1 / N for softmax rows -- an affine map, no tables (csrc/fw_gattn.hip dc_coef)
                 lamb, spec = a.lamb, (None if N != 64 and a._kind == 'DC' else _spectral_tables(a._kind, a.num_bands, x.device, n=N))
             o = GlobalAttnFn.apply(qkv, lamb, (B, N, a.heads, pa, site, spec))
             if po > 0:

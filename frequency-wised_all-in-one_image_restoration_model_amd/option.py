@@ -50,7 +50,7 @@ _FLAGS = [
                              help='storage type of activations / GEMM operands in the HIP kernels (accumulation is f32).')),
     ('--vit_band_grid', dict(type=str, default='head_dim', choices=['head_dim', 'tokens'],
                              help='grid of the ViT band masks: head_dim x head_dim (the reference: needs 64 tokens, 128x128 inputs) or '
-                                  'tokens x tokens (the size of the attention map: 64 or 256).')),
+                                  'tokens x tokens (the size of the attention map: 64, 256, 576 or 1024).')),
     ('--grad_allreduce_dtype', dict(type=str, default='fp32', choices=['fp32', 'bf16'],
                                     help='wire type of the data-parallel gradient all-reduce.')),
 ]

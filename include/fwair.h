@@ -280,24 +280,25 @@ int fw_small_linear_bwd(const float* dy, const float* y, const float* x, const f
                         int K, float slope, void* stream);
 
 /* ---- ViT global attention (net/encoder_ViT.py:76-98 `Attention.forward`; BASELINE configs[4]: N = 256 tokens at 256x256) -----
- * q | k | v: T [B*N][ld], head h at column h * 64 (head_dim 64); N in {64, 256}, or -- with lamb = NULL -- any other multiple of
- * 64 from 128 to 1024 (576 at 384x384, 1024 at 512x512).  out: T [B*N][heads*64]; lse: f32 [B][heads][N].
+ * q | k | v: T [B*N][ld], head h at column h * 64 (head_dim 64); N in {64, 256}, or any other multiple of 64 from 128 to 1024
+ * (576 at 384x384, 1024 at 512x512; lamb at 576 and 1024 only, NULL elsewhere).  out: T [B*N][heads*64]; lse: f32 [B][heads][N].
  * attn = softmax(q k^T scale) [+ sum_i lamb[i] band_i(attn)] -> dropout(p) -> attn v, one workgroup per (image, head, 64 queries),
  * the 64 x N score block in registers at N in {64, 256}; at the other N the key tiles stream past with an online softmax (same lse,
- * same mask indices, plain attention + Dropout only).  Dropout (encoder_ViT.py:67,94): counter-based mask of (seed[0], site, flat index of the
+ * same mask indices).  Dropout (encoder_ViT.py:67,94): counter-based mask of (seed[0], site, flat index of the
  * [B][heads][N][N] map), re-derived by the backward pass; drop_p = 0 or eval: off.  lamb (optional, N = 64 only -- the reference's
  * masks are dim_head x dim_head, encoder_ViT.py:56,60): f32 [nb][lamb_batch (1 | B)][heads] of encoder_ViT.py:62-66,85-92, evaluated
  * as a 64x64 2-D DFT on the f32 MFMA; bandidx: u8 [64][64] band of every un-shifted spectrum bin; panels: f32 cos[64][64], sin[64][64].
- * N = 256 with lamb: only the 'DC' decomposition on the N x N grid (encoder_ViT.py:59-60 'frequency_decompose_dc' with masks sized
- * by the map): nb = 2, bandidx = panels = NULL; band 0 is the mean of the map, 1 / N for softmax rows, so the kernel evaluates
- * attn' = (1 + lamb[1]) attn + (lamb[0] - lamb[1]) / N without a transform; `<n>_bands` at N = 256 is fw_gattn_bands_fwd / bwd, which
- * require the tables.  Every other lamb / N combination (any lamb at N not in {64, 256} included) and every other N is an argument
- * error. */
+ * N in {256, 576, 1024} with lamb: only the 'DC' decomposition on the N x N grid (encoder_ViT.py:59-60 'frequency_decompose_dc' with
+ * masks sized by the map): nb = 2, bandidx = panels = NULL; band 0 is the mean of the map, 1 / N for softmax rows, so the kernel
+ * evaluates attn' = (1 + lamb[1]) attn + (lamb[0] - lamb[1]) / N without a transform (at 576 / 1024 the streaming forward keeps a
+ * second, unrescaled accumulator for the constant term); `<n>_bands` is fw_gattn_bands_fwd / bwd at N = 256 and fw_gattn_bandsn_fwd /
+ * bwd at N = 576 / 1024, which require the tables.  Every other lamb / N combination (any lamb at N not in {64, 256, 576, 1024}
+ * included) and every other N is an argument error. */
 int fw_gattn_fwd(int dtype, const void* q, const void* k, const void* v, long ld, void* out, long ldo, float* lse, int B, int heads, int N,
                  float scale, const void* seed, int site, float drop_p, const float* lamb, int nb, int lamb_batch, const void* bandidx,
                  const float* panels, void* stream);
 /* Same domain as fw_gattn_fwd.  dq, dk, dv: T, same layout as q / k / v (row stride ldd); dvec: f32 [B][heads][N] scratch
- * (rowsum(dO . O); unused with lamb at N = 64, required with lamb at N = 256, where it receives rowsum(P . dP));
+ * (rowsum(dO . O); unused with lamb at N = 64, required with lamb at N = 256 / 576 / 1024, where it receives rowsum(P . dP));
  * dlamb: accumulated (atomics), same layout as lamb. */
 int fw_gattn_bwd(int dtype, const void* q, const void* k, const void* v, long ld, const void* o, long ldo, const void* dout, long lddo,
                  const float* lse, float* dvec, void* dq, void* dk, void* dv, long ldd, int B, int heads, int N, float scale,
@@ -319,6 +320,23 @@ int fw_gattn_bands_bwd(int dtype, const void* q, const void* k, const void* v, l
                        float* dvec, void* dq, void* dk, void* dv, long ldd, int B, int heads, float scale, const void* seed, int site,
                        float drop_p, const float* lamb, float* dlamb, int nb, int lamb_batch, const void* bandidx, const float* panels,
                        const float* amap, float* pmap, float* gmap, float* work, void* stream);
+/* `<n>_bands` masks sized by the map at N = 576 (384x384 inputs) and N = 1024 (512x512) -- any other N is an argument error;
+ * encoder_ViT.py:55-56,85-92 with FrequencyDecompose('frequency_decompose', 1/nb, N, N).  The arguments of fw_gattn_bands_fwd plus
+ * N; bandidx: u8 [N][N] (symmetric), panels: f32 cos[N][N], sin[N][N] of 2 pi u i / N.  A probabilities kernel (two walks over the
+ * key tiles: online lse, then attn = exp(s scale - lse) as f32), four LDS-free 64x64-tile passes of a batched N x N 2-D DFT on the
+ * f32 MFMA (row, column with the lamb weights, inverse column, output: attn += Re IDFT2(W . DFT2(attn))), and an apply kernel
+ * (Dropout, attn v).  amap: f32 [B*heads][N][N], kept for the backward pass; work: 4 * B*heads * N * N floats of scratch
+ * ([4][B*heads][N][N]); B * heads <= 65535. */
+int fw_gattn_bandsn_fwd(int dtype, const void* q, const void* k, const void* v, long ld, void* out, long ldo, float* lse, int B, int heads,
+                        int N, float scale, const void* seed, int site, float drop_p, const float* lamb, int nb, int lamb_batch,
+                        const void* bandidx, const float* panels, float* amap, float* work, void* stream);
+/* The arguments of fw_gattn_bands_bwd plus N (576 | 1024).  pmap, gmap: f32 [B*heads][N][N] scratch; work: 6 * B*heads * N * N floats
+ * of scratch ([6][B*heads][N][N]: the two pairs of transform planes of the forward, and the spectrum of the probabilities that
+ * encoder_ViT.py:85-92 differentiates lamb against); dvec: f32 [B][heads][N]; dlamb accumulated, one atomic per workgroup and band. */
+int fw_gattn_bandsn_bwd(int dtype, const void* q, const void* k, const void* v, long ld, const void* dout, long lddo, const float* lse,
+                        float* dvec, void* dq, void* dk, void* dv, long ldd, int B, int heads, int N, float scale, const void* seed,
+                        int site, float drop_p, const float* lamb, float* dlamb, int nb, int lamb_batch, const void* bandidx,
+                        const float* panels, const float* amap, float* pmap, float* gmap, float* work, void* stream);
 /* nn.Dropout call sites of the ViT (encoder_ViT.py:31,33,73,158,189) with the same counter-based masks.  mode 0: y = drop(x) (f32);
  * 1: y = res + drop(x) (f32); 2: y = drop(gelu(x)) (T); 3: y = drop(x) * gelu'(aux) (T, backward of 2); 4: y = drop(x + aux[i % period])
  * (f32: pos_embedding add + emb dropout, encoder_ViT.py:187-189).  n = elements of the contiguous tensor; p = 0: identity masks. */
