@@ -82,9 +82,13 @@ def build_panels(mask_shifted):
     return panels, Mw
 
 
-def emulate_filter(P, panels, Mw):
-    """numpy restatement of band_filter() in csrc/fw_attn.hip (same products, same order); P: [..., 64, 64]."""
+def emulate_filter(P, panels, Mw, stage=None):
+    """numpy restatement of band_filter2() in csrc/fw_attn.hip (same products, same order); P: [..., 64, 64].
+    stage: applied to the input and to every stage output the kernel writes to LDS in the operand type (T, Y, Z), e.g. a rounding
+    to bf16; None keeps the chain exact in the arrays' own precision."""
     o = 0
+    if stage is None:
+        stage = lambda a: a
 
     def take(r, c):
         nonlocal o
@@ -93,17 +97,18 @@ def emulate_filter(P, panels, Mw):
         return a
     C2, S2N, CU, SU, SUN, CH, SH, SHN, GC, GSN = (take(32, 64), take(32, 64), take(48, 64), take(48, 64), take(48, 64),
                                                     take(64, 64), take(64, 64), take(64, 64), take(64, 32), take(64, 32))
-    Tr = P @ C2.T                                       # [i][v]
-    Ti = P @ S2N.T
+    P = stage(P)
+    Tr = stage(P @ C2.T)                                # [i][v]
+    Ti = stage(P @ S2N.T)
     Xr = CU @ Tr + SU @ Ti                              # [u][v]
     Xi = CU @ Ti + SUN @ Tr
-    Yr = Xr * Mw
-    Yi = Xi * Mw
-    Ypr = np.zeros(Yr.shape[:-2] + (64, 32)); Ypi = np.zeros_like(Ypr)
+    Yr = stage(Xr * Mw)
+    Yi = stage(Xi * Mw)
+    Ypr = np.zeros(Yr.shape[:-2] + (64, 32), dtype=Yr.dtype); Ypi = np.zeros_like(Ypr)
     Ypr[..., :48, :] = Yr
     Ypi[..., :48, :] = Yi
-    ZrT = np.swapaxes(Ypr, -1, -2) @ CH.T + np.swapaxes(Ypi, -1, -2) @ SHN.T     # [v][i]
-    ZiT = np.swapaxes(Ypi, -1, -2) @ CH.T + np.swapaxes(Ypr, -1, -2) @ SH.T
+    ZrT = stage(np.swapaxes(Ypr, -1, -2) @ CH.T + np.swapaxes(Ypi, -1, -2) @ SHN.T)     # [v][i]
+    ZiT = stage(np.swapaxes(Ypi, -1, -2) @ CH.T + np.swapaxes(Ypr, -1, -2) @ SH.T)
     outT = GC @ ZrT + GSN @ ZiT                         # [j][i]
     return np.swapaxes(outT, -1, -2)
 

@@ -457,3 +457,410 @@ def l1_loss_bound(a, b):
     n = a.numel()
     mag = float((a - b).abs().sum()) / n
     return mag, l1_chain_length(n) * U32 * mag * SECOND_ORDER
+
+
+# ------------------------------------------------------------------------------------------------ window attention (csrc/fw_attn.hip)
+# Element-wise bounds of fw_attn_fwd / fw_attn_bwd.  The reference evaluates the operation in f64 from the storage-rounded operands
+# and keeps every intermediate the kernels form (scores s, P, B1(P), P', dP', dS, lse); each bound below counts the roundings between
+# that intermediate and the f64 value, read off the kernels (attn_*, attn2_*, attn2x_* share the arithmetic; they differ in the walk).
+# u = U32 throughout; ut = the rounding of a value stored in the operand type before the next MFMA product or as an output.
+# ut = UBF: v_cvt_pk_bf16_f32 rounds to nearest even (fw_common.h f2bf / pack_bf2), half an ulp of 8 significant bits
+# scores: sum_d k q in an f32 MFMA chain (D terms; bf16 products are exact in f32, f32 ones round once), then  acc * scale,
+# bias + (-100), and the sum of the two: D + 3 roundings of partial results that scale * sum |q||k| + |bias| + |mask| bounds
+ATTN_SCORE_ROUNDINGS = 3
+# exp argument x = s - max (forward) or s - lse (backward): the subtraction, the product with log2(e) inside __expf, and the f32
+# value of log2(e) itself -- three roundings relative to |x|, i.e. a relative error 3 u |x| of exp(x)
+ATTN_EXP_ARG_ROUNDINGS = 3
+ATTN_EXP_VALUE_ERR = 2 * U32      # v_exp_f32: 1 ulp
+ATTN_SUM_EXTRA = 2                # softmax sum: NK / 4 sequential additions per lane (positive terms), then 2 shuffle steps
+ATTN_NORM_ERR = DIV_ERR + U32     # inv = 1.0f / sum (1 ulp) and p * inv
+# lse = max + __logf(sum): v_log_f32 (1 ulp of log2 sum, and not better than 1 ulp of 1 when sum is just above 1), the product with
+# ln 2 and ln 2's own f32 value: 4 u (1 + log sum); then the final sum, one rounding of |lse|
+ATTN_LOG_ERR = 4 * U32
+ATTN_COMBINE_ROUNDINGS = 3        # P' = p * a + b + f * c: each term passes at most three roundings (fewer when contracted to fma)
+ATTN_ACC_EXTRA = 2                # a 64- or 128-term f32 MFMA chain: K roundings, + the scale product behind dq / dk, + slack of one
+ATTN_DS_ROUNDINGS = 2             # dS = p * (dp - D_i): the difference (relative to |dp| + |D_i|) and the product
+ATTN_LANE_TERMS = 16              # score elements a lane owns per key tile: its sequential partial sums are this long
+ATTN_WAVE_FOLD = 6                # wave_sum: 6 shuffle steps
+ATTN_BIN_FOLD = 64                # LDS atomics into one of the 225 relative positions: at most 64 (i, j) pairs share one (i == j)
+# The ONE measured constant: the error of the partial-DFT band filter B1 (band_filter2: four MFMA stages; in bf16 the panels, the
+# input and the stage outputs T, Y, Z are rounded to bf16).  Its worst-case chain is several times |B1(x)| itself (sum |x| * 2 / 4096
+# * 45 * 23 * 8 per element), useless as a bound, and even the largest error of a map, carried element by element through the next
+# 64-term product, swamps a filter term that is 10 % short.  What the outputs see is that error CONTRACTED with another operand:
+# sum_j e_ij w_j.  The e_ij are rounding errors (round to nearest even: zero mean -- the measured mean is below 3 % of the rms --
+# and not aligned with w), so the sum has the standard deviation sigma ||w||_2, sigma = the rms of e; the bound allows
+# ATTN_FILTER_SIGMAS of them.  sigma is measured on the CPU, never on a GPU: fwair.lfs.emulate_filter with the panels, the input
+# and every stage output rounded to the operand type (f32: the whole chain in f32) against the exact f64 chain, on the softmax maps
+# P and the gradient maps dP' of these tests' own inputs at score scales 1, 4 and 35
+# (tests/test_window_attention_bounds_cpu.py::test_filter_allowance_is_the_measured_one prints and re-checks it).  Figures: the
+# largest rms over one row or one column of a map, relative to max |x| of that map, was 5.3e-4 (P) and 1.14e-3 (dP') in bf16,
+# 2.8e-8 and 6.4e-8 in f32.  The bf16 figure is set by the roundings to bf16 and is the same on every host; the f32 one depends on the
+# order in which the host's BLAS accumulates, so its constant is the next whole number of u above it, 2 u.  The margin of 2 is for
+# what the emulation does not share with the kernel: the f32 product with the mask weights before the rounding of Y, and the order
+# of accumulation.
+ATTN_FILTER_RMS = {torch.bfloat16: 1.2e-3, torch.float32: 2 * U32}
+ATTN_FILTER_MARGIN = 2.0
+ATTN_FILTER_SIGMAS = 4.0          # with the margin: 8 measured standard deviations
+
+
+def attn_other_band(lq, kt):
+    """the kt-th band that is not lq (key tile kt of inter-band attention)"""
+    return kt if kt < lq else kt + 1
+
+
+def attn_key_slot(lq, lk):
+    """which of the two key-gradient buffers (0: dk / dv, 1: dk2 / dv2) query band lq writes its gradient of key band lk to"""
+    return lq if lq < lk else lq - 1
+
+
+def attn_walk(nwin, chunks):
+    """per = ceil(nwin / chunks) windows per workgroup; workgroup g walks [g * per, min(nwin, (g + 1) * per)).
+    -> (per, busy workgroups, windows of the last busy one, idle workgroups)"""
+    per = -(-nwin // chunks)
+    busy = -(-nwin // per)
+    return per, busy, nwin - (busy - 1) * per, chunks - busy
+
+
+def attn2_chunks(nwin, heads, L, per_cu):
+    """grid.x of attn2_* / attn2x_*: min(nwin, max(1, 256 * per_cu / (heads * L)))"""
+    return min(nwin, max(1, 256 * per_cu // (heads * L)))
+
+
+def attn1_bwd_chunks(nwin, heads, L):
+    """grid.x of attn_bwd_kernel (v1): min(nwin, max(1, 1024 / (heads * L)))"""
+    return min(nwin, max(1, 1024 // (heads * L)))
+
+
+def attn_walks(nwin, heads, L, v1):
+    """every (per, chunks) the backward of one problem may run with: the v1 kernel's one, or the v2 kernels' for per_cu 1 and 2"""
+    cs = [attn1_bwd_chunks(nwin, heads, L)] if v1 else [attn2_chunks(nwin, heads, L, p) for p in (1, 2)]
+    return [(attn_walk(nwin, c)[0], c) for c in cs]
+
+
+def walk_crossings(nwin, chunks, nW):
+    """image boundaries (first window of an image b > 0) that lie in the INTERIOR of some workgroup's range"""
+    per = attn_walk(nwin, chunks)[0]
+    return [w for w in range(nW, nwin, nW) if w % per != 0]
+
+
+ATTN_MUTATIONS = ('bias_swapped', 'drop_key63', 'stale_coef', 'no_const', 'filter_09', 'dcoef_first_image', 'mask50')
+
+
+class WAttnCase:
+    """One window-attention problem: geometry and the storage-rounded operands, gathered into window order as f64.
+    qkv [L*B*H*W, 3C] (q | k | v, image index = band * B + b), dout [L*B*H*W, C], tables [L*L, 225, heads] f32,
+    coef [B, heads, 3] f32 or None.  qw / kw / vw / dow: [L, nwin, heads, 64, D]; window = (b * nWy + wy) * nWx + wx."""
+
+    def __init__(self, dtype, D, heads, B, H, W, L, mode, shift, lfs, qkv, dout, tables, coef=None):
+        self.dtype, self.D, self.heads, self.geo, self.lfs = dtype, D, heads, (B, H, W, L, mode, shift), lfs
+        self.C, self.nkt, self.scale = D * heads, (1 if mode == 0 else L - 1), f32c(float(D) ** -0.5)
+        self.nW = (H // 8) * (W // 8)
+        self.nwin = B * self.nW
+        self.qkv, self.dout, self.tables, self.coef = qkv, dout, tables, coef
+        t = torch.arange(64)
+        wy, wx = torch.arange(H // 8)[:, None, None], torch.arange(W // 8)[None, :, None]
+        y, x = (wy * 8 + t // 8 + shift) % H, (wx * 8 + t % 8 + shift) % W                     # pixel of token t in the unrolled image
+        img = torch.arange(L * B).view(L, B, 1, 1, 1)
+        self.rows = ((img * H + y) * W + x).reshape(L, self.nwin, 64)
+        g = lambda m, c0: m[self.rows][..., c0:c0 + self.C].double().view(L, self.nwin, 64, heads, D).transpose(2, 3)
+        self.qw, self.kw, self.vw, self.dow = g(qkv, 0), g(qkv, self.C), g(qkv, 2 * self.C), g(dout, 0)
+        i, j = t[:, None], t[None, :]
+        self.bin = (i // 8 - j // 8 + 7) * 15 + (i % 8 - j % 8 + 7)                              # [64 queries][64 keys] -> 0 .. 224
+        self.image = torch.arange(self.nwin) // self.nW
+        # shift regions of the ROLLED image per axis: [0, size - 8), [size - 8, size - shift), [size - shift, size)
+        reg = lambda p, size: (p >= size - 8).long() + (p >= size - shift).long()
+        lab = (3 * reg(wy * 8 + t // 8, H) + reg(wx * 8 + t % 8, W)).reshape(self.nW, 64)
+        self.diff = (lab[:, :, None] != lab[:, None, :]) if shift else torch.zeros(self.nW, 64, 64, dtype=torch.bool)
+
+    def keys(self, lq):
+        L, mode = self.geo[3], self.geo[4]
+        return [lq] if mode == 0 else [attn_other_band(lq, kt) for kt in range(L - 1)]
+
+    def gather(self, buf):
+        """device or host [rows, >= C] buffer -> [L, nwin, heads, 64, D] f64 on the host (window order)"""
+        L = self.geo[3]
+        m = buf.detach().cpu()[:, :self.C]
+        return m[self.rows].double().view(L, self.nwin, 64, self.heads, self.D).transpose(2, 3)
+
+
+def attn_filter_f64():
+    """-> (B1 as a function of f64 maps [..., 64, 64], |g| spectrum for abs_conv): the exact band filter of the 3-band decomposition"""
+    from fwair import lfs
+    panels, Mw = lfs.build_panels(lfs.band_masks_shifted('frequency_decompose_1', 0.5, 64, 64)[1].numpy())
+    Mw = Mw.astype(np.float64)
+    f = lambda x: torch.from_numpy(lfs.emulate_filter(x.numpy(), panels, Mw))
+    delta = torch.zeros(64, 64, dtype=torch.float64)
+    delta[0, 0] = 1.0
+    return f, torch.fft.rfft2(f(delta).abs())
+
+
+def attn_filter_emulated(dtype):
+    """band_filter2 as the kernel of `dtype` runs it: panels in the operand type, the input and T, Y, Z rounded to it; f32: all in f32"""
+    from fwair import lfs
+    panels, Mw = lfs.build_panels(lfs.band_masks_shifted('frequency_decompose_1', 0.5, 64, 64)[1].numpy())
+    if dtype == torch.bfloat16:
+        panels = torch.from_numpy(panels).to(dtype).double().numpy()
+        stage = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dtype).double().numpy()
+        return lambda x: torch.from_numpy(lfs.emulate_filter(x.double().numpy(), panels, Mw.astype(np.float64), stage)).to(x.dtype)
+    panels = panels.astype(np.float32)
+    return lambda x: torch.from_numpy(lfs.emulate_filter(x.float().numpy(), panels, Mw, lambda a: a.astype(np.float32))).to(x.dtype)
+
+
+def abs_conv(t, ghat):
+    """sum_(i', j') |g[i - i', j - j']| t[i', j'] (circular): what an element-wise error t of the filter's input can become behind it"""
+    return torch.fft.irfft2(torch.fft.rfft2(t) * ghat, s=(64, 64)).clamp_min(0) * (1 + 1e-9)
+
+
+def _attn_band(c, lq, ft, rs, filt, mutation, lse_in, walks):
+    """Query band lq of case c evaluated in float type ft (f64: the reference; f32: the emulation), rs = the rounding of a value the
+    kernel stores in the operand type.  -> dict of intermediates and results, all [nwin, heads, ...]."""
+    B, H, W, L, mode, shift = c.geo
+    keys, NK = c.keys(lq), 64 * c.nkt
+    cat = lambda w, dim: torch.cat([w[lk] for lk in keys], dim).to(ft)
+    q, k, v, do = c.qw[lq].to(ft), cat(c.kw, -2), cat(c.vw, -2), c.dow[lq].to(ft)
+    bins = c.bin.t() if mutation == 'bias_swapped' else c.bin
+    bias = torch.cat([c.tables[lq * L + lk].to(ft)[bins] for lk in keys], 1).permute(2, 0, 1)            # [heads, 64, NK]
+    mval = -50.0 if mutation == 'mask50' else -100.0
+    mask = (c.diff.to(ft) * mval).repeat(B, 1, c.nkt)[:, None]                                           # [nwin, 1, 64, NK]
+    bm = bias + mask
+    r = dict(q=q, k=k, v=v, do=do)
+    s = (q @ k.transpose(-1, -2)) * c.scale + bm
+    r['s'], r['smag'] = s, (q.abs() @ k.abs().transpose(-1, -2)) * c.scale + bias.abs() + mask.abs()
+    m = s.max(-1, keepdim=True).values
+    e = torch.exp(s - m)
+    if mutation == 'drop_key63':
+        e[..., NK - 1] = 0
+    tot = e.sum(-1, keepdim=True)
+    P = e * (1 / tot) if ft == torch.float32 else e / tot
+    r['x'], r['tot'], r['lse'], r['P'] = s - m, tot, (m + torch.log(tot)).squeeze(-1), P
+    one = torch.ones(c.nwin, c.heads, 1, 1, dtype=ft)
+    ca, cb, cc = one, 0 * one, 0 * one
+    if c.lfs:
+        img = c.image.clone()
+        if mutation == 'stale_coef':
+            first = torch.arange(c.nW, c.nwin, c.nW)
+            img[first] -= 1
+        cf = c.coef.to(ft)[img]                                                                          # [nwin, heads, 3]
+        ca, cb, cc = (cf[..., n, None, None] for n in range(3))
+        if mutation == 'no_const':
+            cb = 0 * cb
+        if mutation == 'filter_09':
+            cc = 0.9 * cc
+    r['ca'], r['cb'], r['cc'] = ca, cb, cc
+
+    def combine(p, tag):
+        if not c.lfs:
+            return p
+        if c.lfs == 2:
+            r['B1' + tag] = filt(p)
+            return p * ca + cb + r['B1' + tag] * cc
+        return p * ca + cb
+    Pp = combine(P, 'f')
+    r['Pp'] = Pp
+    r['out'] = rs(rs(Pp) @ v)
+    # ---- backward, from the lse the backward is given
+    lse = (r['lse'] if lse_in is None else lse_in.to(ft))[..., None]
+    Pb = torch.exp(s - lse)
+    dPp = do @ v.transpose(-1, -2)
+    Ppb = combine(Pb, 'b')
+    r['xb'], r['Pb'], r['dPp'], r['Ppb'] = s - lse, Pb, dPp, Ppb
+    dv = rs(rs(Ppb).transpose(-1, -2) @ do)
+    if c.lfs == 2:
+        r['B1d'] = filt(dPp)
+        dP = dPp * ca + r['B1d'] * cc
+    else:
+        dP = dPp * ca
+    if c.lfs:
+        t3 = (r['B1d'] * Pb) if c.lfs == 2 else torch.zeros_like(Pb)
+        r['cterms'] = torch.stack([dPp * Pb, dPp, t3], -1)                                               # [nwin, heads, 64, NK, 3]
+        per_win = r['cterms'].sum((2, 3))
+        credit = c.image.clone()
+        if mutation == 'dcoef_first_image':
+            per = walks[0][0]
+            credit = c.image[torch.arange(c.nwin) // per * per]
+        r['dcoef'] = torch.zeros(B, c.heads, 3, dtype=ft).index_add_(0, credit, per_win)
+    Di = (Pb * dP).sum(-1, keepdim=True)
+    dS = Pb * (dP - Di)
+    r['dP'], r['Di'], r['dS'] = dP, Di, dS
+    fold = lambda t: [torch.zeros(225, c.heads, dtype=t.dtype).index_add_(0, c.bin.reshape(-1), t[..., kt * 64:(kt + 1) * 64]
+                      .sum(0).reshape(c.heads, 4096).t().contiguous()) for kt in range(c.nkt)]
+    r['fold'] = fold
+    r['dbias'] = fold(dS)
+    dSs = rs(dS)
+    r['dq'] = rs((dSs @ k) * c.scale)
+    dk = rs((dSs.transpose(-1, -2) @ q) * c.scale)
+    r['dk'], r['dv'] = list(dk.split(64, -2)), list(dv.split(64, -2))
+    return r
+
+
+def _attn_collect(c, bands):
+    """per-band results -> out / dq [L, nwin, heads, 64, D], lse [L, nwin, heads, 64], dk / dv [L][kt] -> [nwin, heads, 64, D],
+    dbias [L*L, 225, heads], dcoef [B, heads, 3] or None"""
+    L = c.geo[3]
+    res = {n: torch.stack([b[n] for b in bands]) for n in ('out', 'lse', 'dq')}
+    res['dk'], res['dv'] = [b['dk'] for b in bands], [b['dv'] for b in bands]
+    res['dbias'] = torch.zeros(L * L, 225, c.heads, dtype=bands[0]['dbias'][0].dtype)
+    for lq, b in enumerate(bands):
+        for kt, lk in enumerate(c.keys(lq)):
+            res['dbias'][lq * L + lk] = b['dbias'][kt]
+    res['dcoef'] = bands[0]['dcoef'] if c.lfs else None
+    return res
+
+
+def attn_emulate(c, lse_in=None):
+    """The honest kernel on the host: f32 arithmetic, the operand type's rounding where the kernels round (P', dS, the outputs, the
+    filter's stages), the backward fed with the emulated forward's own lse.  -> the results as _attn_collect returns them (f32)."""
+    dt_ = c.dtype
+    rs = (lambda t: t.to(dt_).to(torch.float32)) if dt_ != torch.float32 else (lambda t: t)
+    filt = attn_filter_emulated(dt_) if c.lfs == 2 else None
+    keep = ('out', 'lse', 'dq', 'dk', 'dv', 'dbias', 'dcoef')
+    bands = []
+    for lq in range(c.geo[3]):
+        r = _attn_band(c, lq, torch.float32, rs, filt, None, None if lse_in is None else lse_in[lq], None)
+        bands.append({n: r[n] for n in keep if n in r})
+    return _attn_collect(c, bands)
+
+
+def attn_reference(c, mutation=None, lse_in=None, v1=False):
+    """f64 reference of case c (or of one of the wrong kernels of ATTN_MUTATIONS) with the element-wise bounds of a kernel's deviation
+    from it.  lse_in [L, nwin, heads, 64]: the lse the backward is GIVEN (a kernel's own output); without it the backward bounds assume
+    an lse within its own bound.  v1: attn_fwd / attn_bwd_kernel's walk instead of the v2 kernels'.
+    -> {name: (value, tol)} shaped as _attn_collect returns them."""
+    B, H, W, L, mode, shift = c.geo
+    D, NK, u = c.D, 64 * c.nkt, U32
+    ut = UBF if c.dtype == torch.bfloat16 else 0.0
+    walks = attn_walks(c.nwin, c.heads, L, v1)
+    filt, ghat = attn_filter_f64() if c.lfs == 2 else (None, None)
+    fsig, Z = ATTN_FILTER_MARGIN * ATTN_FILTER_RMS[c.dtype], ATTN_FILTER_SIGMAS
+    ident = lambda t: t
+    stored = lambda val, tol: tol + ut * (val.abs() + tol)                      # a value rounded to the operand type
+    vals, tols = [], []
+    for lq in range(L):
+        r = _attn_band(c, lq, torch.float64, ident, filt, mutation, None if lse_in is None else lse_in[lq].double(), walks)
+        q, k, v, do, P, Pb = r['q'], r['k'], r['v'], r['do'], r['P'], r['Pb']
+        ca, cb, cc = r['ca'], r['cb'], r['cc']
+        t = {}
+        es = (D + ATTN_SCORE_ROUNDINGS) * u * r['smag']
+        # forward softmax: relative error of exp(x_j) is num_j; the error of the row maximum cancels between numerator and sum, the
+        # sum's relative error is the P-weighted mean of num_j plus its own roundings
+        num = es + ATTN_EXP_ARG_ROUNDINGS * u * r['x'].abs() + ATTN_EXP_VALUE_ERR
+        avg = (P * num).sum(-1, keepdim=True)
+        sum_err = avg + (NK // 4 + ATTN_SUM_EXTRA) * u
+        tolP = P * torch.expm1(num + sum_err + ATTN_NORM_ERR) + F32_TINY
+        lse = r['lse']
+        t['lse'] = sum_err.squeeze(-1) + ATTN_LOG_ERR * (1 + torch.log(r['tot'].squeeze(-1))) + u * lse.abs()
+        # backward softmax: exp(s - lse) with the given lse; without one, an lse within its bound
+        e_lse = (u * lse.abs() if lse_in is not None else t['lse'])[..., None]
+        tolPb = Pb * torch.expm1(es + e_lse + ATTN_EXP_ARG_ROUNDINGS * u * r['xb'].abs() + ATTN_EXP_VALUE_ERR) + F32_TINY
+        tol_dPp = (D + ATTN_ACC_EXTRA) * u * (do.abs() @ v.abs().transpose(-1, -2))
+
+        def filt_sigma(x):                                                     # rms of the filter's own error, per map
+            return fsig * x.abs().amax((-1, -2), keepdim=True)
+
+        def combine_tol(p, tolp, tag):                                         # error of P' = a p + b + c B1(p)
+            if not c.lfs:
+                return tolp
+            tol = ca.abs() * tolp + ATTN_COMBINE_ROUNDINGS * u * ((ca * p).abs() + cb.abs())
+            if c.lfs == 2:
+                # the error of the filter's INPUT, carried through it exactly (|g| convolution); its own error goes separately
+                tol = tol + cc.abs() * abs_conv(tolp, ghat) + ATTN_COMBINE_ROUNDINGS * u * (cc * r['B1' + tag]).abs()
+            return tol
+        zero = torch.zeros(c.nwin, c.heads, 1, 1, dtype=torch.float64)
+        gP, gPb, gd = (cc.abs() * filt_sigma(x) if c.lfs == 2 else zero for x in (P, Pb, r['dPp']))     # sigma of c B1's own error
+        tolPp = stored(r['Pp'], combine_tol(P, tolP, 'f'))
+        out = r['Pp'] @ v
+        t['out'] = stored(out, tolPp @ v.abs() + (NK + ATTN_ACC_EXTRA) * u * (r['Pp'].abs() @ v.abs())) \
+            + Z * gP * (v * v).sum(-2, keepdim=True).sqrt()
+        tolPpb = stored(r['Ppb'], combine_tol(Pb, tolPb, 'b'))
+        dv = r['Ppb'].transpose(-1, -2) @ do
+        t['dv'] = list((stored(dv, tolPpb.transpose(-1, -2) @ do.abs()
+                               + (64 + ATTN_ACC_EXTRA) * u * (r['Ppb'].abs().transpose(-1, -2) @ do.abs()))
+                        + Z * gPb * (do * do).sum(-2, keepdim=True).sqrt()).split(64, -2))
+        dPp, dP = r['dPp'], r['dP']
+        if c.lfs:
+            tol_dP = ca.abs() * tol_dPp + 2 * u * (ca * dPp).abs()
+            if c.lfs == 2:
+                tB1d = abs_conv(tol_dPp, ghat)
+                tol_dP = tol_dP + cc.abs() * tB1d + 2 * u * (cc * r['B1d']).abs()
+                # <B1(dP'), P>: the filter's own error contracted with P over the whole map
+                t3 = tB1d * Pb + (r['B1d'].abs() + tB1d) * tolPb + Z * filt_sigma(dPp) * (Pb * Pb).sum((-1, -2), keepdim=True).sqrt() / (64 * NK)
+            else:
+                t3 = torch.zeros_like(Pb)
+            # d(a, b, c): per lane 16 products and sums per window, `per` windows, the wave fold, then one atomic per wave of
+            # every workgroup that holds windows of the image
+            chain = max(1 + ATTN_LANE_TERMS * c.nkt + per + ATTN_WAVE_FOLD + 4 * (-(-c.nW // per) + 1) for per, _ in walks)
+            terr = torch.stack([tol_dPp * Pb + (dPp.abs() + tol_dPp) * tolPb, tol_dPp, t3], -1).sum((2, 3)) \
+                + chain * u * r['cterms'].abs().sum((2, 3))
+            t['dcoef'] = torch.zeros(B, c.heads, 3, dtype=torch.float64).index_add_(0, c.image, terr)
+        else:
+            tol_dP = tol_dPp
+        Di = r['Di']
+        tolD = (tolPb * dP.abs() + (Pb + tolPb) * tol_dP).sum(-1, keepdim=True) \
+            + (1 + NK // 4 + ATTN_SUM_EXTRA) * u * (Pb * dP).abs().sum(-1, keepdim=True) \
+            + Z * gd * (Pb * Pb).sum(-1, keepdim=True).sqrt()                   # c B1(dP')'s own error contracted with the row of P
+        gS = Pb * gd                                                            # sigma of that error as dS = P (dP - D_i) carries it on
+        dS = r['dS']
+        tol_dS = tolPb * (dP - Di).abs() + (Pb + tolPb) * (tol_dP + tolD + u * (dP.abs() + Di.abs())) + ATTN_DS_ROUNDINGS * u * dS.abs()
+        # dbias: `per` additions into the lane's accumulator, the LDS fold, one global atomic per busy workgroup
+        bchain = max(per + ATTN_BIN_FOLD + attn_walk(c.nwin, ch)[1] for per, ch in walks)
+        t['dbias'] = [a + bchain * u * b + Z * g.sqrt() for a, b, g in zip(r['fold'](tol_dS), r['fold'](dS.abs()), r['fold'](gS * gS))]
+        tol_dSs = stored(dS, tol_dS)
+        dq = (dS @ k) * c.scale
+        t['dq'] = stored(dq, c.scale * (tol_dSs @ k.abs() + (NK + ATTN_ACC_EXTRA) * u * (dS.abs() @ k.abs()))) \
+            + c.scale * Z * ((gS * gS) @ (k * k)).sqrt()
+        dk = (dS.transpose(-1, -2) @ q) * c.scale
+        t['dk'] = list((stored(dk, c.scale * (tol_dSs.transpose(-1, -2) @ q.abs()
+                                              + (64 + ATTN_ACC_EXTRA) * u * (dS.abs().transpose(-1, -2) @ q.abs())))
+                        + c.scale * Z * ((gS * gS).transpose(-1, -2) @ (q * q)).sqrt()).split(64, -2))
+        vals.append(dict(out=out, lse=lse, dq=dq, dk=list(dk.split(64, -2)), dv=list(dv.split(64, -2)), dbias=r['dbias'],
+                         dcoef=r.get('dcoef')))
+        tols.append(t)
+        del r
+    V, T = _attn_collect(c, vals), _attn_collect(c, [dict(tt, dcoef=tt.get('dcoef')) for tt in tols])
+    if c.lfs:
+        T['dcoef'] = sum(tt['dcoef'] for tt in tols)
+    return {n: (V[n], T[n]) for n in V if V[n] is not None}
+
+
+def attn_with_prefill(ref, c, dbias0, dcoef0=None, v1=False):
+    """the reference of a backward that ACCUMULATES into buffers holding dbias0 / dcoef0: value + pre-fill, and one more rounding of
+    |pre-fill| for every atomic addition that lands on the word (one per busy workgroup for dbias; one per wave of every workgroup
+    that holds windows of the image for dcoef)"""
+    walks = attn_walks(c.nwin, c.heads, c.geo[3], v1)
+    ref = dict(ref)
+    badds = max(attn_walk(c.nwin, ch)[1] for _, ch in walks)
+    ref['dbias'] = (ref['dbias'][0] + dbias0.double(), ref['dbias'][1] + badds * U32 * dbias0.double().abs())
+    if dcoef0 is not None:
+        adds = max(4 * (-(-c.nW // per) + 1) for per, _ in walks)
+        ref['dcoef'] = (ref['dcoef'][0] + dcoef0.double(), ref['dcoef'][1] + adds * U32 * dcoef0.double().abs())
+    return ref
+
+
+def attn_outputs_flat(res):
+    """{name: tensor or per-band lists} -> {name: one flat tensor} in a fixed order (dk / dv: [lq][kt] concatenated)"""
+    flat = {}
+    for n, x in res.items():
+        if x is None:
+            continue
+        flat[n] = torch.cat([y.reshape(-1) for band in x for y in band]) if isinstance(x, list) else x.reshape(-1)
+    return flat
+
+
+def attn_inputs(dtype, D, heads, B, H, W, L, mode, shift, lfs, score_std=None, lam_scale=0.3, seed=0):
+    """Seeded case: N(0, 1) operands rounded to `dtype`; with score_std, q and k are scaled so that scale * q.k has that standard
+    deviation (sigma_q = sigma_k = sqrt(score_std)); tables 0.5 N(0, 1); lambda = lam_scale N(0, 1) per (image, band, head), turned
+    into (a, b, c) = (1 + l2, -l2 / 64, l1 - l2) (lfs 2) or (1 + l1, -l1 / 64, 0) (lfs 1) in f32."""
+    g = torch.Generator().manual_seed(seed * 7919 + 31 * D + 17 * heads + B * H * W + 5 * L + mode + shift + lfs)
+    C, rows = D * heads, L * B * H * W
+    qkv = torch.randn(rows, 3 * C, generator=g)
+    if score_std:
+        qkv[:, :2 * C] *= score_std ** 0.5
+    dout = torch.randn(rows, C, generator=g)
+    tables = 0.5 * torch.randn(L * L, 225, heads, generator=g)
+    coef = None
+    if lfs:
+        lam = lam_scale * torch.randn(B, 2, heads, generator=g)
+        l1, l2 = (lam[:, 0], lam[:, 1]) if lfs == 2 else (torch.zeros_like(lam[:, 0]), lam[:, 0])
+        coef = torch.stack([1 + l2, -l2 / 64, (l1 - l2) if lfs == 2 else torch.zeros_like(l1)], -1).float().contiguous()
+    r = lambda t: t.to(dtype).float()
+    return WAttnCase(dtype, D, heads, B, H, W, L, mode, shift, lfs, r(qkv), r(dout), tables, coef)

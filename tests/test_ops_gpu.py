@@ -720,13 +720,18 @@ def test_lfs_lambda_heads(nb, NT):
 
 
 # ------------------------------------------------------------------------------------------------ shapes of the TIMED step (B = 16)
-# The bench runs B = 16 at 128x128.  At that size three code paths fire that the small cases above never reach:
-#   * fw_attn_fwd caps its grid at 4 096 workgroups and LOOPS over items (with a trailing barrier between items),
-#   * fw_attn_bwd's chunks walk many windows per workgroup, accumulating the bias gradient across them,
+# The bench runs B = 16 at 128x128.  At that size code paths fire that the small cases above never reach:
+#   * fw_attn_fwd / fw_attn_bwd dispatch these shapes to the v2 kernels -- attn2_fwd / attn2_bwd_kernel (decoder, encoder intra) and
+#     attn2x_fwd / attn2x_bwd_kernel (encoder inter, L = 3) -- whose 256 * per_cu / (heads * L) workgroups per head WALK 16 to 49
+#     windows each, prefetching the next window's tiles and accumulating the bias gradient (and d(a, b, c)) across the walk.  The
+#     4 096-workgroup cap and item loop of attn_fwd_kernel and the 1024 / (heads * L) chunks of attn_bwd_kernel (v1: inter-band
+#     with L = 2 only) are NOT reached from here; tests/test_window_attention_pin_gpu.py::test_v1_kernels_at_size runs them,
 #   * fw_dwconv_fwd / _bwd switch to the LDS-tiled kernel (dwconv_tile_kernel) once B*H*W*C >= 80 M elements.
 @pytest.mark.parametrize('dtype', DTYPES)
 def test_attention_decoder_timed_shape(dtype):
-    """decoderlayer_0 of the timed step: B = 16, 128x128, C = 112, 2 heads, LFS (3 bands), shifted -> 8 192 items > the 4 096 cap."""
+    """decoderlayer_0 of the timed step: B = 16, 128x128, C = 112, 2 heads, LFS (3 bands), shifted: 4 096 windows x 2 heads on
+    attn2_fwd / attn2_bwd_kernel<56, LFS 2>, 128 or 256 workgroups per head walking 32 or 16 windows each (256 windows per image: no
+    walk crosses an image)."""
     B, H, W, heads, shift, lfs, nb = 16, 128, 128, 2, 4, 2, 3
     C = 56 * heads
     qkv = q(rnd(B * H * W, 3 * C), dtype).requires_grad_(True)
