@@ -40,7 +40,7 @@ template <typename T> FW_DEV void store_vec(T* p, const float* f) { *reinterpret
 struct ConvArgs {
     const char* x; long ldx;            // channels [0, cin1)
     const char* x2; long ldx2;          // channels [cin1, cin) (or null)
-    int cin, cin1;                      // multiples of the 64-byte chunk
+    int cin, cin1;                      // cin: a multiple of the 64-byte chunk; cin1 < cin (with x2): a multiple of 64 channels
     const char* w;                      // T [coutp][9 * cin], tap-major; coutp = roundup(cout, 16)
     const float* bias;                  // [cout] or null
     char* out; long ldo; int out_f32;

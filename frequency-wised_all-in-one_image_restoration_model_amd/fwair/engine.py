@@ -16,7 +16,7 @@ import torch.distributed as dist
 
 from . import functional as Fn
 from . import ops
-from .lib import call
+from .lib import call, gc_quiet, graph_capture
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -411,11 +411,11 @@ class TrainEngine:
         torch.cuda.synchronize()
         ops.reserve_capture_tables()
         ga, gb, gc = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
-        with torch.cuda.graph(ga):
+        with graph_capture(ga):
             self._split_a(*self._static)
-        with torch.cuda.graph(gb, pool=ga.pool()):
+        with graph_capture(gb, pool=ga.pool()):
             self._out = self._split_b()
-        with torch.cuda.graph(gc, pool=ga.pool()):
+        with graph_capture(gc, pool=ga.pool()):
             self._optim()
         self._gsplit = (ga, gb, gc)
 
@@ -448,29 +448,30 @@ class TrainEngine:
             self._optim(1)
             return out
         if getattr(self, '_p1', None) is None:
-            static = (xq.clone(), xk.clone())
-            snap = self._snapshot()
-            s = torch.cuda.Stream()
-            s.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(s):
-                for _ in range(2):
-                    self._fwd_bwd_p1(*static); self.allreduce(self.n_enc); self._optim(1)
-            torch.cuda.current_stream().wait_stream(s)
-            torch.cuda.synchronize()
-            single = self.allreduce.world == 1
-            ops.reserve_capture_tables()
-            g1 = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g1):
-                out = self._fwd_bwd_p1(*static)
-                if single:
-                    self._optim(1)
-            g2 = None
-            if not single:
-                g2 = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(g2, pool=g1.pool()):
-                    self._optim(1)
-            self._restore(snap)
-            self._p1 = (static, g1, g2, out)
+            with gc_quiet():
+                static = (xq.clone(), xk.clone())
+                snap = self._snapshot()
+                s = torch.cuda.Stream()
+                s.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(s):
+                    for _ in range(2):
+                        self._fwd_bwd_p1(*static); self.allreduce(self.n_enc); self._optim(1)
+                torch.cuda.current_stream().wait_stream(s)
+                torch.cuda.synchronize()
+                single = self.allreduce.world == 1
+                ops.reserve_capture_tables()
+                g1 = torch.cuda.CUDAGraph()
+                with graph_capture(g1):
+                    out = self._fwd_bwd_p1(*static)
+                    if single:
+                        self._optim(1)
+                g2 = None
+                if not single:
+                    g2 = torch.cuda.CUDAGraph()
+                    with graph_capture(g2, pool=g1.pool()):
+                        self._optim(1)
+                self._restore(snap)
+                self._p1 = (static, g1, g2, out)
         static, g1, g2, out = self._p1
         if xq is not static[0]:
             static[0].copy_(xq, non_blocking=True); static[1].copy_(xk, non_blocking=True)
@@ -501,6 +502,7 @@ class TrainEngine:
         self.m.copy_(m); self.v.copy_(v); self.hyper.copy_(h); self.hyper_rest.copy_(hr)
         self.resync()
 
+    @gc_quiet()                                              # collect before the warm-up, no collection until the graphs exist
     def capture(self, xq, xk, clean, warmup=2):
         """Warm up eagerly on a side stream, then capture forward+backward (and, single-GPU, the optimizer) into HIP graphs."""
         self._static = (xq.clone(), xk.clone(), clean.clone())
@@ -537,14 +539,14 @@ class TrainEngine:
             self._gsplit = None
         ops.reserve_capture_tables()
         self._g1 = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self._g1):
+        with graph_capture(self._g1):
             self._out = self._fwd_bwd(*self._static)
             if single:
                 self._optim()
         self._g2 = None
         if not single:
             self._g2 = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self._g2, pool=self._g1.pool()):
+            with graph_capture(self._g2, pool=self._g1.pool()):
                 self._optim()
         self._restore(snap)
         self._graph = True

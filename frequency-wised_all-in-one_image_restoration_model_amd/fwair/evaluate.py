@@ -17,7 +17,7 @@ import sys
 import numpy as np
 import torch
 
-from .lib import call
+from .lib import call, gc_quiet, graph_capture
 
 
 def tile_origins(size, tile):
@@ -159,6 +159,7 @@ class EvalEngine:
         if self.packed is None or self.packed.numel() < plan['max_px']:
             self.packed = torch.empty(plan['max_px'], dtype=torch.float32, device=self.dev)
 
+    @gc_quiet()                                              # collect before the warm-up, no collection until the graph exists
     def _capture(self):
         cur = torch.cuda.current_stream()
         s = torch.cuda.Stream()
@@ -170,7 +171,7 @@ class EvalEngine:
         torch.cuda.synchronize()
         try:
             g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
+            with graph_capture(g):
                 self.gout = self.net(x_query=self.gin, x_key=self.gin)
             self._graph = g
         except RuntimeError as e:

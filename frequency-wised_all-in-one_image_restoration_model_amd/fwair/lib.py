@@ -1,6 +1,8 @@
 """ctypes binding of libfwair_hip.so.  Prototypes are parsed from include/fwair.h (the single source of
 truth for the C ABI), so the header, the library and this loader cannot drift apart silently."""
+import contextlib
 import ctypes
+import gc
 import os
 import re
 
@@ -95,3 +97,43 @@ def call(name, *args):
     if rc != 0:
         raise RuntimeError(f'fwair: {name} failed with code {rc} '
                            f'({"argument check at source line " + str(-rc) if rc < 0 else "hipError"})')
+
+
+_quiet_depth = 0
+
+
+@contextlib.contextmanager
+def gc_quiet():
+    """Collect Python's cyclic garbage now and keep the collector off until the block ends (its earlier state is restored).
+    Re-entrant: a nested region neither collects nor re-enables -- between a capture's warm-up steps and the capture itself the set
+    of live parameters must not change (functional.refresh_shadows builds its device table from it during the warm-up).
+    For the ONE thread that drives captures: the depth is a plain module global, so a region opened from a second thread while one is
+    open would neither collect nor restore; the engines capture from the thread that steps them, and nothing else opens one."""
+    global _quiet_depth
+    if _quiet_depth:
+        yield
+        return
+    gc.collect()
+    was_on = gc.isenabled()
+    gc.disable()
+    _quiet_depth = 1
+    try:
+        yield
+    finally:
+        _quiet_depth = 0
+        if was_on:
+            gc.enable()
+
+
+@contextlib.contextmanager
+def graph_capture(graph, **kw):
+    """torch.cuda.graph(graph, **kw) with Python's cyclic garbage collector out of the way.  torch.cuda.graph no longer collects on
+    entry (torch.compiler.config.force_cudagraph_gc is off by default), so a collection that falls INSIDE the capture -- on this
+    thread or on autograd's -- runs the destructors of whatever dead cycle is around: an engine of an earlier run with its graphs,
+    private pools, streams and parameters (whose weak references edit functional's shadow tables).  A capture has aborted the
+    process with the collector running on autograd's thread inside it; that it was the release of such objects under the capture is
+    inferred from that traceback, not demonstrated.  Callers that warm up first open gc_quiet() around
+    the warm-up AND the capture, so that the collection happens before both."""
+    with gc_quiet():
+        with torch.cuda.graph(graph, **kw):
+            yield

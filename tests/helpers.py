@@ -864,3 +864,561 @@ def attn_inputs(dtype, D, heads, B, H, W, L, mode, shift, lfs, score_std=None, l
         coef = torch.stack([1 + l2, -l2 / 64, (l1 - l2) if lfs == 2 else torch.zeros_like(l1)], -1).float().contiguous()
     r = lambda t: t.to(dtype).float()
     return WAttnCase(dtype, D, heads, B, H, W, L, mode, shift, lfs, r(qkv), r(dout), tables, coef)
+
+
+# ------------------------------------------------------------------------------------------------ convolutional plug-ins (csrc/fw_conv.hip)
+# Plain f64 statements of the 15 entries, written from include/fwair.h and the reference operators (nn.Conv2d, nn.BatchNorm2d, the
+# published DCNv2 definition), with element-wise bounds counted from the kernels' roundings.  Every statement is a function of a float
+# type `ft` and a storage rounding `rs`: ft = f64, rs = identity is the reference; ft = f32 with rs = the operand type's rounding is
+# the honest emulation tests/test_conv_bounds_cpu.py holds against the bounds; `mutation` names one of the wrong kernels the bounds
+# must reject.  Nothing here imports fwair.convnets.
+CONV_MUTATIONS = ('taps_not_flipped', 'halo_shift', 'border_clamped', 'bias_after_act', 'res_before_act', 'cin1_off_group',
+                  'stride2_at_2o')
+BN_MUTATIONS = ('biased_running_var', 'rstd_no_eps', 'dres_before_slope')
+DCN_MUTATIONS = ('validity_ignored', 'mask_no_sigmoid_grad', 'offsets_swapped')
+
+
+def rup(v, m):
+    return (v + m - 1) // m * m
+
+
+def conv_chunk(dtype):
+    """elements of one 64-byte MFMA K chunk"""
+    return 32 if dtype == torch.bfloat16 else 16
+
+
+def storage_rounding(dtype):
+    """rs(t): t rounded to `dtype` (round to nearest even), in t's own float type"""
+    return (lambda t: t) if dtype in (torch.float32, torch.float64) else (lambda t: t.to(dtype).to(t.dtype))
+
+
+def conv_out_size(n, stride):
+    return (n - 1) // stride + 1
+
+
+def conv_panel_ref(weight, cin, kind='fwd', flip=True):
+    """weight [Co, Ci, k, k] (k = 1 | 3) -> the tap-major panel fw_conv3x3 reads, in weight's float type.
+    'fwd':   [roundup(Co, 16)][9 * cin], element (co, tap, ci); a 1x1 weight sits at the centre tap; cin >= Ci, zero beyond Ci.
+    'dgrad': [roundup(Ci, 16)][9 * cin], element (ci, 8 - tap, co); cin >= Co.  The input gradient of a stride-1 convolution is the
+             convolution of dy with this panel.  flip=False leaves the taps unflipped (a mutation).
+    Rows above Co (Ci) are zero."""
+    Co, Ci, k, _ = weight.shape
+    if kind == 'fwd':
+        out = torch.zeros(rup(Co, 16), 9, cin, dtype=weight.dtype)
+        if k == 3:
+            out[:Co, :, :Ci] = weight.reshape(Co, Ci, 9).transpose(1, 2)
+        else:
+            out[:Co, 4, :Ci] = weight.reshape(Co, Ci)
+    else:
+        assert k == 3
+        out = torch.zeros(rup(Ci, 16), 9, cin, dtype=weight.dtype)
+        w = weight.reshape(Co, Ci, 9).permute(1, 2, 0)                    # (ci, tap, co)
+        out[:Ci, :, :Co] = w.flip(1) if flip else w
+    return out.reshape(out.shape[0], 9 * cin)
+
+
+def _tap_rows(B, H, W, S, oy_shift=0, ix_shift=0):
+    """-> (rows [B*Ho*Wo, 9] clamped source row of every tap, ok [B*Ho*Wo, 9] inside the image): iy = oy*S - 1 + ky, ix = ox*S - 1 + kx"""
+    Ho, Wo = conv_out_size(H, S), conv_out_size(W, S)
+    tap = torch.arange(9)
+    iy = (torch.arange(Ho) * S - 1 + oy_shift)[:, None, None] + (tap // 3)[None, None, :]
+    ix = (torch.arange(Wo) * S - 1 + ix_shift)[None, :, None] + (tap % 3)[None, None, :]
+    ok = (iy >= 0) & (iy < H) & (ix >= 0) & (ix < W)
+    row = iy.clamp(0, H - 1) * W + ix.clamp(0, W - 1)
+    rows = (torch.arange(B)[:, None, None, None] * (H * W) + row[None]).reshape(-1, 9)
+    return rows, ok[None].expand(B, Ho, Wo, 9).reshape(-1, 9)
+
+
+def im2col3_ref(x, B, H, W, C, stride, mutation=None):
+    """x [B*H*W, >= C] -> col [B*Ho*Wo, 9 * C]: col[(b, oy, ox)][tap * C + c] = x[(b, oy*S - 1 + ky, ox*S - 1 + kx)][c], 0 outside the
+    image (pad columns of x are never read).  A data mover: exact in every type."""
+    s = 1 if mutation == 'stride2_at_2o' else 0                            # both axes read S o .. S o + 2 in place of S o - 1 .. S o + 1
+    rows, ok = _tap_rows(B, H, W, stride, oy_shift=s, ix_shift=s + (1 if mutation == 'halo_shift' else 0))
+    col = x[:, :C][rows]                                                   # [Mo, 9, C]
+    if mutation != 'border_clamped':
+        col = torch.where(ok[..., None], col, torch.zeros((), dtype=col.dtype))
+    return col.reshape(rows.shape[0], 9 * C)
+
+
+def col2im3_ref(dcol, B, H, W, C, stride):
+    """the adjoint of im2col3_ref: dx[(b, y, x)][c] = sum of dcol[(b, oy, ox)][tap * C + c] over the (oy, ox, tap) that read (y, x).
+    -> (dx [B*H*W, C], mag = the same sum of magnitudes) in dcol's type"""
+    rows, ok = _tap_rows(B, H, W, stride)
+    d = dcol.reshape(-1, 9, C) * ok[..., None].to(dcol.dtype)
+    dx = torch.zeros(B * H * W, C, dtype=dcol.dtype).index_add_(0, rows.reshape(-1), d.reshape(-1, C))
+    mag = torch.zeros(B * H * W, C, dtype=dcol.dtype).index_add_(0, rows.reshape(-1), d.abs().reshape(-1, C))
+    return dx, mag
+
+
+COL2IM_ROUNDINGS = 9              # at most 9 taps land on one pixel: 8 additions, and one spare
+
+
+def col2im3_bound(dx, mag, dtype):
+    tol = COL2IM_ROUNDINGS * U32 * mag
+    return tol + UBF * (dx.abs() + tol) if dtype == torch.bfloat16 else tol
+
+
+def popcount(v):
+    return bin(v).count('1')
+
+
+CONV_LRELU_ROUNDINGS = 1          # x * slope
+
+
+def conv3x3_ref(x, x2, cin, cin1, panel, bias, res, cout, B, H, W, stride, taps, act, slope, out_dtype, ft=torch.float64,
+                mutation=None):
+    """fw_conv3x3 in float type ft.  x [B*H*W, >= cin1], x2 [B*H*W, >= cin - cin1] or None (channels [0, cin1) from x, the rest from
+    x2), panel [roundup(cout, 16), 9 * cin] (conv_panel_ref), bias [cout] f32 or None, res [Mo, >= cout] or None; order: + bias,
+    LeakyReLU (act 1), + res.  out_dtype: the type the output is STORED in.
+    -> (value [Mo, cout], tol [Mo, cout]).  The bound is the GEMM bound (GemmRef on the f64 im2col operand, K = popcount(taps) * cin,
+    plus GEMM_EPI_ROUNDINGS for the epilogue), carried through LeakyReLU (Lipschitz max(1, |slope|), one product) and the storage
+    rounding; the f32 emulation passes tol = None."""
+    split = cin1 + (64 if mutation == 'cin1_off_group' else 0)           # the mutation switches sources one 64-channel group late
+    assert x2 is None or x.shape[1] >= split
+    src = x[:, :cin].to(ft) if x2 is None else torch.cat([x[:, :split], x2[:, split - cin1:cin - cin1]], 1).to(ft)
+    mask = torch.tensor([(taps >> t) & 1 for t in range(9)], dtype=ft).repeat_interleave(cin)
+    w = panel[:cout].to(ft) * mask
+    K = popcount(taps & 0x1ff) * cin
+    M1, Mo1 = H * W, conv_out_size(H, stride) * conv_out_size(W, stride)
+    vals, tols = [], []
+    for b in range(B):                                                     # one image at a time keeps the operand small
+        col = im2col3_ref(src[b * M1:(b + 1) * M1], 1, H, W, cin, stride, mutation)
+        ref = GemmRef(col, w)
+        v, mag = ref.acc, ref.mag
+        r = res[b * Mo1:(b + 1) * Mo1, :cout].to(ft) if res is not None else None
+        bv = bias.to(ft) if bias is not None else None
+        if bv is not None and mutation != 'bias_after_act':
+            v, mag = v + bv, mag + bv.abs()
+        if r is not None and mutation == 'res_before_act':
+            v = v + r
+        tol = (K + GEMM_EPI_ROUNDINGS) * U32 * mag
+        if act == 1:
+            tol = max(1.0, abs(slope)) * tol + CONV_LRELU_ROUNDINGS * U32 * v.abs()
+            v = torch.where(v > 0, v, v * f32c(slope))
+        if bv is not None and mutation == 'bias_after_act':
+            v = v + bv
+        if r is not None and mutation != 'res_before_act':
+            v, tol = v + r, tol + (K + GEMM_EPI_ROUNDINGS) * U32 * r.abs()
+        if out_dtype == torch.bfloat16:
+            tol = tol + UBF * (v.abs() + tol)
+        vals.append(v); tols.append(tol)
+    v = torch.cat(vals)
+    return (v, torch.cat(tols)) if ft == torch.float64 else (storage_rounding(out_dtype)(v), None)
+
+
+# ---- DCNv2 (fw_dcn_im2col / fw_dcn_bwd).  om [M, 32] f32: 2k / 2k + 1 = (dy, dx) of tap k, 18 + k = mask logit, 27..31 unused.
+# The kernels form the sample point in f32: py = float(y + ky - 1) + dy is ONE f32 addition of an exact integer and the stored offset,
+# and the reference takes exactly that f32 value (the statement is "at the stored inputs"); floor and the fractions wy = py - floor(py)
+# are then exact.  What is left to count, per term w * a * m of the sample:
+#   1 - wy, 1 - wx (one rounding each), their product, the product with the pixel, the sum of the four corners (3), the product with m
+DCN_TERM_ROUNDINGS = 8
+# m = 1 / (1 + __expf(-o)): the exp argument (product with log2 e and its f32 value: relative 3 u |o| of the result), v_exp_f32 1 ulp,
+# the sum 1 + e, the division (1 ulp); e / (1 + e) <= 1 scales the first two
+DCN_SIGMOID_ROUNDINGS = 3         # 1 + e, the division (2 u)
+DCN_WAVE_FOLD = 6
+
+
+def dcn_sigmoid_err(o):
+    """relative error of the kernels' sigmoid(o), o an f64 tensor of f32 logits"""
+    return ATTN_EXP_ARG_ROUNDINGS * U32 * o.abs() + ATTN_EXP_VALUE_ERR + DCN_SIGMOID_ROUNDINGS * U32
+
+
+def _dcn_geometry(om, B, H, W, ft, mutation=None):
+    """per tap k: dict(rows [4][M] clamped corner rows (00, 01, 10, 11), valid [4][M], wy, wx [M] in ft, m [M] in ft)"""
+    M = B * H * W
+    p = torch.arange(M)
+    xx, yy, b0 = p % W, (p // W) % H, (p // (W * H)) * (H * W)
+    o32 = om.float()
+    taps = []
+    for k in range(9):
+        iy, ix = (2 * k + 1, 2 * k) if mutation == 'offsets_swapped' else (2 * k, 2 * k + 1)
+        py = (yy + (k // 3 - 1)).float() + o32[:, iy]                      # the kernel's single f32 addition
+        px = (xx + (k % 3 - 1)).float() + o32[:, ix]
+        fy, fx = py.floor(), px.floor()
+        wy, wx = (py - fy).to(ft), (px - fx).to(ft)                        # exact in f32
+        y0, x0 = fy.long(), fx.long()
+        vy = [(y0 >= 0) & (y0 < H), (y0 + 1 >= 0) & (y0 + 1 < H)]
+        vx = [(x0 >= 0) & (x0 < W), (x0 + 1 >= 0) & (x0 + 1 < W)]
+        cy = [y0.clamp(0, H - 1), (y0 + 1).clamp(0, H - 1)]
+        cx = [x0.clamp(0, W - 1), (x0 + 1).clamp(0, W - 1)]
+        rows = [b0 + cy[i] * W + cx[j] for i in (0, 1) for j in (0, 1)]
+        valid = [vy[i] & vx[j] for i in (0, 1) for j in (0, 1)]
+        if mutation == 'validity_ignored':
+            valid = [torch.ones_like(v) for v in valid]
+        logit = om[:, 18 + k].to(ft)
+        m = 1 / (1 + torch.exp(-logit))
+        taps.append(dict(rows=rows, valid=valid, wy=wy, wx=wx, m=m, logit=om[:, 18 + k].double()))
+    return taps
+
+
+def _dcn_weights(t):
+    wy, wx = t['wy'], t['wx']
+    return [(1 - wy) * (1 - wx), (1 - wy) * wx, wy * (1 - wx), wy * wx]
+
+
+def dcn_im2col_ref(x, om, B, H, W, C, out_dtype, ft=torch.float64, mutation=None):
+    """col[p][k * C + c] = sigmoid(om[p][18 + k]) * sum over the four corners of w_corner * x[corner][c], a corner outside the image
+    counting as zero.  x [M, >= C] storage-rounded values, om [M, 32] f32.  -> (col [M, 9 * C], tol); f32 emulation: tol = None."""
+    xs = x[:, :C].to(ft)
+    cols, tols = [], []
+    for t in _dcn_geometry(om, B, H, W, ft, mutation):
+        s, mag = 0, 0
+        for w, r, v in zip(_dcn_weights(t), t['rows'], t['valid']):
+            term = torch.where(v[:, None], w[:, None] * xs[r], torch.zeros((), dtype=ft))
+            s, mag = s + term, mag + term.abs()
+        m = t['m'][:, None]
+        v = s * m
+        tol = (DCN_TERM_ROUNDINGS * U32 + dcn_sigmoid_err(t['logit'])[:, None].to(ft)) * mag * m
+        if out_dtype == torch.bfloat16:
+            tol = tol + UBF * (v.abs() + tol)
+        cols.append(v); tols.append(tol)
+    col = torch.cat(cols, 1)
+    return (col, torch.cat(tols, 1)) if ft == torch.float64 else (storage_rounding(out_dtype)(col), None)
+
+
+def dcn_bwd_ref(dcol, x, om, B, H, W, C, dx0=None, ft=torch.float64, mutation=None):
+    """the backward of dcn_im2col_ref from g = dcol [M, 9 * C]:
+      dx[corner][c] += g m w_corner (valid corners only; a scatter, f32 atomics in the kernel), on top of dx0 [M, C]
+      dom[p][2k] = sum_c g m ((1 - wx)(a10 - a00) + wx (a11 - a01)),  dom[p][2k + 1] likewise in x,
+      dom[p][18 + k] = (sum_c g val) m (1 - m);  a = the corner values, zero where invalid;  columns 27..31 are not written.
+    -> dict dx, dom [M, 27] with tol_dx, tol_dom (f64) or just dx, dom (emulation)"""
+    M = B * H * W
+    xs, g = x[:, :C].to(ft), dcol.to(ft).reshape(M, 9, C)
+    dx = torch.zeros(M, C, dtype=ft) if dx0 is None else dx0.to(ft).clone()
+    dxmag, adds = dx.abs().clone(), torch.zeros(M, dtype=ft)
+    dxrel = torch.zeros(M, C, dtype=ft)                                    # sum of |term| * the term's own relative error
+    dom, tdom = torch.zeros(M, 27, dtype=ft), torch.zeros(M, 27, dtype=ft)
+    chain = -(-C // 64) + DCN_WAVE_FOLD
+    for k, t in enumerate(_dcn_geometry(om, B, H, W, ft, mutation)):
+        gk, m, wy, wx = g[:, k], t['m'][:, None], t['wy'][:, None], t['wx'][:, None]
+        em = dcn_sigmoid_err(t['logit'])[:, None].to(ft)
+        a = [torch.where(v[:, None], xs[r], torch.zeros((), dtype=ft)) for r, v in zip(t['rows'], t['valid'])]
+        for w, r, v in zip(_dcn_weights(t), t['rows'], t['valid']):
+            term = torch.where(v[:, None], gk * m * w[:, None], torch.zeros((), dtype=ft))
+            dx.index_add_(0, r, term)
+            dxmag.index_add_(0, r, term.abs())
+            dxrel.index_add_(0, r, term.abs() * (6 * U32 + em))            # g m, 1 - wy, 1 - wx, two products, and one spare
+            adds.index_add_(0, r, v.to(ft))
+        val = (1 - wy) * ((1 - wx) * a[0] + wx * a[1]) + wy * ((1 - wx) * a[2] + wx * a[3])
+        vmag = (1 - wy) * ((1 - wx) * a[0].abs() + wx * a[1].abs()) + wy * ((1 - wx) * a[2].abs() + wx * a[3].abs())
+        gy = (1 - wx) * (a[2] - a[0]) + wx * (a[3] - a[1])
+        gymag = (1 - wx) * (a[2].abs() + a[0].abs()) + wx * (a[3].abs() + a[1].abs())
+        gx = (1 - wy) * (a[1] - a[0]) + wy * (a[3] - a[2])
+        gxmag = (1 - wy) * (a[1].abs() + a[0].abs()) + wy * (a[3].abs() + a[2].abs())
+        sm, smag = (gk * val).sum(1), (gk.abs() * vmag).sum(1)
+        m1, e1 = t['m'], em[:, 0]
+        dom[:, 2 * k], dom[:, 2 * k + 1] = (gk * m * gy).sum(1), (gk * m * gx).sum(1)
+        if mutation == 'mask_no_sigmoid_grad':
+            dom[:, 18 + k] = sm
+        else:
+            dom[:, 18 + k] = sm * m1 * (1 - m1)
+        per = (DCN_TERM_ROUNDINGS + chain) * U32
+        tdom[:, 2 * k] = (per + e1) * (gk.abs() * m * gymag).sum(1)
+        tdom[:, 2 * k + 1] = (per + e1) * (gk.abs() * m * gxmag).sum(1)
+        # m (1 - m): |dm| = m e1; 1.0f - m carries |dm| and its own rounding ABSOLUTELY (m next to 1 loses 1 - m altogether)
+        dm = m1 * e1
+        d1m = dm + U32 * (1 - m1) + U32 * m1
+        tdom[:, 18 + k] = per * smag * m1 * (1 - m1) + smag * (dm * (1 - m1) + m1 * d1m + 2 * U32 * m1 * (1 - m1))
+    if ft != torch.float64:
+        return dict(dx=dx, dom=dom)
+    tol_dx = dxrel + (adds[:, None] + 1) * U32 * dxmag
+    return dict(dx=dx, dom=dom, tol_dx=tol_dx, tol_dom=tdom, adds=adds)
+
+
+# ---- BatchNorm2d on a token-major map (fw_bn_cl_fwd / fw_bn_cl_bwd).  The kernels take the batch variance in ONE pass,
+#     var = E[x^2] - mean^2 from f32 column sums,
+# so the error of the two sums, each relative to its own magnitude, lands on var relative to E[x^2] = var (1 + mean^2 / var): the
+# conditioning factor BN_COND below, stated in the bound explicitly.  The reference takes mean and variance in two passes in f64.
+# Column sums: a thread adds ceil(rows / (grid * RL)) values, then one atomic per thread lands on the word: grid * RL of them.
+BN_MEAN_ROUNDINGS = 1             # sum / rows
+BN_VAR_ROUNDINGS = 7              # x * x, the division, mean * mean, the difference, and E|x| |mean| <= E[x^2] taken twice for d(mean^2)
+RSQRT_ERR = 2 * U32               # rsqrtf: 1 ulp
+BN_APPLY_ROUNDINGS = 5            # x - mean, * rstd, * gamma, + beta, + res
+BN_BWD_ROUNDINGS = 8              # dz * slope, x - mean, * rstd (xh), gamma * rstd, 1 / rows, two products, two differences (fma halves them)
+
+
+def bn_grid(rows, C):
+    """-> (blocks, RL): the launch of colstats_kernel / bn_bwd_stats_kernel by the contract of fw_bn_cl_*"""
+    RL = max(256 // (C // 4), 1)
+    return min(-(-rows // RL), 1024), RL
+
+
+def bn_chain(rows, C):
+    """longest chain of f32 additions between one value and its column sum"""
+    grid, RL = bn_grid(rows, C)
+    lanes = min(rows, grid * RL)
+    return -(-rows // lanes) + lanes
+
+
+def bn_cond(mean, var):
+    """1 + mean^2 / var (inf where var == 0)"""
+    return 1 + mean * mean / var
+
+
+def bn_cl_fwd_ref(x, gamma, beta, rmean, rvar, res, C, training, eps, momentum, slope, out_dtype, ft=torch.float64, mutation=None):
+    """x [rows, >= C] storage-rounded, gamma / beta / rmean / rvar [C] f32, res [rows, >= C] or None.
+    y = lrelu((x - mean) rstd gamma + beta [+ res], slope) (slope 1.0: no activation); train: batch statistics (two passes in f64),
+    running statistics r' = r (1 - momentum) + momentum s with the UNBIASED variance rows / max(rows - 1, 1); eval: running statistics.
+    -> dict y, mean, rstd, rmean, rvar [, tol_*] (f64), or the f32 emulation's values (one-pass variance, as the kernel)."""
+    rows = x.shape[0]
+    xs = x[:, :C].to(ft)
+    eps, momentum, slope = f32c(eps), f32c(momentum), f32c(slope)
+    g, b, rm, rv = (t.to(ft) for t in (gamma, beta, rmean, rvar))
+    emul = ft != torch.float64
+    out = {}
+    if training:
+        if emul:
+            mean = xs.sum(0) / rows
+            var = ((xs * xs).sum(0) / rows - mean * mean).clamp_min(0)
+        else:
+            mean = xs.mean(0)
+            var = ((xs - mean) ** 2).mean(0)
+        unb = 1.0 if mutation == 'biased_running_var' else rows / max(rows - 1, 1)
+        rstd = 1 / (var.sqrt() if mutation == 'rstd_no_eps' else (var + eps).sqrt())
+        out['rmean'], out['rvar'] = rm * (1 - momentum) + momentum * mean, rv * (1 - momentum) + momentum * var * unb
+        if not emul:
+            chain = bn_chain(rows, C)
+            cond = bn_cond(mean, var)
+            ex2 = torch.where(var > 0, var * cond, mean * mean)             # E[x^2] = var (1 + mean^2 / var)
+            e_mean = (chain + BN_MEAN_ROUNDINGS) * U32 * xs.abs().mean(0)
+            e_var = (3 * chain + BN_VAR_ROUNDINGS) * U32 * ex2
+            hi, lo = 1 / ((var - e_var).clamp_min(0) + eps).sqrt(), 1 / (var + e_var + eps).sqrt()
+            e_rstd = torch.maximum(hi - rstd, rstd - lo) + (U32 + RSQRT_ERR) * hi
+            out['tol_rmean'] = momentum * e_mean + 3 * U32 * ((rm * (1 - momentum)).abs() + (momentum * mean).abs())
+            out['tol_rvar'] = momentum * unb * e_var + 5 * U32 * ((rv * (1 - momentum)).abs() + momentum * var * unb)
+            out['cond'] = cond
+    else:
+        mean, var = rm, rv
+        rstd = 1 / (var + eps).sqrt()
+        out['rmean'], out['rvar'] = rm, rv
+        if not emul:
+            e_mean, e_rstd = torch.zeros_like(mean), (U32 + RSQRT_ERR) * rstd
+            out['tol_rmean'] = out['tol_rvar'] = torch.zeros_like(mean)
+    d = xs - mean
+    t = d * rstd * g
+    v = t + b
+    r = res[:, :C].to(ft) if res is not None else None
+    if r is not None:
+        v = v + r
+    y = torch.where(v > 0, v, v * slope)
+    out.update(y=y, mean=mean, rstd=rstd)
+    if emul:
+        out['y'] = storage_rounding(out_dtype)(y)
+        return out
+    tol = g.abs() * (d.abs() * e_rstd + (rstd + e_rstd) * e_mean) \
+        + BN_APPLY_ROUNDINGS * U32 * (t.abs() + b.abs() + (r.abs() if r is not None else 0))
+    tol = max(1.0, abs(slope)) * tol + U32 * v.abs()
+    out['tol_y'] = tol + UBF * (y.abs() + tol) if out_dtype == torch.bfloat16 else tol
+    out['tol_mean'], out['tol_rstd'] = e_mean + U32 * mean.abs(), e_rstd
+    return out
+
+
+def bn_cl_bwd_ref(dy, y, x, mean, rstd, gamma, C, training, slope, out_dtype, ft=torch.float64, mutation=None):
+    """dz = dy * (slope where y < 0) (slope 1.0: dz = dy, y is not read); s0 = sum dz = d(beta), s1 = sum dz xh = d(gamma),
+    xh = (x - mean) rstd with the GIVEN mean / rstd [C] (f32 values); dx = gamma rstd (dz - s0 / rows - xh s1 / rows) (train) or
+    gamma rstd dz (eval); dres = dz.  -> dict dx, dres, sums [2, C] [, tol_*]"""
+    rows = x.shape[0]
+    slope = f32c(slope)
+    dz = dy[:, :C].to(ft)
+    if slope != 1.0:
+        dz = torch.where(y[:, :C].to(ft) < 0, dz * slope, dz)
+    mean, rstd, g = mean.to(ft), rstd.to(ft), gamma.to(ft)
+    xh = (x[:, :C].to(ft) - mean) * rstd
+    s0, s1 = dz.sum(0), (dz * xh).sum(0)
+    gr = g * rstd
+    dx = gr * (dz - s0 / rows - xh * s1 / rows) if training else gr * dz
+    rs = storage_rounding(out_dtype)
+    dres = dy[:, :C].to(ft) if mutation == 'dres_before_slope' else dz
+    if ft != torch.float64:
+        return dict(dx=rs(dx), dres=rs(dres), sums=torch.stack([s0, s1]))
+    chain = bn_chain(rows, C)
+    t0, t1 = (chain + 1) * U32 * dz.abs().sum(0), (chain + 4) * U32 * (dz * xh).abs().sum(0)
+    mag = dz.abs() + (s0 / rows).abs() + (xh * s1 / rows).abs() if training else dz.abs()
+    tol = gr.abs() * ((t0 + xh.abs() * t1) / rows if training else 0) + BN_BWD_ROUNDINGS * U32 * gr.abs() * mag
+    st = (lambda v, t: t + UBF * (v.abs() + t)) if out_dtype == torch.bfloat16 else (lambda v, t: t)
+    return dict(dx=dx, dres=dres, sums=torch.stack([s0, s1]), tol_dx=st(dx, tol), tol_dres=st(dres, U32 * dz.abs()),
+                tol_sums=torch.stack([t0, t1]))
+
+
+# ---- the elementwise entries: one f32 expression per element, stored in the operand type
+def lrelu_ref(x, slope):
+    return torch.where(x > 0, x, x * f32c(slope))
+
+
+def lrelu_bwd_ref(dy, y, slope):
+    """from the OUTPUT's sign"""
+    return torch.where(y < 0, dy * f32c(slope), dy)
+
+
+def dgm_fwd_ref(x, dcn, gamma, beta, slope):
+    """-> (out, tol before the storage rounding): lrelu(x + dcn + x gamma + beta); four f32 operations on terms of these magnitudes"""
+    v = x + dcn + x * gamma + beta
+    return lrelu_ref(v, slope), 4 * U32 * (x.abs() + dcn.abs() + (x * gamma).abs() + beta.abs()) * max(1.0, abs(slope))
+
+
+def dgm_bwd_ref(dout, out, x, gamma, slope):
+    """-> dict dz, dx, dgamma and tol_* (before the storage rounding)"""
+    dz = torch.where(out < 0, dout * f32c(slope), dout)
+    dx, dg = dz * (1 + gamma), dz * x
+    return dict(dz=dz, dx=dx, dgamma=dg, tol_dz=U32 * dz.abs(), tol_dx=3 * U32 * dz.abs() * (1 + gamma.abs()), tol_dgamma=2 * U32 * dg.abs())
+
+
+def gap_cl_ref(x, B, P, C):
+    """[B * P, >= C] -> (mean over the P pixels [B, C], tol: P sequential f32 additions and the division)"""
+    v = x[:, :C].reshape(B, P, C)
+    return v.mean(1), (P + 1) * U32 * v.abs().mean(1)
+
+
+def gap_cl_bwd_ref(dgap, P):
+    """[B, C] -> [B * P, C]: dgap / P broadcast (one f32 division)"""
+    return (dgap / P).repeat_interleave(P, 0)
+
+
+def nchw_to_tokens_ref(img, Cp):
+    """f32 [B, Ci, HW] -> [B * HW, Cp], channels >= Ci zero"""
+    B, Ci, HW = img.shape
+    out = torch.zeros(B * HW, Cp, dtype=img.dtype)
+    out[:, :Ci] = img.permute(0, 2, 1).reshape(B * HW, Ci)
+    return out
+
+
+def tokens_to_nchw_ref(tok, B, Ci, HW):
+    return tok[:, :Ci].reshape(B, HW, Ci).permute(0, 2, 1).contiguous()
+
+
+def stored(value, tol, dtype):
+    """bound of a value after its rounding to the storage type"""
+    return tol + UBF * (value.abs() + tol) if dtype == torch.bfloat16 else tol + U32 * value.abs()
+
+
+# ---- seeded cases shared by tests/test_conv_bounds_cpu.py (host) and tests/test_conv_kernels_gpu.py (device)
+def dyadic(*shape, seed, lo, hi, denom):
+    """integers in [lo, hi] over denom (a power of two): sums of a few thousand of them are exact in f32, in any order"""
+    return torch.randint(lo, hi + 1, shape, generator=torch.Generator().manual_seed(seed)).float() / denom
+
+
+def padded(values, ld, pad=float('nan')):
+    """[rows, C] -> [rows, ld] with `pad` in the columns >= C"""
+    out = torch.full((values.shape[0], ld), pad, dtype=values.dtype)
+    out[:, :values.shape[1]] = values
+    return out
+
+
+class ConvCase:
+    """One fw_conv3x3 problem.  Operands are f32 tensors holding values already rounded to `dtype`; x / x2 / res carry `pad` in the
+    columns the kernel must not consume.  exact: x, res, bias = integers / 8, weights = small integers, slope 1/8, so every f32
+    partial sum is exact and the result does not depend on the order of summation.  dgrad: the operand is dy [M, cin] of a stride-1
+    convolution with weight [cin, cout, 3, 3] and the panel is the flipped, transposed one: the output is dx [M, cout]."""
+
+    def __init__(self, dtype, B, H, W, stride, cin, cout, k=3, cin1=None, bias=True, act=1, slope=0.1, res=True, out_f32=False,
+                 ldx=None, ldx2=None, ldr=None, ldo=None, pad=float('nan'), seed=0, dgrad=False, exact=False, flip=True):
+        self.dtype, self.geo, self.stride, self.cin, self.cout = dtype, (B, H, W), stride, cin, cout
+        self.cin1 = cin if cin1 is None else cin1
+        self.taps, self.act, self.slope = (0x1ff if k == 3 else 0x010), act, (0.125 if exact else slope)
+        self.out_dtype = torch.float32 if out_f32 or dtype == torch.float32 else dtype
+        self.out_f32 = int(out_f32)
+        self.Ho, self.Wo = conv_out_size(H, stride), conv_out_size(W, stride)
+        M, Mo = B * H * W, B * self.Ho * self.Wo
+        rs = storage_rounding(dtype)
+        s = 1000 * seed + 7 * cin + cout + H * W
+        if exact:
+            mk = lambda *sh, n: dyadic(*sh, seed=s + n, lo=-8, hi=8, denom=8)
+            wgt = dyadic(*((cin, cout) if dgrad else (cout, cin)), k, k, seed=s + 9, lo=-2, hi=2, denom=1)
+        else:
+            mk = lambda *sh, n: rs(signed_magnitudes(*sh, seed=s + n))
+            wgt = rs(signed_magnitudes(*((cin, cout) if dgrad else (cout, cin)), k, k, seed=s + 9))
+        xs = mk(M, cin, n=1)
+        self.x = padded(xs[:, :self.cin1], ldx or self.cin1, pad)
+        self.x2 = padded(xs[:, self.cin1:], ldx2 or cin - self.cin1, pad) if self.cin1 < cin else None
+        self.weight = wgt
+        self.panel = conv_panel_ref(wgt, cin, 'dgrad' if dgrad else 'fwd', flip)
+        self.bias = (mk(cout, n=2) if exact else signed_magnitudes(cout, seed=s + 2)) if bias else None
+        self.res = padded(mk(Mo, cout, n=3), ldr or cout, pad) if res else None
+        self.ldo = ldo or cout
+
+    def ref(self, ft=torch.float64, mutation=None):
+        B, H, W = self.geo
+        return conv3x3_ref(self.x, self.x2, self.cin, self.cin1, self.panel, self.bias, self.res, self.cout, B, H, W, self.stride,
+                           self.taps, self.act, self.slope, self.out_dtype, ft, mutation)
+
+    def tiles(self):
+        """output tiles of 4 x 16 pixels = workgroups asked for (the grid is capped at CONV_GRID_CAP)"""
+        return self.geo[0] * (-(-self.Ho // 4)) * (-(-self.Wo // 16))
+
+
+CONV_GRID_CAP = 2048
+BN_GRID_CAP = 1024
+DCN_BWD_GRID_CAP = 65536          # blocks of 4 waves, one (pixel, tap) per wave and trip
+
+
+def bn_inputs(dtype, rows, C, ratio=0.0, std=0.0625, seed=0, exact=False):
+    """-> dict x, res, dy [rows, C] (rounded to dtype), gamma, beta, rmean, rvar [C] f32.  Columns have |mean| / std = ratio.
+    exact: integers / 8 in [-1, 1], so sums of x and x^2 over up to 2^18 rows are exact in f32"""
+    s = 100 * seed + rows + C
+    rs = storage_rounding(dtype)
+    g = torch.Generator().manual_seed(s)
+    if exact:
+        x, dy, res = (dyadic(rows, C, seed=s + n, lo=-8, hi=8, denom=8) for n in (1, 2, 3))
+    else:
+        sign = torch.randint(0, 2, (C,), generator=g).float() * 2 - 1
+        x = rs(std * (torch.randn(rows, C, generator=g) + ratio * sign))
+        dy, res = rs(torch.randn(rows, C, generator=g)), rs(std * torch.randn(rows, C, generator=g))
+    u = lambda lo, hi: lo + (hi - lo) * torch.rand(C, generator=g)
+    return dict(x=x, dy=dy, res=res, gamma=u(0.5, 1.5) * (torch.randint(0, 2, (C,), generator=g).float() * 2 - 1), beta=std * u(-1, 1),
+                rmean=std * u(-1, 1), rvar=std * std * u(0.5, 1.5))
+
+
+DCN_BORDER_CLASSES = ('integer', 'above_top', 'below_bottom', 'far_before', 'far_after', 'mixed')
+
+
+def dcn_inputs(dtype, B, H, W, C, kind='random', seed=0, logit_scale=1.0):
+    """-> dict x [M, C], dcol [M, 9 * C] (rounded to dtype), om [M, 32] f32 (columns 27..31 hold NaN: never read).
+    kind 'random': offsets N(0, 1.5) (many samples leave a small image), or one border class for EVERY tap of every pixel:
+      'integer'      offsets in {-1, 0, 1}: the sample sits on a pixel, wy = wx = 0, the +1 corners weigh nothing
+      'above_top'    py in (-1, 0): the y0 = -1 corners are invalid, the y0 + 1 = 0 ones valid; same in x
+      'below_bottom' py in (H - 1, H): the y0 + 1 = H corners are invalid
+      'far_before'   py <= -1 and px < -1: no corner contributes (py = -1 exactly is among them: the y0 + 1 = 0 corners are then
+                     valid in y with weight 0, and px keeps all four outside);  'far_after'  py >= H and px > W: likewise
+      'mixed'        the classes above cycled over the taps of a pixel
+      'dyadic'       offsets drawn from {0, +-1, +-0.5}: bilinear weights in {0, 1/4, 1/2, 1}, logits 0 (m = 1/2 exactly)"""
+    M = B * H * W
+    g = torch.Generator().manual_seed(50 * seed + M + C)
+    rs = storage_rounding(dtype)
+    p = torch.arange(M)
+    yy, xx = ((p // W) % H).float()[:, None], (p % W).float()[:, None]
+    ky, kx = (torch.arange(9) // 3 - 1).float()[None], (torch.arange(9) % 3 - 1).float()[None]
+    frac = 0.125 + 0.75 * torch.rand(M, 9, 2, generator=g)
+
+    def target(cls):                                                       # sample points [M, 9] in y and x
+        if cls == 'integer':
+            d = torch.randint(-1, 2, (M, 9, 2), generator=g).float()
+            return yy + ky + d[..., 0], xx + kx + d[..., 1]
+        if cls == 'above_top':
+            return -frac[..., 0], -frac[..., 1]
+        if cls == 'below_bottom':
+            return H - 1 + frac[..., 0], W - 1 + frac[..., 1]
+        if cls == 'far_before':
+            return -1 - 2 * frac[..., 0] * (frac[..., 1] > 0.5), -1 - 3 * frac[..., 1]
+        return H + 2 * frac[..., 0] * (frac[..., 1] > 0.5), W + 3 * frac[..., 1]
+    om = torch.full((M, 32), float('nan'))
+    om[:, 18:27] = logit_scale * torch.randn(M, 9, generator=g)
+    if logit_scale >= 30:                                                  # exactly +-logit_scale: the sigmoid saturates, exp stays finite
+        om[:, 18:27] = logit_scale * torch.sign(om[:, 18:27])
+    if kind == 'random':
+        om[:, :18] = 1.5 * torch.randn(M, 18, generator=g)
+    elif kind == 'dyadic':
+        om[:, :18] = torch.tensor([0.0, 1.0, -1.0, 0.5, -0.5])[torch.randint(0, 5, (M, 18), generator=g)]
+        om[:, 18:27] = 0.0
+    else:
+        classes = DCN_BORDER_CLASSES[:5]
+        ty, tx = torch.zeros(M, 9), torch.zeros(M, 9)
+        for i, cls in enumerate(classes):
+            cy, cx = target(cls)
+            sel = torch.full((9,), kind == cls) if kind != 'mixed' else (torch.arange(9) % 5 == i)
+            ty, tx = torch.where(sel[None], cy + 0 * ty, ty), torch.where(sel[None], cx + 0 * tx, tx)
+        om[:, 0:18:2], om[:, 1:18:2] = ty - (yy + ky), tx - (xx + kx)
+    if kind == 'dyadic':
+        x, dcol = dyadic(M, C, seed=seed + 1, lo=-8, hi=8, denom=8), dyadic(M, 9 * C, seed=seed + 2, lo=-4, hi=4, denom=4)
+    else:
+        x, dcol = rs(signed_magnitudes(M, C, seed=seed + 1)), rs(signed_magnitudes(M, 9 * C, seed=seed + 2))
+    return dict(x=x, dcol=dcol, om=om)
