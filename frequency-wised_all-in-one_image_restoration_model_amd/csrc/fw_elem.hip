@@ -1765,6 +1765,8 @@ extern "C" int fw_lrelu_bwd(int dtype, const void* dy, const float* x, float* dx
 }
 // dst must be pre-initialised when accumulate != 0 (the z range may then be split over blockIdx.y with atomics).
 // zstride and the segment [0, max(n, off2 + n2)) rounded up to 4 must lie inside every slab row.
+// accumulate == 2: add like 1, but one block keeps the whole z range -- one read-modify-write per address, no atomics, so the same
+// inputs give the same bits (fw_modulator_bwd).
 extern "C" int fw_slab_reduce(const float* slab, int nz, long n, long zstride, float* dst, int accumulate, float* dst2, long off2, long n2,
                               void* stream) {
     FW_CHECK_ARG(slab && dst && nz > 0 && n > 0 && zstride % 4 == 0 && ((uintptr_t)slab & 15) == 0);
@@ -1772,7 +1774,7 @@ extern "C" int fw_slab_reduce(const float* slab, int nz, long n, long zstride, f
     const long end = dst2 ? off2 + n2 : n;
     const long gx = ((end + 3) / 4 + 63) / 64;
     int zper = nz;                                  // plain stores need the whole z range in one block
-    if (accumulate) {                               // aim at >= ~1024 blocks, at least 8 slab rows per block
+    if (accumulate && accumulate != 2) {                         // aim at >= ~1024 blocks, at least 8 slab rows per block
         long splits = 1024 / gx;
         if (splits > nz / 8) splits = nz / 8;
         if (splits < 1) splits = 1;

@@ -5,6 +5,9 @@
 //   fwd : y[T] = (x - mean) * rstd * gamma + beta ; saves mean, rstd (fp32)
 //   bwd : dx[f32] = (dres?) + rstd * (g - mean(g) - xhat * mean(g*xhat)),  g = dy * gamma
 //         dgamma += sum_rows dy * xhat ; dbeta += sum_rows dy      (block partials -> atomicAdd)
+//   learnable window modulator of the decoder blocks (decoder_Uformer.py:536-539,687-691):
+//   fwd : y[T] = LN(x) * gamma + beta + mod[window position of the row]      (a compile-time branch of the forward kernel)
+//   bwd : dmod[p] += sum of dy over the rows at window position p            (slices by plain stores -> fw_slab_reduce, no atomics)
 #include "fw_common.h"
 #include <stdlib.h>
 
@@ -38,24 +41,40 @@ template <> struct RawV<bf16raw> {
 // pass ran at 2.8 TB/s.  Now a lane group owns U rows per step -- all their loads are issued back to back from CLAMPED coordinates
 // (no branch between them), then the rows are reduced and written -- and the per-lane arrays are sized by NV = ceil(C / 4 / G),
 // not by the C = 1024 maximum.  G lanes per row (16 / 32 / 64 by width) so that narrow rows (C = 28, 56) do not idle a wave.
-template <typename T, int G, int NV, int U>
+//
+// MOD (fw_layernorm_mod_fwd): the decoder's learnable window modulator (decoder_Uformer.py:536-539,687-691) rides on the same stream.
+// The reference adds an [64][C] table to the 64 tokens of every 8x8 window AFTER norm1, the cyclic shift and the window partition; the
+// token of row r = (b, yy, xx) of the [B*H*W, C] stream sits at window position p(r) = ((yy - s) & 7) * 8 + ((xx - s) & 7)
+// (roll(-s) puts pixel yy at rolled row (yy - s) mod H, and 8 | H), so  y[r] = T(LN(x[r]) * gamma + beta + mod[p(r)]).  The table rows
+// (<= 229 KB in all, L2-resident) are requested with the U rows of x, from the same clamped coordinates.  MOD is a compile-time branch:
+// the plain instantiations (MOD = false) compile every modulator statement out and never read the four trailing arguments.
+template <typename T, int G, int NV, int U, bool MOD = false>
 __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x, long ldx, const float* __restrict__ gamma,
                                                      const float* __restrict__ beta, T* __restrict__ y, long ldy,
                                                      float* __restrict__ mean, float* __restrict__ rstd, int rows,
-                                                     int C, float eps) {
+                                                     int C, float eps, const float* __restrict__ mod, int H, int W, int shift) {
     constexpr int RPB = 256 / G;
     const int gl = threadIdx.x % G, gr = threadIdx.x / G;
     const int nv = C >> 2;
     const long r0 = (long)blockIdx.x * RPB * U;
     f32x4 v[U][NV];
+    f32x4 mv[MOD ? U : 1][MOD ? NV : 1];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
         const long row = r0 + u * RPB + gr;
-        const float* xr = x + (row < rows ? row : rows - 1) * ldx;
+        const long rc = row < rows ? row : rows - 1;
+        const float* xr = x + rc * ldx;
+        const float* mr = nullptr;
+        if (MOD) {
+            const unsigned iy = (unsigned)rc / (unsigned)W;           // rows is an int: 32-bit divisions
+            const int xx = (int)((unsigned)rc - iy * (unsigned)W), yy = (int)(iy % (unsigned)H);
+            mr = mod + (long)((((yy - shift) & 7) << 3) + ((xx - shift) & 7)) * C;
+        }
 #pragma unroll
         for (int t = 0; t < NV; ++t) {
             const int c4 = gl + G * t;
             v[u][t] = *reinterpret_cast<const f32x4*>(xr + (c4 < nv ? c4 : nv - 1) * 4);
+            if (MOD) mv[u][t] = *reinterpret_cast<const f32x4*>(mr + (c4 < nv ? c4 : nv - 1) * 4);
         }
     }
     f32x4 gam[NV], bet[NV];
@@ -94,6 +113,10 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x
                 float o[4];
 #pragma unroll
                 for (int e = 0; e < 4; ++e) o[e] = (v[u][t][e] - mu) * rs * gam[t][e] + bet[t][e];
+                if (MOD) {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) o[e] += mv[u][t][e];
+                }
                 T* yp = y + row * ldy + c4 * 4;
                 if (sizeof(T) == 4) *reinterpret_cast<f32x4*>(yp) = f32x4{o[0], o[1], o[2], o[3]};
                 else *reinterpret_cast<uint2*>(yp) = make_uint2(pack_bf2(o[0], o[1]), pack_bf2(o[2], o[3]));
@@ -218,7 +241,15 @@ int ln_fwd_launch(const float* x, long ldx, const float* g, const float* b, void
                   float* rstd, int rows, int C, float eps, hipStream_t st) {
     const int rpb = 256 / G * U;
     hipLaunchKernelGGL((ln_fwd_kernel<T, G, NV, U>), dim3(fw_cdiv(rows, rpb)), dim3(256), 0, st, x, ldx, g, b, (T*)y, ldy,
-                       mean, rstd, rows, C, eps);
+                       mean, rstd, rows, C, eps, (const float*)nullptr, 1, 1, 0);
+    FW_LAUNCH_RET();
+}
+template <typename T, int G, int NV, int U>
+int ln_mod_fwd_launch(const float* x, long ldx, const float* g, const float* b, const float* mod, void* y, long ldy, float* mean,
+                      float* rstd, int rows, int C, int H, int W, int shift, float eps, hipStream_t st) {
+    const int rpb = 256 / G * U;
+    hipLaunchKernelGGL((ln_fwd_kernel<T, G, NV, U, true>), dim3(fw_cdiv(rows, rpb)), dim3(256), 0, st, x, ldx, g, b, (T*)y, ldy,
+                       mean, rstd, rows, C, eps, mod, H, W, shift);
     FW_LAUNCH_RET();
 }
 static inline int ln_group(int C) { return C <= 32 ? 8 : (C <= 64 ? 16 : (C <= 128 ? 32 : 64)); }
@@ -237,6 +268,105 @@ int ln_bwd_launch(const void* dy, long lddy, const float* x, long ldx, const flo
                   int rows, int C, void* twin, long ldtw, const float* twscale, int twrps, hipStream_t st) {
     hipLaunchKernelGGL((ln_bwd_kernel<T, G, NV, U>), dim3(ln_bwd_grid(rows, C)), dim3(256), 0, st, (const T*)dy, lddy, x, ldx, g, mean, rstd,
                        dres, lddres, dx, lddx, partial, pstride, rows, C, (T*)twin, ldtw, twscale, twrps);
+    FW_LAUNCH_RET();
+}
+
+// ---- gradient of the window modulator: dmod[p][c] = sum over the rows r with p(r) = p of dy[r][c] -----------------------------------
+// Every window holds each p once, so a sum has n = rows / 64 terms; the rows that share p are 8 tokens apart along x and 8 image rows
+// apart along y.  A workgroup owns one yq = (yy - s) & 7, a column chunk and one of nz slices of the n terms: its 8 groups of 32 lanes
+// take the eight xq = (xx - s) & 7, so the 8 * TG tokens the block requests at a time are consecutive in memory.  Inside a group CL
+// lanes span the chunk's columns (E elements each: 16 bytes of f32, 16 or -- rows not 16-byte aligned -- 8 bytes of bf16) and the
+// TG = 32 / CL token groups take every TG-th term; LD loads are issued from clamped terms before any is added.  The token groups are
+// folded through LDS in a fixed order and slice z stores its [64][C] partial with plain stores: no atomics, the same bits every call.
+template <typename T, int E> struct ModV;
+template <> struct ModV<float, 4> {
+    f32x4 v;
+    FW_MEM void load(const float* p) { v = *reinterpret_cast<const f32x4*>(p); }
+    FW_MEM void add(float* a) const { a[0] += v[0]; a[1] += v[1]; a[2] += v[2]; a[3] += v[3]; }
+};
+template <> struct ModV<bf16raw, 4> {
+    RawV<bf16raw> r;
+    FW_MEM void load(const bf16raw* p) { r.load(p); }
+    FW_MEM void add(float* a) const { float f[4]; r.unpack(f); a[0] += f[0]; a[1] += f[1]; a[2] += f[2]; a[3] += f[3]; }
+};
+template <> struct ModV<bf16raw, 8> {
+    uint4 v;
+    FW_MEM void load(const bf16raw* p) { v = *reinterpret_cast<const uint4*>(p); }
+    FW_MEM void add(float* a) const {
+        const unsigned w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+        for (int i = 0; i < 4; ++i) { a[2 * i] += __uint_as_float(w[i] << 16); a[2 * i + 1] += __uint_as_float(w[i] & 0xffff0000u); }
+    }
+};
+
+constexpr int MOD_LD = 8;        // loads a lane has in flight
+
+template <typename T, int E, int CL>
+__global__ __launch_bounds__(256) void mod_bwd_kernel(const T* __restrict__ dy, long lddy, float* __restrict__ partial, int n, int per,
+                                                      int C, int W, int shift) {
+    constexpr int TG = 32 / CL;
+    const int cl = threadIdx.x % CL, tg = threadIdx.x / CL % TG, xq = threadIdx.x / 32;
+    const int yq = blockIdx.y, z = blockIdx.z;
+    const int col = (blockIdx.x * CL + cl) * E;
+    const bool cok = col < C;                                  // E | C: a vector is inside the row or outside it
+    const int W8 = W >> 3;
+    const int g0 = (yq + shift) & 7, x0 = (xq + shift) & 7;      // first image row (of all B * H) and first token of this (yq, xq)
+    const int lo = z * per, hi = min(n, lo + per);              // terms of this slice: term u = (image row g0 + 8 (u / W8), token x0 + 8 (u % W8))
+    const T* base = dy + (cok ? col : 0);
+    float acc[E];
+#pragma unroll
+    for (int e = 0; e < E; ++e) acc[e] = 0.f;
+    for (int u = lo + tg; u < hi; u += TG * MOD_LD) {
+        ModV<T, E> v[MOD_LD];
+#pragma unroll
+        for (int i = 0; i < MOD_LD; ++i) {
+            const int uc = min(u + i * TG, hi - 1);
+            const int j = uc / W8, k = uc - j * W8;
+            v[i].load(base + ((long)(g0 + 8 * j) * W + x0 + 8 * k) * lddy);
+        }
+#pragma unroll
+        for (int i = 0; i < MOD_LD; ++i) {
+            if (u + i * TG < hi) v[i].add(acc);
+        }
+    }
+    if (TG > 1) {
+        __shared__ float red[256 * E];
+#pragma unroll
+        for (int e = 0; e < E; ++e) red[threadIdx.x * E + e] = acc[e];
+        __syncthreads();
+        if (tg == 0) {
+#pragma unroll
+            for (int t = 1; t < TG; ++t) {
+#pragma unroll
+                for (int e = 0; e < E; ++e) acc[e] += red[(threadIdx.x + t * CL) * E + e];
+            }
+        }
+    }
+    if (tg != 0 || !cok) return;
+    float* pp = partial + ((long)z * 64 + yq * 8 + xq) * C + col;
+#pragma unroll
+    for (int e = 0; e < E; e += 4) *reinterpret_cast<f32x4*>(pp + e) = f32x4{acc[e], acc[e + 1], acc[e + 2], acc[e + 3]};
+}
+
+// Slices of the n = rows / 64 terms.  Each slice writes a [64][C] f32 partial that the fold re-reads -- 2 nz / n of the bf16 bytes of
+// dy, twice -- so a slice keeps at least 16 terms (12.5 %); 32 slices put 8 * 32 * chunks = 256 .. 1024 workgroups on the 256 CUs at
+// the decoder's four shapes (batch 16, 128 x 128: n = 4096 / 1024 / 256 / 64 -> nz = 32 / 32 / 16 / 4), and the fold of <= 32 slices
+// needs no split of its own.
+static inline int mod_bwd_slices(int rows, int C) {
+    const int n = rows / 64;
+    return max(1, min(32, n / 16));
+}
+
+template <typename T, int E>
+int mod_bwd_launch(const void* dy, long lddy, float* partial, int rows, int C, int W, int shift, hipStream_t st) {
+    const int n = rows / 64, nz = mod_bwd_slices(rows, C), per = fw_cdiv(n, nz), nvr = C / E;
+#define MOD_B(CL)                                                                                                              \
+    hipLaunchKernelGGL((mod_bwd_kernel<T, E, CL>), dim3(fw_cdiv(nvr, CL), 8, nz), dim3(256), 0, st, (const T*)dy, lddy, partial, n, \
+                       per, C, W, shift)
+    if (nvr <= 8) MOD_B(8);
+    else if (nvr <= 16) MOD_B(16);
+    else MOD_B(32);
+#undef MOD_B
     FW_LAUNCH_RET();
 }
 
@@ -291,4 +421,43 @@ extern "C" int fw_layernorm_bwd(int dtype, const void* dy, long lddy, const floa
                                 long lddx, float* dgamma, float* dbeta, float* partial, int rows, int C, void* stream) {
     return fw_layernorm_bwd2(dtype, dy, lddy, x, ldx, gamma, mean, rstd, dres, lddres, dx, lddx, dgamma, dbeta, partial, rows, C,
                              nullptr, 0, nullptr, 1, stream);
+}
+
+// y[r] = T(LN(x[r]) * gamma + beta + mod[p(r)]),  p(r) = ((yy - shift) & 7) * 8 + ((xx - shift) & 7) for row r = (b, yy, xx) of the
+// [B*H*W, C] stream; mod: f32 [64][C], 16-byte aligned.  mean / rstd as fw_layernorm_fwd writes them.
+extern "C" int fw_layernorm_mod_fwd(int dtype, const float* x, long ldx, const float* gamma, const float* beta, const float* mod, void* y,
+                                    long ldy, float* mean, float* rstd, int rows, int C, int H, int W, int shift, float eps, void* stream) {
+    FW_CHECK_ARG(rows > 0 && C > 0 && C % 4 == 0 && C <= 1024 && ldx % 4 == 0 && ldy % 4 == 0);
+    FW_CHECK_ARG(x && gamma && beta && mod && y && mean && rstd && ((uintptr_t)mod & 15) == 0);
+    FW_CHECK_ARG(H > 0 && W > 0 && H % 8 == 0 && W % 8 == 0 && rows % ((long)H * W) == 0 && shift >= 0 && shift < 8);
+    hipStream_t st = (hipStream_t)stream;
+#define LN_F(T) LN_DISPATCH(ln_mod_fwd_launch, T, x, ldx, gamma, beta, mod, y, ldy, mean, rstd, rows, C, H, W, shift, eps, st)
+    return dtype == FW_DT_BF16 ? LN_F(bf16raw) : LN_F(float);
+#undef LN_F
+}
+
+// Number of slices fw_modulator_bwd writes for (rows, C): the caller provides `partial` f32 [slices][64][C], 16-byte aligned.
+extern "C" int fw_modulator_bwd_blocks(int rows, int C) { return mod_bwd_slices(rows, C); }
+
+// dmod[p][c] += sum over the rows r with p(r) = p of dy[r][c]  (dmod: f32 [64][C], ACCUMULATED).  dy is read once; slice z of the
+// rows / 64 terms stores partial[z] and fw_slab_reduce folds the slices into dmod on the same stream, every address by one
+// read-modify-write -- unless dmod is null: the caller folds `partial` later (fw_slab_reduce / fw_slab_reduce_multi).
+extern "C" int fw_modulator_bwd(int dtype, const void* dy, long lddy, float* dmod, float* partial, int rows, int C, int H, int W, int shift,
+                                void* stream) {
+    FW_CHECK_ARG(rows > 0 && C > 0 && C % 4 == 0 && C <= 1024 && lddy % 4 == 0 && lddy >= C);
+    FW_CHECK_ARG(dy && partial && ((uintptr_t)partial & 15) == 0);
+    FW_CHECK_ARG(H > 0 && W > 0 && H % 8 == 0 && W % 8 == 0 && rows % ((long)H * W) == 0 && shift >= 0 && shift < 8);
+    hipStream_t st = (hipStream_t)stream;
+    int rc;
+    if (dtype != FW_DT_BF16) {
+        FW_CHECK_ARG(((uintptr_t)dy & 15) == 0);
+        rc = mod_bwd_launch<float, 4>(dy, lddy, partial, rows, C, W, shift, st);
+    } else if (C % 8 == 0 && lddy % 8 == 0 && ((uintptr_t)dy & 15) == 0) {
+        rc = mod_bwd_launch<bf16raw, 8>(dy, lddy, partial, rows, C, W, shift, st);
+    } else {
+        FW_CHECK_ARG(((uintptr_t)dy & 7) == 0);
+        rc = mod_bwd_launch<bf16raw, 4>(dy, lddy, partial, rows, C, W, shift, st);
+    }
+    if (rc || !dmod) return rc;
+    return fw_slab_reduce(partial, mod_bwd_slices(rows, C), 64L * C, 64L * C, dmod, 2, nullptr, 0, 0, stream);
 }

@@ -387,6 +387,44 @@ class LnResFn(torch.autograd.Function):
         return dx, rg, rb
 
 
+class LnResModFn(torch.autograd.Function):
+    """LnResFn with the decoder's learnable window modulator (decoder_Uformer.py:536-539,687-691):
+    (x) -> (x, LayerNorm(x) + mod[p(row)]), mod the [64, C] weight of the block's nn.Embedding and p(row) the position of the token
+    in its 8x8 window after the cyclic shift (geo = (H, W, shift); csrc/fw_norm.hip).  The table is added behind the normalisation,
+    so LayerNorm's backward sees the same dy as without it; the table's gradient is one more reduction of that dy."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, mod, geo):
+        ctx.set_materialize_grads(False)
+        ctx.rs_hint = getattr(x, '_fw_rs', None)            # as LnResFn
+        rows, C = x.shape
+        y = act_empty(rows, C, config.compute_dtype, x.device)
+        mean, rstd = ops.layernorm_mod_fwd(x, gamma, beta, mod, geo[0], geo[1], geo[2], y)
+        ctx.save_for_backward(x, gamma, mean, rstd)
+        ctx.beta, ctx.mod, ctx.geo = beta, mod, geo
+        return x.view_as(x), y
+
+    @staticmethod
+    def backward(ctx, dres, dy):
+        x, gamma, mean, rstd = ctx.saved_tensors
+        dg, rg = _grad_target(gamma)
+        db, rb = _grad_target(ctx.beta)
+        if dy is None:
+            return dres, None, None, None, None
+        dm, rm = _grad_target(ctx.mod)
+        dy = aligned(dy)
+        twin = None
+        if ctx.rs_hint is not None:
+            twin = act_empty(x.shape[0], x.shape[1], dy.dtype, x.device)
+        rs, rps = ctx.rs_hint if ctx.rs_hint is not None else (None, 1)
+        dx = ops.layernorm_bwd(dy, x, gamma, mean, rstd, dg, db, dres=dres, defer=rg is None and rb is None, twin=twin, twscale=rs,
+                               tw_rows_per_scale=rps)
+        if twin is not None:
+            dx._fw_twin = (twin, rs, rps)
+        ops.modulator_bwd(dy, dm, ctx.geo[0], ctx.geo[1], ctx.geo[2], defer=rm is None)
+        return dx, rg, rb, rm, None
+
+
 def linear(x, weight, bias=None, residual=None, rowscale=None, rows_per_scale=1, x_pre=None, gelu_out=False, out_f32=False, fuse=None):
     y = LinearFn.apply(x, weight, bias, residual, rowscale, rows_per_scale, x_pre, gelu_out, out_f32, fuse)
     if residual is not None and y.requires_grad and (x.dtype != torch.float32 or rowscale is not None):

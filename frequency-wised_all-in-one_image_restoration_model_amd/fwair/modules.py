@@ -5,7 +5,8 @@ through fwair.functional.  Citations are file:line of the reference.
 
 Supported (= every configuration of the reference that runs):
   Uformer encoder (encoder_msa_type freq | origin, L in {2, 3}) + Uformer decoder with
-  degradation_embedding_method in {all_3_bands, all_DC, all_2_bands} or none.
+  degradation_embedding_method in {all_3_bands, all_DC, all_2_bands} or none, with or without the learnable window
+  modulator of the four decoder layers (learnable_modulator).
 Anything else raises NotImplementedError instead of silently diverging.
 """
 import math
@@ -198,7 +199,7 @@ class DecLeWinTransformerBlock(nn.Module):
     """decoder_Uformer.py:504-756 (`LeWinTransformerBlock`, plain + all_* path)."""
 
     def __init__(self, dim, input_resolution, num_heads, win_size=8, shift_size=0, mlp_ratio=4., drop_path=0.,
-                 all_degradation_embedding_method=(), debug_mode=False):
+                 all_degradation_embedding_method=(), debug_mode=False, modulator=False):
         super().__init__()
         self.dim, self.input_resolution, self.num_heads = dim, input_resolution, num_heads
         self.win_size, self.shift_size = win_size, shift_size
@@ -213,6 +214,9 @@ class DecLeWinTransformerBlock(nn.Module):
             # constructor raises its NotImplementedError; at 128 / 256 / 512 every stage side is covered
             from net.utils.frequency_decompose import FrequencyDecompose
             self.visual_decompose = FrequencyDecompose('frequency_decompose', 1, input_resolution[0], input_resolution[1], inverse='visual')
+        # :536-539, registered before norm1 as there (same state_dict key order); nn.Embedding's own N(0, 1) initialisation stays:
+        # _init_weights touches Linear and LayerNorm only
+        self.modulator = nn.Embedding(WIN * WIN, dim) if modulator else None
         self.norm1 = nn.LayerNorm(dim)
         self.attn = DecWindowAttention(input_resolution, dim, (self.win_size, self.win_size), num_heads,
                                        all_degradation_embedding_method)
@@ -234,7 +238,15 @@ class DecLeWinTransformerBlock(nn.Module):
         # two independent masks per block, as the reference's two self.drop_path(...) calls draw (decoder_Uformer.py:739,751)
         dp = Fn.droppath_scale(self._name + 'attn', batch, self.drop_path_rate, self.training, x.device)
         dp2 = Fn.droppath_scale(self._name + 'mlp', batch, self.drop_path_rate, self.training, x.device)
-        x, xn = Fn.LnResFn.apply(x, self.norm1.weight, self.norm1.bias)
+        xn0 = None
+        if self.modulator is None:
+            x, xn = Fn.LnResFn.apply(x, self.norm1.weight, self.norm1.bias)
+        else:
+            if visual is not None:          # the "before" spectrum is norm1's output without the table (:668-673 precede :687)
+                with torch.no_grad():
+                    xn0 = Fn.LayerNormFn.apply(x.detach(), self.norm1.weight, self.norm1.bias)
+            # :687-691: the table is added to every window behind norm1, the cyclic shift and the partition -- one kernel with norm1
+            x, xn = Fn.LnResModFn.apply(x, self.norm1.weight, self.norm1.bias, self.modulator.weight, (h, h, self.shift_size))
         qkv = self.attn.qkv(xn)
         geo = (C, batch, h, h, self.num_heads, 1, 0, self.shift_size, self.attn.lfs_mode if coef is not None else 0)
         tab = self.attn.relative_position_bias_table
@@ -245,7 +257,7 @@ class DecLeWinTransformerBlock(nn.Module):
             lamb = []
             if coef is not None:           # (a, b, c) = (1 + lambda_last, -lambda_last / 64, ...): the LAST band's lambda, [B, 1, heads] (:277-296)
                 lamb = (coef.detach()[:, :, 0] - 1.0).reshape(batch, 1, self.num_heads)
-            visual.append([self._spectrum(xn, batch, h), self._spectrum(y, batch, h), lamb])
+            visual.append([self._spectrum(xn if xn0 is None else xn0, batch, h), self._spectrum(y, batch, h), lamb])
             x = x + (y if dp is None else y * dp.repeat_interleave(h * h)[:, None])
         else:
             x = Fn.linear(o, self.attn.proj.weight, self.attn.proj.bias, residual=x, rowscale=dp, rows_per_scale=h * h)
@@ -254,11 +266,12 @@ class DecLeWinTransformerBlock(nn.Module):
 
 
 class DecBasicUformerLayer(nn.Module):
-    def __init__(self, dim, input_resolution, depth, num_heads, win_size, mlp_ratio, drop_path, methods, debug_mode=False):
+    def __init__(self, dim, input_resolution, depth, num_heads, win_size, mlp_ratio, drop_path, methods, debug_mode=False,
+                 modulator=False):
         super().__init__()
         self.blocks = nn.ModuleList([
             DecLeWinTransformerBlock(dim, input_resolution, num_heads, win_size, 0 if i % 2 == 0 else win_size // 2, mlp_ratio,
-                                     drop_path[i] if isinstance(drop_path, list) else drop_path, methods, debug_mode)
+                                     drop_path[i] if isinstance(drop_path, list) else drop_path, methods, debug_mode, modulator)
             for i in range(depth)])
 
 
@@ -296,7 +309,10 @@ class UformerDecoder(nn.Module):
         dec_dpr = enc_dpr[::-1]
         self.input_proj = InputProj(in_chans, E)
         self.output_proj = OutputProj(2 * E, out_chans)
-        mk = lambda dim, res, d, h, dpr: DecBasicUformerLayer(dim, (res, res), d, h, win_size, mlp_ratio, dpr, methods, self.debug_mode)
+        # :850 -- the multi-scale restoration modulator: the four decoder layers get it, the encoder layers and bottlenecks do not (:998)
+        modulator = bool(getattr(opt, 'learnable_modulator', False))
+        mk = lambda dim, res, d, h, dpr, mod=False: DecBasicUformerLayer(dim, (res, res), d, h, win_size, mlp_ratio, dpr, methods,
+                                                                         self.debug_mode, mod)
         o = 0
         for i in range(4):
             setattr(self, f'encoderlayer_{i}', mk(E * 2 ** i, img_size // 2 ** i, depths[i], num_heads[i], enc_dpr[o:o + depths[i]]))
@@ -305,13 +321,13 @@ class UformerDecoder(nn.Module):
         self.bottleneck_0 = mk(E * 16, img_size // 16, depths[4], num_heads[4], conv_dpr)
         self.bottleneck_1 = mk(E * 16, img_size // 16, depths[4], num_heads[4], conv_dpr)
         self.upsample_3 = Upsample(E * 16, E * 8)
-        self.decoderlayer_3 = mk(E * 16, img_size // 8, depths[5], num_heads[5], dec_dpr[:depths[5]])
+        self.decoderlayer_3 = mk(E * 16, img_size // 8, depths[5], num_heads[5], dec_dpr[:depths[5]], modulator)
         self.upsample_2 = Upsample(E * 16, E * 4)
-        self.decoderlayer_2 = mk(E * 8, img_size // 4, depths[6], num_heads[6], dec_dpr[sum(depths[5:6]):sum(depths[5:7])])
+        self.decoderlayer_2 = mk(E * 8, img_size // 4, depths[6], num_heads[6], dec_dpr[sum(depths[5:6]):sum(depths[5:7])], modulator)
         self.upsample_1 = Upsample(E * 8, E * 2)
-        self.decoderlayer_1 = mk(E * 4, img_size // 2, depths[7], num_heads[7], dec_dpr[sum(depths[5:7]):sum(depths[5:8])])
+        self.decoderlayer_1 = mk(E * 4, img_size // 2, depths[7], num_heads[7], dec_dpr[sum(depths[5:7]):sum(depths[5:8])], modulator)
         self.upsample_0 = Upsample(E * 4, E)
-        self.decoderlayer_0 = mk(E * 2, img_size, depths[8], num_heads[8], dec_dpr[sum(depths[5:8]):sum(depths[5:9])])
+        self.decoderlayer_0 = mk(E * 2, img_size, depths[8], num_heads[8], dec_dpr[sum(depths[5:8]):sum(depths[5:9])], modulator)
         self.apply(self._init_weights)                                          # :1094-1104
         self._order = ['encoderlayer_0', 'encoderlayer_1', 'encoderlayer_2', 'encoderlayer_3', 'bottleneck_0', 'bottleneck_1',
                        'decoderlayer_3', 'decoderlayer_2', 'decoderlayer_1', 'decoderlayer_0']

@@ -436,6 +436,30 @@ def layernorm_bwd(dy, x, gamma, mean, rstd, dgamma, dbeta, dres=None, defer=Fals
     return dx
 
 
+def layernorm_mod_fwd(x, gamma, beta, mod, H, W, shift, y, eps=1e-5):
+    """y[r] = T(LN(x[r]) * gamma + beta + mod[p(r)]) into the given y (fw_layernorm_mod_fwd: p(r) is the window position of row r of
+    the [B*H*W, C] stream under the cyclic shift).  -> mean, rstd"""
+    rows, C = x.shape
+    mean = torch.empty(rows, dtype=torch.float32, device=x.device)
+    rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
+    call('fw_layernorm_mod_fwd', dt(y.dtype), x, _ld(x), gamma, beta, mod, y, _ld(y), mean, rstd, rows, C, H, W, shift, eps)
+    return mean, rstd
+
+
+def modulator_bwd(dy, dmod, H, W, shift, defer=False):
+    """dmod[p] += sum over the rows with p(r) = p of dy[r].  With defer (dmod is a persistent gradient buffer) inside a backward pass
+    the kernel only stores its slices and the pass's one fold adds them (flush_slabs); otherwise fw_modulator_bwd folds them itself."""
+    rows, C = dy.shape
+    nz = lib().fw_modulator_bwd_blocks(rows, C)
+    partial = torch.empty((nz, 64 * C), dtype=torch.float32, device=dy.device)
+    deferred = defer and _in_backward()
+    if not deferred:
+        _note_write(dmod)
+    call('fw_modulator_bwd', dt(dy.dtype), dy, _ld(dy), None if deferred else dmod, partial, rows, C, H, W, shift)
+    if deferred:
+        slab_reduce(partial, nz, 64 * C, 64 * C, dmod, defer=True)
+
+
 # ------------------------------------------------------------------------------------------------ attention
 def attn_fwd(qkv, C, B, H, W, heads, L, mode, shift, bias, coef=None, lfs=0):
     """qkv: [L*B*H*W, 3C] (q | k | v).  bias: f32 [L*L or 1, 225, heads].  -> out [rows, C], lse."""

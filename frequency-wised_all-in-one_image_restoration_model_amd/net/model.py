@@ -28,6 +28,16 @@ def _apply_dtype(opt):
                                 'bfloat16': torch.bfloat16}[str(name)]
 
 
+def options_from_checkpoint(opt, sd):
+    """Set on `opt` what a state_dict itself tells about the model it was saved from, so that restoring it does not depend on the
+    command line repeating it: the training batch from the MoCo queue (K = 3 * batch_size, net/model.py:35 of the reference) and
+    `learnable_modulator` from the presence of the decoder blocks' `modulator.weight` tables (decoder_Uformer.py:536-537)."""
+    if 'E.E.queue' in sd:
+        opt.batch_size = sd['E.E.queue'].shape[-1] // 3
+    opt.learnable_modulator = any(k.startswith('R.R.') and k.endswith('.modulator.weight') for k in sd)
+    return opt
+
+
 class Decoder(nn.Module):
     def __init__(self, opt):
         super().__init__()

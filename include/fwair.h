@@ -49,7 +49,9 @@ int fw_gemm_last_kernel(char* buf, int n);
 int fw_wgrad_group_prob_bytes(void);
 int fw_wgrad_group(const void* tab, void* probs, int nprob, const void* items, int nitems, int tile, void* stream);
 
-/* split-K without atomics: slice z stores its partial tile at C + z*c_zstride (and xsum + z*xsum_zstride); this sums the slices */
+/* split-K without atomics: slice z stores its partial tile at C + z*c_zstride (and xsum + z*xsum_zstride); this sums the slices.
+ * accumulate: 0 store, 1 add (a long z range may be split over blocks that add atomically), 2 add with the whole z range in one block
+ * (one read-modify-write per address: deterministic) */
 int fw_slab_reduce(const float* slab, int nz, long n, long zstride, float* dst, int accumulate, float* dst2, long off2, long n2,
                    void* stream);
 /* Many slabs in one launch (ops.flush_slabs: every weight-gradient / LayerNorm partial of a backward pass is folded once,
@@ -73,6 +75,25 @@ int fw_layernorm_bwd2(int dtype, const void* dy, long lddy, const float* x, long
                       const float* rstd, const float* dres, long lddres, float* dx, long lddx, float* dgamma, float* dbeta,
                       float* partial, int rows, int C, void* twin, long ldtw, const float* twscale, int tw_rows_per_scale,
                       void* stream);
+
+/* ---- learnable window modulator of the decoder blocks (--learnable_modulator; decoder_Uformer.py:536-539,687-691) ----------
+ * The reference adds an nn.Embedding(64, C) table to the 64 tokens of every 8x8 window after norm1, the cyclic shift and the window
+ * partition, in front of the Q/K/V projection.  On the token-major [B*H*W, C] stream the window position of row r = (b, yy, xx)
+ * under shift s (0 or 4) is  p(r) = ((yy - s) mod 8) * 8 + ((xx - s) mod 8)  (roll(-s) moves pixel yy to rolled row (yy - s) mod H,
+ * and 8 | H, 8 | W).
+ * fw_layernorm_mod_fwd: y[r] = T(LN(x[r]) * gamma + beta + mod[p(r)]); mod f32 [64][C], 16-byte aligned; mean / rstd exactly as
+ * fw_layernorm_fwd writes them (the same kernel body with the table add compiled in).
+ * fw_modulator_bwd: dmod[p] += sum over the rows with p(r) = p of dy[r]  (dmod f32 [64][C], ACCUMULATED).  dy is read once; the
+ * rows / 64 terms of a sum are cut into fw_modulator_bwd_blocks(rows, C) slices, slice z stores partial[z] (caller scratch f32
+ * [slices][64][C], 16-byte aligned) with plain stores, and fw_slab_reduce (accumulate = 2: one read-modify-write per address) folds
+ * them into dmod on the same stream: no floating-point atomics, identical calls give identical bits.  dmod == NULL leaves the fold
+ * to the caller (ops.flush_slabs folds every slab of a backward pass in one launch).  LayerNorm's own backward is unchanged: the
+ * gradient reaching it is the same dy. */
+int fw_layernorm_mod_fwd(int dtype, const float* x, long ldx, const float* gamma, const float* beta, const float* mod, void* y,
+                         long ldy, float* mean, float* rstd, int rows, int C, int H, int W, int shift, float eps, void* stream);
+int fw_modulator_bwd_blocks(int rows, int C);
+int fw_modulator_bwd(int dtype, const void* dy, long lddy, float* dmod, float* partial, int rows, int C, int H, int W, int shift,
+                     void* stream);
 
 /* ---- window attention (decoder_Uformer.py:240-293 with :387-409,634-651,678-686,721-729 folded in;
  *      encoder_Uformer.py:152-183 "origin", :256-310 intra / inter band attention) ---------------------
