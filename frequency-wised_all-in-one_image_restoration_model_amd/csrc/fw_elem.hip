@@ -1523,6 +1523,7 @@ extern "C" int fw_dwconv_fwd(int dtype, const void* g1, long ld1, int in_gelu, c
                              int B, int H, int W, int C, void* stream) {
     const int e = dtype == FW_DT_BF16 ? 8 : 4;
     FW_CHECK_ARG(g1 && w && bias && h2 && g2 && C % e == 0 && ld1 % e == 0 && ld2 % e == 0 && W % SX == 0);
+    FW_CHECK_ARG(B > 0 && H > 0 && W > 0 && C > 0 && ld1 >= C && ld2 >= C);      // a row holds its C channels: loads and stores stay inside it
     const long n = (long)B * H * (W / SX) * (C / 4);
     // the LDS-tiled form wins where the tensors outgrow the 256 MB infinity cache (stage-0 layers); below that the strips are as fast
     if (dw_tiled(B, H, W, C) && (long)H * W * ld1 < (1L << 31)) {      // a workgroup walks several tiles (dwconv_fwd_pipe_kernel)
@@ -1564,6 +1565,7 @@ extern "C" int fw_dwconv_bwd(int dtype, const void* dh2, long ldg, const void* g
     const int e = dtype == FW_DT_BF16 ? 8 : 4;
     FW_CHECK_ARG(dh2 && h1 && w && dh1 && dw && dbias && C % e == 0 && ld1 % e == 0 && ldg % e == 0 && ldo % e == 0 && W % SX == 0);
     FW_CHECK_ARG(ldg == ld1);                      // the data-gradient strip kernel walks dh2 and h1 with one row stride
+    FW_CHECK_ARG(B > 0 && H > 0 && W > 0 && C > 0 && ld1 >= C && ldo >= C);      // a row holds its C channels: loads and stores stay inside it
     const long n = (long)B * H * (W / SX) * (C / 4);
     const int nvg = (C / 4 + WG_VL - 1) / WG_VL;
     const long nst = (long)B * H * (W / SX);

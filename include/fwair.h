@@ -122,7 +122,9 @@ int fw_attn_bwd(int dtype, int D, int nkt, int lfs, const void* q, const void* k
  * bwd: dh1 = GELU'(h1) * convT(dh2), dw / dbias accumulated; g1 may be NULL: the weight gradient then takes GELU(h1) in-kernel
  * (input-centric form: exactly one GELU per element).
  * w is TAP-MAJOR f32 [9][C] (a per-step permuted copy of the [C,1,3,3] parameter); dw is ACCUMULATED into in the
- * parameter's own [C][9] layout, dbias likewise ([C]). */
+ * parameter's own [C][9] layout, dbias likewise ([C]).  h2, g2 and dh1 are plain stores.
+ * Checked: C and every row stride a multiple of 8 (bf16) / 4 (f32) elements, every row stride >= C, W % 8 == 0, ldg == ld1 (g1, h1
+ * and dh2 share one row stride), sizes > 0. */
 int fw_dwconv_fwd(int dtype, const void* in, long ld1, int in_gelu, const float* w, const float* bias, void* h2, void* g2, long ld2, int B,
                   int H, int W, int C, void* stream);
 int fw_dwconv_bwd(int dtype, const void* dh2, long ldg, const void* g1, const void* h1, long ld1, const float* w, void* dh1,

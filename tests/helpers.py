@@ -1422,3 +1422,258 @@ def dcn_inputs(dtype, B, H, W, C, kind='random', seed=0, logit_scale=1.0):
     else:
         x, dcol = rs(signed_magnitudes(M, C, seed=seed + 1)), rs(signed_magnitudes(M, 9 * C, seed=seed + 2))
     return dict(x=x, dcol=dcol, om=om)
+
+
+# ------------------------------------------------------------------------------------------------ LeFF depthwise 3x3 (csrc/fw_elem.hip)
+# fw_dwconv_fwd / fw_dwconv_bwd: the plain f64 statement, element-wise bounds counted from the kernels' roundings, and a restatement
+# of the host dispatch (which of the five kernels a call reaches, and with which walk).  Tensors are [B*H*W, >= C] float64 holding
+# storage-rounded values, on the host or the device; w is [C, 9] in the parameter's own layout (the ABI takes its transpose), bias [C].
+#   fwd : h2 = bias + sum_(ky,kx) w[ky,kx] g[y + ky - 1][x + kx - 1],  g = GELU(h1) (in_gelu) or the stored g1;  g2 = GELU(h2)
+#   bwd : dh1 = GELU'(h1) sum_(ky,kx) w[ky,kx] dh2[y - ky + 1][x - kx + 1]
+#         dw[c][ky,kx] += sum_p g[p] dh2[p - (ky,kx) + 1],  dbias[c] += sum_p dh2[p]
+# The constants below restate csrc/fw_elem.hip; tests/test_dwconv_bounds_cpu.py reads them back out of the source.
+DW_TILED_MIN = 10_000_000         # B*H*W*C from which the LDS-tiled forms run (H % DT_TY == 0 as well)
+DT_TY, DT_TX, DT_CB = 8, 16, 64   # a tile: rows x pixels x channels
+DW_SX = 8                         # SX: pixels of a strip
+WG_VL, WG_SL = 32, 8              # weight-gradient block: channel vectors x strip lanes
+DW_FWD_WANT, DW_BWD_WANT = 2048, 1024   # workgroups the pipelined forward / the fused backward aim for
+DW_NT_MAX = 32                    # tile rows a workgroup walks at most
+DW_NSTRIP_MAX, DW_WG_MIN_BLOCKS = 16, 384
+DW_STRIP_GRID_CAP = 8192          # grid_for: workgroups of 256 threads, then a grid-stride loop
+DW_TPB = 256
+DW_TAP_ROUNDINGS = 9 + 1 + 1      # nine taps, the bias (forward) or the product with GELU' (backward), one spare
+DW_MUTATIONS = ('halo_top_neighbour', 'halo_bottom_neighbour', 'col_left_clamped', 'col_right_clamped', 'taps_not_flipped',
+                'kykx_swapped', 'cblock_dropped', 'half_tile_dropped', 'beyond_w_counted', 'gelu_missing', 'gelu_twice',
+                'gelu_grad_at_gelu', 'dw_tap_reversed', 'prefill_overwritten', 'tile_row_dropped')
+
+
+def _cdiv(a, b):
+    return -(-a // b)
+
+
+def _dw_walk(B, H, W, C, want):
+    """the persistent tile walk of dwconv_fwd_pipe_kernel / dwconv_bwd_fused_kernel: ncol tile columns (channel block x 16 pixels),
+    nrow = B * H / 8 tile rows numbered straight through the images, NT consecutive rows per workgroup"""
+    ntx, nty = _cdiv(W, DT_TX), H // DT_TY
+    ncol, nrow = _cdiv(C, DT_CB) * ntx, B * nty
+    raw = ncol * nrow // want
+    NT = min(max(raw, 1), DW_NT_MAX)
+    nchunk = _cdiv(nrow, NT)
+    wgs = ncol * nchunk
+    return dict(NT=NT, raw=raw, ncol=ncol, ntx=ntx, nrow=nrow, nchunk=nchunk, wgs=wgs, wgs_padded=rup(wgs, 8), idle=rup(wgs, 8) - wgs,
+                crossing=sum(1 for r in range(nty, nrow, nty) if r % NT), last_walk=nrow - (nchunk - 1) * NT)
+
+
+def dwconv_plan(B, H, W, C, ld, dtype, g1):
+    """What fw_dwconv_fwd (input row stride ld) and fw_dwconv_bwd (dh2 / h1 row stride ld, g1 kept or not) launch for this shape.
+    -> dict fwd / bwd: 'form' and the launch arithmetic of that form.
+      fwd form 'strip' | 'fwd_pipe' | 'tile';  bwd form 'strip+wgrad' | 'fused' | 'tile+wgrad'
+      walks (fwd_pipe, fused): NT, raw (the quotient before the clamp), nchunk (walks per tile column), wgs / wgs_padded / idle
+        (workgroups before and after padding to 8, and the padded ones that find no walk), crossing (walks of a column that cross an
+        image border), last_walk (tile rows of the last walk)
+      strip: grid (padded to 8), threads, passes of the grid-stride loop;  tile: wgs, wgs_padded
+      bwd also: NSTRIP, wgrad_blocks, nsg (weight-gradient blocks per channel group) whether or not the weight-gradient kernel runs,
+      and dw_depth: the longest chain of f32 additions between one product and dw / dbias in the form that runs."""
+    assert dtype in (torch.float32, torch.bfloat16)
+    tiled = H % DT_TY == 0 and B * H * W * C >= DW_TILED_MIN
+    off32 = H * W * ld < 2 ** 31
+    n = B * H * (W // DW_SX) * (C // 4)
+    grid = rup(min(max(_cdiv(n, DW_TPB), 1), DW_STRIP_GRID_CAP), 8)
+    strip = dict(grid=grid, threads=n, passes=_cdiv(n, grid * DW_TPB))
+    nb = B * (H // DT_TY) * _cdiv(W, DT_TX) * _cdiv(C, DT_CB)
+    tile = dict(wgs=nb, wgs_padded=rup(nb, 8))
+    if tiled and off32:
+        fwd = dict(form='fwd_pipe', **_dw_walk(B, H, W, C, DW_FWD_WANT))
+    elif tiled:
+        fwd = dict(form='tile', **tile)
+    else:
+        fwd = dict(form='strip', **strip)
+    nvg, nst = _cdiv(C // 4, WG_VL), B * H * (W // DW_SX)
+    NSTRIP = DW_NSTRIP_MAX
+    while NSTRIP > 2 and _cdiv(nst, NSTRIP * WG_SL) * nvg < DW_WG_MIN_BLOCKS:
+        NSTRIP >>= 1
+    nsg = _cdiv(nst, NSTRIP * WG_SL)
+    wg = dict(NSTRIP=NSTRIP, nsg=nsg, wgrad_blocks=nsg * nvg, dead_lanes=C // 4 % WG_VL != 0)
+    # chains: a product (one rounding in f32), then
+    #   wgrad: 8 pixels x NSTRIP strips into a register, one shuffle, the four waves' LDS atomics, one global atomic per block of the
+    #          channel group;   fused: 8 pixels into gk, NT tiles into the LDS partial (dbias: 8 x NT into a register), two shuffles,
+    #          the four waves, one global atomic per workgroup of the same channel block (ntx * nchunk of them)
+    if tiled and not g1 and off32:
+        walk = _dw_walk(B, H, W, C, DW_BWD_WANT)
+        bwd = dict(form='fused', **walk, **wg, dw_depth=1 + 8 * walk['NT'] + walk['NT'] + 2 + 4 + walk['ntx'] * walk['nchunk'])
+    else:
+        bwd = dict(form='tile+wgrad' if tiled else 'strip+wgrad', **(tile if tiled else strip), **wg, dw_depth=1 + 8 * NSTRIP + 1 + 4 + nsg)
+    return dict(fwd=fwd, bwd=bwd)
+
+
+def _dw_add_tap(acc, x4, wk, dy, dx, flat_rows=False, clamp=None):
+    """acc[b, y, x] += wk * x4[b, y + dy, x + dx], zero outside the image.  flat_rows: the rows of all images taken as one tall image
+    (a halo row then comes from the neighbouring image); clamp 'left' / 'right': the column outside the image reads the edge column"""
+    if flat_rows:
+        acc, x4 = acc.view(1, -1, *acc.shape[2:]), x4.view(1, -1, *x4.shape[2:])
+    H, W = acc.shape[1:3]
+    ya, yb, xa, xb = max(0, -dy), min(H, H - dy), max(0, -dx), min(W, W - dx)
+    acc[:, ya:yb, xa:xb].addcmul_(x4[:, ya + dy:yb + dy, xa + dx:xb + dx], wk)
+    if clamp == 'left' and dx == -1:
+        acc[:, ya:yb, 0].addcmul_(x4[:, ya + dy:yb + dy, 0], wk)
+    if clamp == 'right' and dx == 1:
+        acc[:, ya:yb, W - 1].addcmul_(x4[:, ya + dy:yb + dy, W - 1], wk)
+
+
+def _dw_stencil(x4, w9, flip, mutation=None):
+    """sum over the nine taps of w[c][ky,kx] x4[y + s (ky - 1)][x + s (kx - 1)], s = +1 (forward) or -1 (flip: the data gradient)"""
+    acc = torch.zeros_like(x4)
+    s = -1 if flip and mutation != 'taps_not_flipped' else 1
+    for ky in range(3):
+        for kx in range(3):
+            k = kx * 3 + ky if mutation == 'kykx_swapped' else ky * 3 + kx
+            dy, dx = s * (ky - 1), s * (kx - 1)
+            flat = (mutation == 'halo_top_neighbour' and dy == -1) or (mutation == 'halo_bottom_neighbour' and dy == 1)
+            clamp = {'col_left_clamped': 'left', 'col_right_clamped': 'right'}.get(mutation)
+            _dw_add_tap(acc, x4, w9[:, k], dy, dx, flat, clamp)
+    return acc
+
+
+def _dw_unwritten(v4, C, W, mutation):
+    """what a kernel that skips its last partial channel block, or its half-width last tile column, leaves of an output: nothing"""
+    if mutation == 'cblock_dropped' and C % DT_CB:
+        v4[..., C // DT_CB * DT_CB:] = 0
+    if mutation == 'half_tile_dropped' and W % DT_TX == 8:
+        v4[:, :, W - 8:] = 0
+    return v4
+
+
+def dw_touched(mutation, B, H, W, C):
+    """[B, H, W, C] mask of the data-output elements (h2, g2, dh1) a mutation of the stencil changes"""
+    m = torch.zeros(B, H, W, C, dtype=torch.bool)
+    if mutation == 'halo_top_neighbour':
+        m[1:, 0] = True
+    elif mutation == 'halo_bottom_neighbour':
+        m[:-1, H - 1] = True
+    elif mutation == 'col_left_clamped':
+        m[:, :, 0] = True
+    elif mutation == 'col_right_clamped':
+        m[:, :, W - 1] = True
+    elif mutation == 'cblock_dropped':
+        m[..., C // DT_CB * DT_CB:] = C % DT_CB != 0
+    elif mutation == 'half_tile_dropped':
+        m[:, :, W - 8:] = W % DT_TX == 8
+    else:
+        m[:] = True
+    return m.reshape(B * H * W, C)
+
+
+def dwconv_ref(src, in_gelu, w, bias, B, H, W, C, dtype, mutation=None):
+    """fw_dwconv_fwd in f64.  src [B*H*W, >= C]: the pre-activation h1 (in_gelu) or the stored activation g1.
+    -> {'h2': (value, tol), 'g2': (value, tol)}, each [B*H*W, C].
+    h2: DW_TAP_ROUNDINGS f32 roundings of partial sums that |bias| + sum |w| |g| bounds, plus sum |w| (operand error of g), plus the
+    storage rounding.  With in_gelu the operand error is gelu_operand_err: GELU's own value error AND, in bf16, the re-rounding of
+    GELU(h1) to bf16 on its way into LDS.  Only dwconv_tile_kernel and dwconv_fwd_pipe_kernel re-round; dwconv_strip_kernel (and
+    both weight-gradient forms and the fused backward) keep GELU(h1) in f32 -- the bound is stated once, for the larger variant.
+    g2 = GELU of the f32 sum (not of the stored h2): the `twin` branch of gemm_expect."""
+    x4 = src[:, :C].reshape(B, H, W, C).contiguous()
+    err4 = None
+    if in_gelu:
+        err4 = gelu_operand_err(x4, dtype)
+        if mutation != 'gelu_missing':
+            x4 = gelu64(gelu64(x4)) if mutation == 'gelu_twice' else gelu64(x4)
+    v = _dw_stencil(x4, w, False, mutation) + bias
+    mag = _dw_stencil(x4.abs(), w.abs(), False) + bias.abs()
+    tol = DW_TAP_ROUNDINGS * U32 * mag
+    if err4 is not None:
+        tol = tol + _dw_stencil(err4, w.abs(), False)
+    v = _dw_unwritten(v, C, W, mutation)
+    t_val = gelu64(v)
+    t_tol = GELU_LIPSCHITZ * tol + gelu_value_err(v.abs() + tol, dtype)
+    if dtype == torch.bfloat16:
+        tol, t_tol = tol + UBF * (v.abs() + tol), t_tol + UBF * (t_val.abs() + t_tol)
+    f = lambda t: t.reshape(B * H * W, C)
+    return dict(h2=(f(v), f(tol)), g2=(f(t_val), f(t_tol)))
+
+
+def dwconv_bwd_ref(dh2, g1, h1, w, B, H, W, C, dtype, ld=None, dw0=None, db0=None, mutation=None, drop=None):
+    """fw_dwconv_bwd in f64.  dh2, h1 (and g1, or None: the kernels evaluate GELU(h1)) [B*H*W, >= C]; dw0 [C, 9] / db0 [C]: what dw /
+    dbias hold before the call (the kernels ADD to them).  ld: the row stride of dh2 / h1 the dispatch sees (default C).
+    drop = (b, y0, y1): the INPUT pixels of rows [y0, y1) of image b left out of dw / dbias (a tile row a walk skipped).
+    -> {'dh1': (value, tol) [B*H*W, C], 'dw': (value, tol) [C, 9], 'dbias': (value, tol) [C]}.
+    dh1: the flipped-tap sum s with DW_TAP_ROUNDINGS roundings, times GELU'(h1): tol_s (|GELU'| + e') + |s| e' + storage.
+    dw / dbias: depth u (sum |g| |dh2| + |prefill|) for ANY order of the additions, depth = the longest chain of the form that
+    dwconv_plan names (zero terms add nothing to the magnitude sum), plus sum |dh2| (GELU value error) where GELU is evaluated
+    in-kernel (kept in f32 there: no re-rounding)."""
+    d4 = dh2[:, :C].reshape(B, H, W, C).contiguous()
+    h4 = h1[:, :C].reshape(B, H, W, C).contiguous()
+    s = _dw_stencil(d4, w, True, mutation)
+    tol_s = DW_TAP_ROUNDINGS * U32 * _dw_stencil(d4.abs(), w.abs(), True)
+    gp = gelu_grad64(gelu64(h4) if mutation == 'gelu_grad_at_gelu' else h4)
+    eg = gelu_grad_value_err(dtype)
+    v = _dw_unwritten(s * gp, C, W, mutation)
+    tol = tol_s * (gp.abs() + eg) + s.abs() * eg
+    if dtype == torch.bfloat16:
+        tol = tol + UBF * (v.abs() + tol)
+    # ---- weight / bias gradient
+    if g1 is not None:
+        g4, ge4 = g1[:, :C].reshape(B, H, W, C).contiguous(), None
+        if mutation == 'gelu_twice':
+            g4 = gelu64(g4)
+    else:
+        ge4 = gelu_value_err(h4, dtype)
+        g4 = h4 if mutation == 'gelu_missing' else (gelu64(gelu64(h4)) if mutation == 'gelu_twice' else gelu64(h4))
+    db4 = d4
+    if drop is not None or mutation == 'half_tile_dropped':
+        g4, db4 = g4.clone(), d4.clone()
+        if drop is not None:
+            b, y0, y1 = drop
+            g4[b, y0:y1] = 0
+            db4[b, y0:y1] = 0
+        if mutation == 'half_tile_dropped' and W % DT_TX == 8:
+            g4[:, :, W - 8:] = 0
+            db4[:, :, W - 8:] = 0
+    dw, mag, gerr = (torch.zeros(C, 9, dtype=d4.dtype, device=d4.device) for _ in range(3))
+    for ky in range(3):
+        for kx in range(3):
+            dy, dx = 1 - ky, 1 - kx                                        # dh2 at p + (dy, dx) meets the input pixel p
+            flat = (mutation == 'halo_top_neighbour' and dy == -1) or (mutation == 'halo_bottom_neighbour' and dy == 1)
+            a, b_ = (g4.view(1, B * H, W, C), d4.view(1, B * H, W, C)) if flat else (g4, d4)
+            Hh = a.shape[1]
+            ya, yb, xa, xb = max(0, -dy), min(Hh, Hh - dy), max(0, -dx), min(W, W - dx)
+            gs, ds = a[:, ya:yb, xa:xb], b_[:, ya + dy:yb + dy, xa + dx:xb + dx]
+            k = ky * 3 + kx
+            dw[:, k] = torch.einsum('byxc,byxc->c', gs, ds)
+            mag[:, k] = torch.einsum('byxc,byxc->c', gs.abs(), ds.abs())
+            if ge4 is not None:
+                gerr[:, k] = torch.einsum('byxc,byxc->c', ge4[:, ya:yb, xa:xb], d4[:, ya + dy:yb + dy, xa + dx:xb + dx].abs())
+            if (mutation == 'col_left_clamped' and dx == -1) or (mutation == 'col_right_clamped' and dx == 1):
+                col = 0 if dx == -1 else W - 1                             # the column outside the image reads the edge column
+                dw[:, k] += torch.einsum('byc,byc->c', g4[:, ya:yb, col], d4[:, ya + dy:yb + dy, col])
+            if mutation == 'beyond_w_counted' and kx == 2 and W % DT_TX == 8:
+                # the clamped strip beyond W holds g[W - 1] again; its first pixel (x = W) meets dh2[W - 1] at kx = 2
+                dw[:, k] += torch.einsum('byc,byc->c', g4[:, ya:yb, W - 1], d4[:, ya + dy:yb + dy, W - 1])
+    db = db4.sum((0, 1, 2))
+    dbmag = db4.abs().sum((0, 1, 2))
+    if mutation == 'beyond_w_counted' and W % DT_TX == 8:
+        db = db + 8 * d4[:, :, W - 1].sum((0, 1))                          # eight clamped columns counted as pixels
+    if mutation == 'cblock_dropped' and C % DT_CB:
+        dw[C // DT_CB * DT_CB:] = 0
+        db[C // DT_CB * DT_CB:] = 0
+    if mutation == 'dw_tap_reversed':
+        dw = dw.flip(1)
+    dw0 = torch.zeros_like(dw) if dw0 is None else dw0.to(dw)
+    db0 = torch.zeros_like(db) if db0 is None else db0.to(db)
+    if mutation != 'prefill_overwritten':
+        dw, db = dw + dw0, db + db0
+    depth = dwconv_plan(B, H, W, C, ld or C, dtype, g1 is not None)['bwd']['dw_depth']
+    tol_w = depth * U32 * (mag + dw0.abs()) + gerr
+    tol_b = depth * U32 * (dbmag + db0.abs())
+    return dict(dh1=(v.reshape(B * H * W, C), tol.reshape(B * H * W, C)), dw=(dw, tol_w), dbias=(db, tol_b))
+
+
+def dwconv_rows_share(dh2, g, B, H, W, C, b, y0, y1):
+    """what the INPUT pixels of rows [y0, y1) of image b add to dw and dbias (g: the activation the weight gradient multiplies, f64):
+    the weight-gradient statement on the window of rows that those pixels' taps reach.  -> (dw part [C, 9], dbias part [C])"""
+    ya, yb = max(0, y0 - 1), min(H, y1 + 1)
+    d4 = dh2[:, :C].reshape(B, H, W, C)[b:b + 1, ya:yb]
+    gm = torch.zeros_like(d4)
+    gm[0, y0 - ya:y1 - ya] = g[:, :C].reshape(B, H, W, C)[b, y0:y1]
+    part = dwconv_bwd_ref(d4.reshape(-1, C), gm.reshape(-1, C), gm.reshape(-1, C), torch.zeros(C, 9, dtype=d4.dtype, device=d4.device),
+                          1, yb - ya, W, C, torch.float32)
+    return part['dw'][0], d4[0, y0 - ya:y1 - ya].sum((0, 1))

@@ -726,7 +726,8 @@ def test_lfs_lambda_heads(nb, NT):
 #     windows each, prefetching the next window's tiles and accumulating the bias gradient (and d(a, b, c)) across the walk.  The
 #     4 096-workgroup cap and item loop of attn_fwd_kernel and the 1024 / (heads * L) chunks of attn_bwd_kernel (v1: inter-band
 #     with L = 2 only) are NOT reached from here; tests/test_window_attention_pin_gpu.py::test_v1_kernels_at_size runs them,
-#   * fw_dwconv_fwd / _bwd switch to the LDS-tiled kernel (dwconv_tile_kernel) once B*H*W*C >= 80 M elements.
+#   * fw_dwconv_fwd / _bwd switch to the LDS-tiled persistent forms (dwconv_fwd_pipe_kernel, dwconv_bwd_fused_kernel) once
+#     B*H*W*C >= 10 M elements and H % 8 == 0; tests/test_dwconv_pin_gpu.py pins every form, walk and cap of that dispatch.
 @pytest.mark.parametrize('dtype', DTYPES)
 def test_attention_decoder_timed_shape(dtype):
     """decoderlayer_0 of the timed step: B = 16, 128x128, C = 112, 2 heads, LFS (3 bands), shifted: 4 096 windows x 2 heads on
@@ -788,10 +789,12 @@ def test_attention_encoder_timed_shape(dtype, mode):
 @pytest.mark.parametrize('dtype', DTYPES)
 def test_dwconv_tiled_kernel_timed_shape(dtype, shape):
     """LeFF depthwise 3x3 of decoderlayer_0 in the timed step: B = 16, 128x128, hidden 448 -> 117 M elements >= the 10 M threshold
-    of fw_dwconv_fwd / fw_dwconv_bwd, so dwconv_tile_kernel<*, 0> (forward + GELU twin) and dwconv_bwd_fused_kernel (data + weight +
-    bias gradient in one pass, persistent over vertically consecutive tiles) run.  Second shape: ragged everywhere -- W = 120 is no
-    multiple of the 16-pixel tile, C = 168 leaves a 40-channel last block, 4 x 17 tile rows do not divide by the tiles a workgroup
-    walks (workgroups cross image borders).  Third: the smallest tiled layer of the step (one tile per image column)."""
+    of fw_dwconv_fwd / fw_dwconv_bwd, so dwconv_fwd_pipe_kernel (forward + GELU twin, persistent over 7 vertically consecutive
+    tiles) and dwconv_bwd_fused_kernel (data + weight + bias gradient in one pass, 14 tiles per workgroup) run; the one-shot
+    dwconv_tile_kernel<*, 0> is reached only past the 32-bit offset guard (tests/test_dwconv_pin_gpu.py::test_offset_guard).
+    Second shape: ragged -- W = 120 is no multiple of the 16-pixel tile, C = 168 leaves a 40-channel last block; its 4 x 17 tile
+    rows are walked one per workgroup (NT = 1), so no walk crosses an image border here: the pin tests' S2 and S3 do that.
+    Third: the smallest tiled layer of the step (one tile per image column, NT = 1)."""
     B, H, W, C = shape
     assert B * H * W * C >= 10_000_000
     h1 = q(rnd(B * H * W, C), dtype).requires_grad_(True)
