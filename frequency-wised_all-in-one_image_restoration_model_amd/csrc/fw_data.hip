@@ -16,6 +16,10 @@
 //     together with the squared error against the ground truth (utils/val_utils.py:52-63) and the uint8 image of utils/image_io.py:383;
 //     SSIM over the packed buffer.  Four consecutive x per thread (one 4-byte load of uint8 / one 16-byte access of f32) where the
 //     row pitch and the pointers are multiples of 4, one x per thread otherwise.
+//   * fw_restore_gather / fw_restore_blend -- the same pair for images of ANY size: tiles may leave the image (whole-sample reflection,
+//     np.pad 'reflect'), overlap by a chosen amount (a linear ramp weights the overlap) and come in the 8 flips / rotations of
+//     fw_train_batch, which the blend undoes before it averages (x8 self-ensemble).  The noise counter is the SOURCE pixel, so
+//     reflected copies, overlapping tiles and all eight turns see one noisy image.
 // All HBM-bound byte / float streaming work: grid-stride kernels, coalesced along x.
 #include "fw_common.h"
 
@@ -312,6 +316,192 @@ __global__ void eval_ssim7_kernel(const long long* __restrict__ itab, const long
     acc = block_sum(acc, red);
     if (threadIdx.x == 0) atomicAdd(out + im, acc);
 }
+
+// ---- restoration of any image size: reflect padding, weighted overlap, the eight turns --------------------------------------------
+// ttab[t] = {image, y0, x0, mode}: [y0, y0 + T) / [x0, x0 + T) may leave the image, mode 0..7 turns the tile as train_batch_kernel's
+// modes do.  gtab[i] = {packed offset, first tile, ny, nx, stride, nmodes, 0, 0}: tile (a, b, m) of the image is first + (a nx + b) nmodes + m.
+// np.pad(mode='reflect') continued periodically ('edge' at n = 1): always inside [0, n)
+FW_DEV int reflect_idx(int y, int n) {
+    if (n == 1) return 0;
+    const int p = 2 * n - 2;
+    int m = y % p;
+    if (m < 0) m += p;
+    return m < n ? m : p - m;
+}
+// tile (oy, ox) -> where it comes from in the unturned tile (train_batch_kernel's map: flipud last -> undone first)
+FW_DEV void mode_preimage(int mode, int T, int oy, int ox, int& py, int& px) {
+    const int k = mode >> 1, ii = (mode & 1) ? T - 1 - oy : oy, jj = ox;
+    if (k == 0) { py = ii; px = jj; }
+    else if (k == 1) { py = jj; px = T - 1 - ii; }
+    else if (k == 2) { py = T - 1 - ii; px = T - 1 - jj; }
+    else { py = T - 1 - jj; px = ii; }
+}
+// its inverse: unturned (py, px) -> where the turned tile holds it
+FW_DEV void mode_image(int mode, int T, int py, int px, int& oy, int& ox) {
+    const int k = mode >> 1;
+    int ii;
+    if (k == 0) { ii = py; ox = px; }
+    else if (k == 1) { ox = py; ii = T - 1 - px; }
+    else if (k == 2) { ii = T - 1 - py; ox = T - 1 - px; }
+    else { ox = T - 1 - py; ii = px; }
+    oy = (mode & 1) ? T - 1 - ii : ii;
+}
+// One tile per blockIdx.y.  Stores run along ox in every mode.  Modes 0..1 and 4..5 (k = 0, 2) of a tile whose columns stay inside the
+// image read four source bytes at once (reversed for k = 2); every other tile reads single bytes of the uint8 image, which for the
+// transposing modes walks down a column: the image is a quarter of the tiles' bytes and stays in cache over its 8 turns.
+__global__ void restore_gather_kernel(const long long* __restrict__ itab, const int* __restrict__ ttab, const float* __restrict__ sigma,
+                                      const unsigned* __restrict__ seed, unsigned site, float* __restrict__ tiles, int T) {
+    const int t = blockIdx.y;
+    const int im = ttab[t * 4 + 0], y0 = ttab[t * 4 + 1], x0 = ttab[t * 4 + 2], mode = ttab[t * 4 + 3] & 7;
+    const unsigned char* clean = reinterpret_cast<const unsigned char*>(itab[im * 4 + 0]);
+    const unsigned char* degr = reinterpret_cast<const unsigned char*>(itab[im * 4 + 1]);
+    const int H = (int)itab[im * 4 + 2], W = (int)itab[im * 4 + 3];
+    const unsigned char* src = degr ? degr : clean;
+    if (!src || H < 1 || W < 1) return;
+    const float sg = sigma[im];
+    const bool synth = !degr && sg > 0.f;
+    const unsigned key = fw_site_key(seed[0], site + (unsigned)im);
+    float* out = tiles + (long)t * 3 * T * T;
+    const int k = mode >> 1;
+    if ((k & 1) == 0 && x0 >= 0 && x0 + T <= W && (((long)src | W | x0) & 3) == 0) {
+        const int q = T / 4, n = 3 * T * q;
+        for (int g = blockIdx.x * blockDim.x + threadIdx.x; g < n; g += gridDim.x * blockDim.x) {
+            const int ox = (g % q) * 4, oy = (g / q) % T, c = g / (q * T);
+            int py, px;
+            mode_preimage(mode, T, oy, k ? ox + 3 : ox, py, px);                    // px: the lowest of the four source columns
+            const long pi = ((long)c * H + reflect_idx(y0 + py, H)) * W + (x0 + px);
+            unsigned char v[4];
+            *reinterpret_cast<unsigned*>(v) = *reinterpret_cast<const unsigned*>(src + pi);
+            float o[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                float d = (float)v[e];
+                if (synth) d = noisy_u8(d, sg, key, pi + e);
+                o[e] = __fdiv_rn(d, 255.0f);
+            }
+            *reinterpret_cast<float4*>(out + ((long)c * T + oy) * T + ox) = k ? make_float4(o[3], o[2], o[1], o[0]) : make_float4(o[0], o[1], o[2], o[3]);
+        }
+        return;
+    }
+    const int n = 3 * T * T;
+    for (int g = blockIdx.x * blockDim.x + threadIdx.x; g < n; g += gridDim.x * blockDim.x) {
+        const int ox = g % T, oy = (g / T) % T, c = g / (T * T);
+        int py, px;
+        mode_preimage(mode, T, oy, ox, py, px);
+        const long pi = ((long)c * H + reflect_idx(y0 + py, H)) * W + reflect_idx(x0 + px, W);   // the SOURCE pixel: also the noise counter
+        float d = (float)src[pi];
+        if (synth) d = noisy_u8(d, sg, key, pi);
+        out[g] = __fdiv_rn(d, 255.0f);
+    }
+}
+
+FW_DEV float ramp_weight(int i, int T, int ramp) { return __fdiv_rn((float)min(min(i + 1, T - i), ramp), (float)ramp); }
+// V = 4: four consecutive x per thread; every tile origin of the image is then a multiple of 4, so the four lie in the same tiles.
+// A tile of k = 0 / 2 holds them in one 16-byte word (reversed for k = 2); a transposing tile holds them down a column of the tile.
+template <int V>
+FW_DEV float restore_blend_body(const unsigned char* __restrict__ clean, const int* __restrict__ ttab, const float* __restrict__ rest,
+                                float* __restrict__ packed, unsigned char* __restrict__ u8out, int H, int W, int t0, int ny, int nx, int stride,
+                                int nmodes, int ntiles, int T, int ramp) {
+    const int wq = W / V;
+    const long n = (long)3 * H * wq;
+    float sse = 0.f;
+    for (long g = (long)blockIdx.x * blockDim.x + threadIdx.x; g < n; g += (long)gridDim.x * blockDim.x) {
+        const int x = (int)(g % wq) * V, y = (int)((g / wq) % H), c = (int)(g / ((long)wq * H));
+        // regular tiles a stride <= y < a stride + T (a <= ny - 2), then the last one; the same along x: ascending tile order
+        const int a0 = y < T ? 0 : (y - T) / stride + 1, a1 = min(y / stride, ny - 2);
+        const int b0 = x < T ? 0 : (x - T) / stride + 1, b1 = min(x / stride, nx - 2);
+        float acc[V], wsum[V];
+#pragma unroll
+        for (int e = 0; e < V; ++e) acc[e] = wsum[e] = 0.f;
+        for (int a = a0; a < ny; a = (a < a1 ? a + 1 : (a < ny - 1 ? ny - 1 : ny))) {
+            for (int b = b0; b < nx; b = (b < b1 ? b + 1 : (b < nx - 1 ? nx - 1 : nx))) {
+                const long tb = (long)t0 + ((long)a * nx + b) * nmodes;
+                if (tb < 0 || tb + nmodes > ntiles) continue;
+                const int dy = y - ttab[tb * 4 + 1], dx = x - ttab[tb * 4 + 2];
+                if (dy < 0 || dy >= T || dx < 0 || dx + V > T) continue;
+                const float wy = ramp_weight(dy, T, ramp);
+                float w[V];
+#pragma unroll
+                for (int e = 0; e < V; ++e) w[e] = __fmul_rn(wy, ramp_weight(dx + e, T, ramp));
+                for (int m = 0; m < nmodes; ++m) {
+                    const int mode = ttab[(tb + m) * 4 + 3] & 7;
+                    const float* p = rest + ((tb + m) * 3 + c) * T * T;
+                    int oy, ox;
+                    float v[V];
+                    if constexpr (V == 4) {
+                        if ((mode & 2) == 0) {                                              // k = 0, 2: along a row of the tile
+                            mode_image(mode, T, dy, (mode & 4) ? dx + 3 : dx, oy, ox);
+                            const float4 r = *reinterpret_cast<const float4*>(p + oy * T + ox);
+                            if (mode & 4) { v[0] = r.w; v[1 % V] = r.z; v[2 % V] = r.y; v[3 % V] = r.x; }
+                            else { v[0] = r.x; v[1 % V] = r.y; v[2 % V] = r.z; v[3 % V] = r.w; }
+                        } else {
+#pragma unroll
+                            for (int e = 0; e < V; ++e) {
+                                mode_image(mode, T, dy, dx + e, oy, ox);
+                                v[e] = p[oy * T + ox];
+                            }
+                        }
+                    } else {
+                        mode_image(mode, T, dy, dx, oy, ox);
+                        v[0] = p[oy * T + ox];
+                    }
+#pragma unroll
+                    for (int e = 0; e < V; ++e) {
+                        acc[e] += __fmul_rn(w[e], v[e]);
+                        wsum[e] += w[e];
+                    }
+                }
+            }
+        }
+        const long pi = ((long)c * H + y) * W + x;
+        float o[V];
+        unsigned char gt[V], q[V];
+        if (clean) {
+            if constexpr (V == 4) *reinterpret_cast<unsigned*>(gt) = *reinterpret_cast<const unsigned*>(clean + pi);
+            else gt[0] = clean[pi];
+        }
+#pragma unroll
+        for (int e = 0; e < V; ++e) {
+            o[e] = acc[e] / wsum[e];
+            if (clean) {
+                const float d = fminf(fmaxf(o[e], 0.f), 1.f) - __fdiv_rn((float)gt[e], 255.0f);
+                sse += d * d;
+            }
+            q[e] = (unsigned char)fminf(fmaxf(o[e] * 255.0f, 0.f), 255.f);           // image_io.py:383: clip, astype(uint8) truncates
+        }
+        if constexpr (V == 4) {
+            *reinterpret_cast<float4*>(packed + pi) = make_float4(o[0], o[1 % V], o[2 % V], o[3 % V]);
+            if (u8out) *reinterpret_cast<unsigned*>(u8out + pi) = *reinterpret_cast<const unsigned*>(q);
+        } else {
+            packed[pi] = o[0];
+            if (u8out) u8out[pi] = q[0];
+        }
+    }
+    return sse;
+}
+__global__ void restore_blend_kernel(const long long* __restrict__ itab, const long long* __restrict__ gtab, const int* __restrict__ ttab,
+                                     const float* __restrict__ rest, float* __restrict__ packed, unsigned char* __restrict__ u8out,
+                                     float* __restrict__ sse, int i0, int ntiles, int T, int ramp) {
+    __shared__ float red[TPB / 64];
+    const int im = i0 + blockIdx.y;
+    const unsigned char* clean = reinterpret_cast<const unsigned char*>(itab[im * 4 + 0]);
+    const int H = (int)itab[im * 4 + 2], W = (int)itab[im * 4 + 3];
+    const long long* gt = gtab + (long)im * 8;
+    const long off = gt[0];
+    const int t0 = (int)gt[1], ny = (int)gt[2], nx = (int)gt[3], stride = (int)gt[4], nmodes = (int)gt[5];
+    if (H < 1 || W < 1 || ny < 1 || nx < 1 || stride < 1 || (nmodes != 1 && nmodes != 8)) return;   // a malformed row writes nothing
+    float* pk = packed + off;
+    unsigned char* u8 = u8out ? u8out + off : nullptr;
+    float acc;
+    // tile origins are multiples of 4 when the stride and the width are (T % 4 == 0; a padded image starts at 0)
+    if ((((long)clean | (long)u8 | off | W | stride) & 3) == 0 && ((long)pk & 15) == 0)
+        acc = restore_blend_body<4>(clean, ttab, rest, pk, u8, H, W, t0, ny, nx, stride, nmodes, ntiles, T, ramp);
+    else
+        acc = restore_blend_body<1>(clean, ttab, rest, pk, u8, H, W, t0, ny, nx, stride, nmodes, ntiles, T, ramp);
+    if (!clean) return;
+    acc = block_sum(acc, red);
+    if (threadIdx.x == 0) atomicAdd(sse + im, acc);
+}
 }  // namespace
 
 #define ST ((hipStream_t)stream)
@@ -357,6 +547,23 @@ extern "C" int fw_eval_blend(const void* itab, const void* gtab, const int* ttab
                  ((uintptr_t)rest & 15) == 0);
     hipLaunchKernelGGL(eval_blend_kernel, dim3(64, (unsigned)nimg), dim3(TPB), 0, ST, (const long long*)itab, (const long long*)gtab, ttab,
                        rest, packed, (unsigned char*)u8out, sse, i0, ntiles, T);
+    FW_LAUNCH_RET();
+}
+extern "C" int fw_restore_gather(const void* itab, const int* ttab, const float* sigma, const void* seed, int site, float* tiles, int N, int T,
+                                 void* stream) {
+    FW_CHECK_ARG(itab && ttab && sigma && seed && tiles && N > 0 && N <= 65535 && T > 0 && T % 4 == 0 && ((uintptr_t)tiles & 15) == 0);
+    long gx = ((long)3 * T * T / 4 + TPB - 1) / TPB;
+    if (gx > 256) gx = 256;
+    hipLaunchKernelGGL(restore_gather_kernel, dim3((unsigned)gx, (unsigned)N), dim3(TPB), 0, ST, (const long long*)itab, ttab, sigma,
+                       (const unsigned*)seed, (unsigned)site, tiles, T);
+    FW_LAUNCH_RET();
+}
+extern "C" int fw_restore_blend(const void* itab, const void* gtab, const int* ttab, const float* rest, float* packed, void* u8out, float* sse,
+                                int i0, int nimg, int ntiles, int T, int ramp, void* stream) {
+    FW_CHECK_ARG(itab && gtab && ttab && rest && packed && sse && i0 >= 0 && nimg > 0 && nimg <= 65535 && ntiles > 0 && T > 0 && T % 4 == 0 &&
+                 ramp >= 1 && (ramp == 1 || ramp <= T / 2) && ((uintptr_t)rest & 15) == 0);
+    hipLaunchKernelGGL(restore_blend_kernel, dim3(64, (unsigned)nimg), dim3(TPB), 0, ST, (const long long*)itab, (const long long*)gtab, ttab,
+                       rest, packed, (unsigned char*)u8out, sse, i0, ntiles, T, ramp);
     FW_LAUNCH_RET();
 }
 extern "C" int fw_eval_ssim7(const void* itab, const void* gtab, const float* packed, float* out, int i0, int nimg, void* stream) {

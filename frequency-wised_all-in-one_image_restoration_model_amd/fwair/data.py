@@ -47,12 +47,13 @@ def crop_img(arr, base=16):
     return arr[crop_h // 2:h - crop_h + crop_h // 2, crop_w // 2:w - crop_w + crop_w // 2, :]
 
 
-def load_u8(path):
-    """dataset_utils.py:118: crop_img(np.array(Image.open(path).convert('RGB')), base=16), returned channels first: uint8 [3, H, W]."""
+def load_u8(path, crop=True):
+    """dataset_utils.py:118: crop_img(np.array(Image.open(path).convert('RGB')), base=16), returned channels first: uint8 [3, H, W].
+    crop=False keeps the image's own size (restore.py --keep_size)."""
     from PIL import Image
     with Image.open(path) as im:
         arr = np.array(im.convert('RGB'))
-    return np.ascontiguousarray(crop_img(arr, base=16).transpose(2, 0, 1))
+    return np.ascontiguousarray((crop_img(arr, base=16) if crop else arr).transpose(2, 0, 1))
 
 
 def _name(path):

@@ -10,7 +10,9 @@ structural_similarity defaults: 7x7 uniform window, sample covariance, 3-pixel b
 
 `EvalEngine` does the same for a whole test set at a time: images of different sizes are taken in chunks that fill a fixed tile buffer,
 one fw_eval_gather / fw_eval_blend / fw_eval_ssim7 launch per chunk (tables in device memory), the network at ONE fixed batch shape
-replayed from a HIP graph, metrics left on the device -- no host synchronisation per image.
+replayed from a HIP graph, metrics left on the device -- no host synchronisation per image.  With a tile overlap, the x8 self-ensemble
+or images smaller than the tile it plans with `plan_tiles_ex` and launches fw_restore_gather / fw_restore_blend instead: tiles that may
+leave the image (reflection), a ramp-weighted overlap, the eight flips / rotations turned back before they are averaged.
 """
 import sys
 
@@ -92,6 +94,38 @@ def plan_tiles(sizes, tile, chunk_tiles):
     return np.array(rows, dtype=np.int32).reshape(-1, 4), np.array(geo, dtype=np.int64).reshape(-1, 4), chunks
 
 
+def tile_origins_ex(size, tile, overlap=0, pad_small=False):
+    """Origins along one axis of an image of any size: P = max(size, tile), range(0, P - tile, tile - overlap) + [P - tile].  overlap = 0
+    is test.py:47-48.  An image smaller than the tile gets the one origin 0: fw_restore_gather reflects it at the bottom / right."""
+    assert 0 <= overlap <= tile // 2
+    assert size >= tile or (pad_small and size >= 1), 'invalid test image size'
+    P = max(size, tile)
+    return list(range(0, P - tile, tile - overlap)) + [P - tile]
+
+
+def plan_tiles_ex(sizes, tile, chunk_tiles, overlap=0, nmodes=1, pad_small=False):
+    """plan_tiles for fw_restore_gather / fw_restore_blend: tiles that overlap by `overlap` pixels (tile_origins_ex), each in `nmodes`
+    (1 or 8) flips / rotations, images smaller than the tile allowed with `pad_small`.
+    ttab int32 [N, 4] = {image, y0, x0, mode}, the modes of a position next to each other; gtab int64 [I, 8] = {offset in the chunk's
+    packed buffer, first tile counted from the chunk's t0, ny, nx, stride, nmodes, 0, 0}; chunks as plan_tiles makes them."""
+    assert nmodes in (1, 8)
+    rows, geo, chunks = [], [], []
+    i0 = t0 = off = 0
+    for i, (H, W) in enumerate(sizes):
+        ys, xs = tile_origins_ex(H, tile, overlap, pad_small), tile_origins_ex(W, tile, overlap, pad_small)
+        n = len(ys) * len(xs) * nmodes
+        if n > chunk_tiles:
+            raise ValueError(f'fwair: image {i} ({H} x {W}) has {n} tiles of {tile}, the tile buffer holds {chunk_tiles}')
+        if len(rows) - t0 + n > chunk_tiles:
+            chunks.append((i0, i, t0, len(rows)))
+            i0, t0, off = i, len(rows), 0
+        geo.append((off, len(rows) - t0, len(ys), len(xs), tile - overlap, nmodes, 0, 0))
+        rows += [(i, y, x, m) for y in ys for x in xs for m in range(nmodes)]
+        off += 3 * H * W
+    chunks.append((i0, len(sizes), t0, len(rows)))
+    return np.array(rows, dtype=np.int32).reshape(-1, 4), np.array(geo, dtype=np.int64).reshape(-1, 8), chunks
+
+
 class EvalEngine:
     """test.py:36-84 for a list of images at device rate.
 
@@ -105,13 +139,21 @@ class EvalEngine:
     padded outputs are never read), so that ONE captured HIP graph serves every batch; use_graph=False launches the same forward eagerly.
     Nothing in run() waits for the device once the tables of a given input list are uploaded (they are cached); the caller
     synchronises when it reads the results.  The captured graph reads the weights in place: build a new engine (or call `reset()`)
-    after the weights were changed by anything but in-place updates."""
+    after the weights were changed by anything but in-place updates.
+    overlap > 0: neighbouring tiles share `overlap` pixels (at most tile / 2) and are blended with a linear ramp of that width, so that
+    no tile border shows.  ensemble: every tile also runs in its 7 flips / rotations and the 8 results, turned back, are averaged
+    (the tile buffer then holds 8 times as many tiles by default).  pad_small: an image smaller than the tile is reflect-padded at the
+    bottom and right instead of refused.  With all three off, and no small image, run() is the path above with its tables and entries;
+    otherwise plan_tiles_ex, fw_restore_gather and fw_restore_blend (ramp = max(overlap, 1)) take their place -- nothing else changes."""
 
-    def __init__(self, net, tile=128, tile_batch=64, use_graph=True, chunk_tiles=None):
+    def __init__(self, net, tile=128, tile_batch=64, use_graph=True, chunk_tiles=None, overlap=0, ensemble=False, pad_small=False):
         assert tile % 8 == 0, 'patch size should be a multiple of window_size'            # test.py:44
         self.net, self.tile, self.tb = net, int(tile), int(tile_batch)
         self.use_graph = bool(use_graph)
-        self.cap = -(-int(chunk_tiles or 16 * self.tb) // self.tb) * self.tb
+        self.overlap, self.ensemble, self.pad_small = int(overlap), bool(ensemble), bool(pad_small)
+        if not 0 <= self.overlap <= self.tile // 2:
+            raise ValueError(f'fwair: tile overlap {overlap} is not in 0 .. tile / 2 = {self.tile // 2}')
+        self.cap = -(-int(chunk_tiles or 16 * self.tb * (8 if self.ensemble else 1)) // self.tb) * self.tb
         self.dev = next(net.parameters()).device
         self._seed = 0
         self.seed_word = torch.zeros(1, dtype=torch.int32, device=self.dev)
@@ -128,7 +170,8 @@ class EvalEngine:
         I = len(ref)
         sig = [float(s) for s in sigma] if isinstance(sigma, (list, tuple)) else [float(sigma)] * I
         key = (tuple((t.data_ptr(), tuple(t.shape)) for t in clean) if clean is not None else None,
-               tuple((t.data_ptr(), tuple(t.shape)) for t in degraded) if degraded is not None else None, tuple(sig), self.cap)
+               tuple((t.data_ptr(), tuple(t.shape)) for t in degraded) if degraded is not None else None, tuple(sig), self.cap,
+               self.overlap, self.ensemble, self.pad_small)
         plan = self._plans.get(key)
         if plan is None:
             for lst in (clean, degraded):
@@ -136,16 +179,21 @@ class EvalEngine:
                     assert t.dtype == torch.uint8 and t.dim() == 3 and t.shape[0] == 3 and t.is_contiguous() and t.device == self.dev
                     assert t.shape == r.shape, 'a degraded image must have the shape of its ground truth'
             sizes = [tuple(t.shape[1:]) for t in ref]
-            ttab, gtab, chunks = plan_tiles(sizes, self.tile, self.cap)
+            ex = self.overlap > 0 or self.ensemble or any(min(h, w) < self.tile for h, w in sizes)
+            if ex:
+                ttab, gtab, chunks = plan_tiles_ex(sizes, self.tile, self.cap, self.overlap, 8 if self.ensemble else 1, self.pad_small)
+            else:                                            # today's tables for today's entries: bit-identical results
+                ttab, gtab, chunks = plan_tiles(sizes, self.tile, self.cap)
             itab = np.array([[clean[i].data_ptr() if clean is not None else 0, degraded[i].data_ptr() if degraded is not None else 0,
                               sizes[i][0], sizes[i][1]] for i in range(I)], dtype=np.int64)
             up = lambda a: torch.from_numpy(a).to(self.dev)
             if len(self._plans) >= 8:
                 self._plans.clear()
             plan = self._plans[key] = dict(
-                I=I, sizes=sizes, chunks=chunks, itab=up(itab), ttab=up(ttab), gtab=up(gtab), sigma=up(np.array(sig, dtype=np.float32)),
+                I=I, sizes=sizes, chunks=chunks, ex=ex, itab=up(itab), ttab=up(ttab), gtab=up(gtab),
+                gtab4=up(np.ascontiguousarray(gtab[:, :4])), sigma=up(np.array(sig, dtype=np.float32)),
                 npix=up(np.array([3.0 * h * w for h, w in sizes], dtype=np.float32)),
-                nwin=up(np.array([3.0 * (h - 6) * (w - 6) for h, w in sizes], dtype=np.float32)),
+                nwin=up(np.array([3.0 * max(h - 6, 0) * max(w - 6, 0) for h, w in sizes], dtype=np.float32)),   # no 7 x 7 window: nan
                 max_px=max(sum(3 * h * w for h, w in sizes[i0:i1]) for i0, i1, _, _ in chunks))
         return plan
 
@@ -212,14 +260,19 @@ class EvalEngine:
         for i0, i1, t0, t1 in plan['chunks']:
             n = t1 - t0
             ttab = plan['ttab'][t0:]
-            call('fw_eval_gather', plan['itab'], ttab, plan['sigma'], self.seed_word, _EVAL_SITE, self.tiles, n, T)
+            call('fw_restore_gather' if plan['ex'] else 'fw_eval_gather', plan['itab'], ttab, plan['sigma'], self.seed_word, _EVAL_SITE,
+                 self.tiles, n, T)
             for s in range(0, n, self.tb):
                 self._forward(s, min(self.tb, n - s))
             px = sum(3 * h * w for h, w in plan['sizes'][i0:i1])
             u8 = torch.empty(px, dtype=torch.uint8, device=self.dev) if want_u8 else None
-            call('fw_eval_blend', plan['itab'], plan['gtab'], ttab, self.rest, self.packed, u8, sse, i0, i1 - i0, n, T)
+            if plan['ex']:
+                call('fw_restore_blend', plan['itab'], plan['gtab'], ttab, self.rest, self.packed, u8, sse, i0, i1 - i0, n, T,
+                     max(self.overlap, 1))
+            else:
+                call('fw_eval_blend', plan['itab'], plan['gtab'], ttab, self.rest, self.packed, u8, sse, i0, i1 - i0, n, T)
             if clean_u8 is not None:
-                call('fw_eval_ssim7', plan['itab'], plan['gtab'], self.packed, ssum, i0, i1 - i0)
+                call('fw_eval_ssim7', plan['itab'], plan['gtab4'], self.packed, ssum, i0, i1 - i0)     # [I][4]: the first four columns
             off = 0
             for h, w in plan['sizes'][i0:i1]:
                 if want_u8:

@@ -5,6 +5,12 @@ reused: a `test.py` on sys.path shadows the standard library's `test` package).
     python restore.py --epochs 1000 --output_path output/run/ --test_de_type denoising_bsd68_25 deraining [--data_root data/]
                       [--ckpt FILE] [--save_imgs True]
     python restore.py --ckpt FILE --input PATH --output DIR          (PATH: an image or a directory of images; no ground truth, no metrics)
+                      [--keep_size] [--tile_overlap N] [--self_ensemble]
+
+`--tile_overlap N` lets neighbouring tiles share N pixels (at most half a tile) and blends them with a linear ramp, so that the tile grid
+does not show; `--self_ensemble` averages the 8 flips / rotations of every tile; both also apply to the test sets, whose PSNR / SSIM
+then are those of the blended / ensembled images.  `--input` takes images of any size (one smaller than the tile is reflect-padded);
+`--keep_size` restores them at their own size instead of the datasets' centre crop to multiples of 16.
 
 Loads `<output_path>ckpt/epoch_<epochs>.pth` (train.py:126) unless `--ckpt` names a file, restores every test set of `--test_de_type`
 through fwair.evaluate.EvalEngine (tiles of `--crop_test_imgs_size`, test.py:47-71 averaging the RESTORED tiles; Gaussian noise of
@@ -24,6 +30,9 @@ _own.add_argument('--input', type=str, default='', help='an image, or a director
 _own.add_argument('--output', type=str, default='', help='where --input images are written')
 _own.add_argument('--tile_batch', type=int, default=64, help='tiles per forward pass')
 _own.add_argument('--no_graph', action='store_true', help='eager launches instead of HIP-graph replay')
+_own.add_argument('--tile_overlap', type=int, default=0, help='pixels neighbouring tiles share (at most half a tile), blended with a ramp')
+_own.add_argument('--self_ensemble', action='store_true', help='average the 8 flips / rotations of every tile (8 times the work)')
+_own.add_argument('--keep_size', action='store_true', help='--input: restore the image at its own size, not cropped to multiples of 16')
 _ARGS, _rest = _own.parse_known_args()
 sys.argv = [sys.argv[0]] + _rest                       # option.py parses sys.argv at import (reference option.py:3)
 
@@ -37,9 +46,11 @@ from option import options as opt                       # noqa: E402
 _ENGINE = {}
 
 
-def _engine(net):
-    if _ENGINE.get('net') is not net:
-        _ENGINE.update(net=net, engine=EvalEngine(net, tile=opt.crop_test_imgs_size, tile_batch=_ARGS.tile_batch, use_graph=not _ARGS.no_graph))
+def _engine(net, pad_small=False):
+    if _ENGINE.get('net') is not net or _ENGINE.get('pad_small') != pad_small:
+        _ENGINE.update(net=net, pad_small=pad_small,
+                       engine=EvalEngine(net, tile=opt.crop_test_imgs_size, tile_batch=_ARGS.tile_batch, use_graph=not _ARGS.no_graph,
+                                         overlap=_ARGS.tile_overlap, ensemble=_ARGS.self_ensemble, pad_small=pad_small))
     return _ENGINE['engine']
 
 
@@ -70,17 +81,13 @@ def test_by_task(net, task, epochs):
 
 
 def restore_files(net, src, dst):
-    """--input / --output: every image of `src` (cropped to multiples of 16 as the datasets do), restored, written as <name>.png."""
+    """--input / --output: every image of `src` (cropped to multiples of 16 as the datasets do, unless --keep_size), restored, written
+    as <name>.png.  Any size goes: an image smaller than the tile is reflect-padded to one tile and cut back."""
     paths = sorted(os.path.join(src, f) for f in os.listdir(src)) if os.path.isdir(src) else [src]
     dev = next(net.parameters()).device
-    imgs = []
-    for p in paths:
-        im = load_u8(p)
-        H, W = im.shape[1:]
-        assert H >= opt.crop_test_imgs_size and W >= opt.crop_test_imgs_size, "invalid test image size (%d, %d)" % (H, W)
-        imgs.append(torch.from_numpy(im).to(dev))
+    imgs = [torch.from_numpy(load_u8(p, crop=not _ARGS.keep_size)).to(dev) for p in paths]
     os.makedirs(dst, exist_ok=True)
-    _, _, out = _engine(net).run(None, imgs, want_u8=True)
+    _, _, out = _engine(net, pad_small=True).run(None, imgs, want_u8=True)
     for p, img in zip(paths, out):
         save_u8(img, os.path.join(dst, os.path.basename(p).split('.')[0] + '.png'))
     return len(paths)

@@ -403,6 +403,27 @@ int fw_eval_blend(const void* itab, const void* gtab, const int* ttab, const flo
 /* utils/val_utils.py:64 as fw_ssim7 computes it, between the packed restored images and the clean uint8 images of the tables:
  * out[image] += sum of the SSIM map over channels and interior pixels, for images i0 .. i0 + nimg - 1. */
 int fw_eval_ssim7(const void* itab, const void* gtab, const float* packed, float* out, int i0, int nimg, void* stream);
+/* fw_eval_gather / fw_eval_blend for images of any size, overlapping tiles and the x8 self-ensemble (fwair/evaluate.py plan_tiles_ex).
+ * itab as above; ttab: int32 [N][4] = {image, y0, x0, mode}, where [y0, y0 + T) x [x0, x0 + T) may leave the image and mode (taken & 7)
+ * is one of fw_train_batch's flips / rotations (utils/image_utils.py:133-175) with 0 = none; gtab: int64 [I][8] = {offset of the image in
+ * the packed buffer (elements), its first tile in the chunk, ny, nx, stride, nmodes (1 or 8), 0, 0}: tile (a, b, m) of the image is row
+ * first + (a nx + b) nmodes + m of ttab.  (fw_eval_ssim7 takes the first four columns as a table of its own.)
+ * fw_restore_gather: tiles[t][c][oy][ox] = source[c][R(y0 + py, H)][R(x0 + px, W)] / 255, (py, px) = the preimage of (oy, ox) under mode:
+ * k = mode >> 1, ii = (mode & 1) ? T - 1 - oy : oy, jj = ox; k = 0: (ii, jj), 1: (jj, T - 1 - ii), 2: (T - 1 - ii, T - 1 - jj),
+ * 3: (T - 1 - jj, ii).  R = whole-sample reflection continued periodically: R(y, 1) = 0, otherwise p = 2 n - 2, m = ((y mod p) + p) mod p,
+ * R = m < n ? m : p - m (np.pad 'reflect' for every pad width), so no origin reads outside the image.  The source is the degraded image
+ * or the clean one with fw_eval_gather's noise, whose counter is the flat CHW index of the SOURCE pixel in the unpadded image:
+ * reflected copies, overlapping tiles and the eight turns see one noisy image. */
+int fw_restore_gather(const void* itab, const int* ttab, const float* sigma, const void* seed, int site, float* tiles, int N, int T,
+                      void* stream);
+/* packed / u8out / sse as fw_eval_blend writes them, with out[c][y][x] = sum(w v) / sum(w) over the tiles (a, b, m) whose footprint in
+ * the image holds (y, x), in ascending tile order (at most 3 x 3 x 8 terms when the overlap is at most T / 2): v = rest[t][c][oy][ox] at
+ * the image of (y - y0, x - x0) under the tile's mode (the turn undone), w = w1(y - y0) w1(x - x0), w1(i) = (float)min(i + 1, T - i, ramp) /
+ * (float)ramp (symmetric, so the same in every mode; the quotient and the product rounded once each).  ramp = 1: fw_eval_blend's plain
+ * mean.  1 <= ramp <= T / 2 or ramp == 1.  Candidates per axis: the regular tiles a stride <= y < a stride + T with a <= ny - 2, and
+ * tile ny - 1.  Gather form, no atomics on pixels. */
+int fw_restore_blend(const void* itab, const void* gtab, const int* ttab, const float* rest, float* packed, void* u8out, float* sse,
+                     int i0, int nimg, int ntiles, int T, int ramp, void* stream);
 
 /* ---- fused LeFF forward (net/utils/leff.py:92-117) for the high-resolution stages, bf16 operands ----------------------------
  * y = res + rowscale * linear2(GELU(dwconv3x3(GELU(linear1(xn))))) in one kernel per 8 x 16 pixel patch: the hidden tensor is

@@ -5,7 +5,10 @@
       image's tiles), psnr and ssim with a host sync each;
   (b) fwair.evaluate.EvalEngine.run on the resident uint8 images: chunks of tiles, HIP-graph replay at a fixed batch, metrics on the device.
 Each is the median of 5 repeats after one warm-up, torch.cuda.synchronize() around each repeat.  Prints one JSON line
-(the record kept as profiles/r05_eval_rate.json)."""
+(the record kept as profiles/r05_eval_rate.json).
+  (c) `--restore`: EvalEngine with overlap=32, and with overlap=32, ensemble=True (fw_restore_gather / fw_restore_blend), next to (b):
+      seconds, tiles and seconds per tile of each, and the summed time of the gather and blend launches as a share of the arm
+      (the record kept as profiles/r12_restore_rate.json)."""
 import json
 import os
 import statistics
@@ -75,6 +78,55 @@ def timed(fn):
         ts.append(time.perf_counter() - t0)
     return statistics.median(ts), ts, out
 
+
+def restore_arm(overlap, ensemble):
+    """Arm (c): EvalEngine with overlapping tiles / the x8 self-ensemble (fw_restore_gather / fw_restore_blend).  -> seconds, tiles,
+    seconds per tile, and the summed time of the gather and blend launches of the chunks (hipEvent pairs around each, one run on its
+    own after the timed repeats) as a share of the arm."""
+    eng = EV.EvalEngine(net, tile=128, tile_batch=64, use_graph=True, overlap=overlap, ensemble=ensemble)
+
+    def run():
+        p, s = eng.run(resident, sigma=25, seed=0)
+        return float(p.mean()), float(s.mean())
+
+    t, ts, (p, s) = timed(run)
+    (plan,) = eng._plans.values()
+    tiles = int(plan['ttab'].shape[0])
+    pairs, real = [], EV.call
+
+    def timed_call(name, *args):
+        if name in ('fw_restore_gather', 'fw_restore_blend'):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            real(name, *args)
+            b.record()
+            pairs.append((name, a, b))
+        else:
+            real(name, *args)
+
+    EV.call = timed_call
+    try:
+        run()
+    finally:
+        EV.call = real
+    torch.cuda.synchronize()
+    ms = {n: sum(a.elapsed_time(b) for m, a, b in pairs if m == n) for n in ('fw_restore_gather', 'fw_restore_blend')}
+    return {'overlap': overlap, 'ensemble': ensemble, 'seconds': round(t, 4), 'repeats_s': [round(x, 4) for x in ts], 'tiles': tiles,
+            'seconds_per_tile': round(t / tiles, 6), 'chunks': len(plan['chunks']), 'engine_graph': bool(eng.use_graph),
+            'gather_ms': round(ms['fw_restore_gather'], 3), 'blend_ms': round(ms['fw_restore_blend'], 3),
+            'gather_blend_share': round((ms['fw_restore_gather'] + ms['fw_restore_blend']) * 1e-3 / t, 5), 'psnr_ssim': [round(p, 3), round(s, 4)]}
+
+
+if '--restore' in sys.argv[1:]:
+    # the record kept as profiles/r12_restore_rate.json: arm (b) next to arm (c) at overlap 32, without and with the ensemble
+    tb, tbs, (pb, sb) = timed(batched)
+    print(json.dumps({'metric': 'seconds to evaluate one test set: 68 images of 320 x 480, sigma 25, bf16, tiles of 128',
+                      'eval_engine': {'seconds': round(tb, 4), 'repeats_s': [round(t, 4) for t in tbs], 'tiles': n_tiles,
+                                      'seconds_per_tile': round(tb / n_tiles, 6), 'psnr_ssim': [round(pb, 3), round(sb, 4)]},
+                      'restore_overlap32': restore_arm(32, False), 'restore_overlap32_ensemble': restore_arm(32, True), 'tile_batch': 64,
+                      'note': 'median of 5 repeats after one warm-up, synchronised around each repeat; gather_ms / blend_ms: hipEvent pairs '
+                              'around the launches of one further run; untrained weights'}))
+    sys.exit(0)
 
 ta, tas, (pa, sa) = timed(per_image)
 tb, tbs, (pb, sb) = timed(batched)
