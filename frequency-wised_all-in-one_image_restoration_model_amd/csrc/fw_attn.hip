@@ -1346,6 +1346,11 @@ int dispatch(bool bwd, int D, int nkt, int lfs, const AttnArgs& a, hipStream_t s
     if (D == DD && nkt == 1 && a.mode == 0 && lfs == FF)                                       \
         return bwd ? bwd2_launch<T, DD, FF>(a, st) : fwd2_launch<T, DD, FF>(a, st);
     FW_ATT2(56, 0) FW_ATT2(56, 1) FW_ATT2(56, 2) FW_ATT2(28, 0) FW_ATT2(64, 0)
+    // the decoder at --embed_dim 32 / 64 (head_dim = embed_dim at every stage).  Geo<T, 64> is Geo<T, 56> without the padding granule
+    // (CH == SL); Geo<T, 32> is the D = 28 tile (KC 1 / 2, DT 2) without padding and with 16-byte granules in bf16, one TileLoad
+    // round per tile.  The filter scratch (Smem2::SCR) does not depend on D and covers TILE_D at both widths, so the O / dV / dK
+    // staging rows fit; dq_pad is 0 (heads * D % 8 == 0).  Two workgroups per CU where 2 x LDS bytes <= 160 KB (fwd2_ / bwd2_launch).
+    FW_ATT2(64, 1) FW_ATT2(64, 2) FW_ATT2(32, 0) FW_ATT2(32, 1) FW_ATT2(32, 2)
 #undef FW_ATT2
     // inter-band, three bands: both key tiles in one pass
     if (D == 28 && nkt == 2 && a.mode == 1 && a.L == 3 && lfs == 0) return x2_launch<T, 28>(bwd, a, st);
@@ -1362,7 +1367,8 @@ int dispatch(bool bwd, int D, int nkt, int lfs, const AttnArgs& a, hipStream_t s
 
 extern "C" int fw_attn_lfs_table_elems() { return OFF_END; }
 
-// dtype: 0 f32 / 1 bf16.  head_dim D in {56, 28} (Uformer) or 64 (ViT encoder: one 64-token "window" per image, zero bias table).  nkt: key tiles of 64 (2 = inter-band, L = 3).
+// dtype: 0 f32 / 1 bf16.  head_dim D in {56, 28} (Uformer), {32, 64} (Uformer decoder at --embed_dim 32 / 64: mode 0, any lfs) or 64 (ViT encoder: one
+// 64-token "window" per image, zero bias table).  nkt: key tiles of 64 (2 = inter-band, L = 3).
 // lfs: 0 none, 1 affine (all_DC / all_2_bands), 2 affine + disc filter (all_3_bands).
 extern "C" int fw_attn_fwd(int dtype, int D, int nkt, int lfs, const void* q, const void* k, const void* v, long ld,
                            void* out, long ldo, float* lse, const float* bias, const float* coef, const void* lfs_tab,

@@ -21,6 +21,7 @@ from . import ops
 from .lib import call
 
 WIN = 8
+DECODER_WIDTHS = (32, 56, 64)       # --embed_dim the decoder runs at; --encoder_embed_dim stays 28 (the LFS heads hard-code 28 * 16)
 # Tokens from which LeFF.run takes the fused forward kernel (csrc/fw_leff.hip).  OFF by default: measured on MI355X the fused kernel
 # LOSES to the unfused chain on every high-resolution stage (tools/leff_probe.py: 1050 vs 490 us at C = 112, 262 144 tokens; 901 us
 # even with its four twin stores removed) -- the 1.5x halo of GELU evaluations and the per-chunk weight fragments from L2 cost more
@@ -300,7 +301,11 @@ class UformerDecoder(nn.Module):
             if 'all' not in m and m not in ('None', 'none'):
                 raise NotImplementedError(f'degradation_embedding_method={m!r} does not run in the reference either '
                                           '(SURVEY.md 0.1); supported: all_3_bands, all_2_bands, all_DC')
-        E = opt.embed_dim
+        E = int(opt.embed_dim)
+        if E not in DECODER_WIDTHS:
+            # head_dim = embed_dim at every stage: window attention (csrc/fw_attn.hip) is instantiated for these three
+            raise NotImplementedError(f'embed_dim={E}: the decoder runs at widths {", ".join(map(str, DECODER_WIDTHS))} '
+                                      '(head_dim = embed_dim at every stage; the HIP window attention takes 32, 56 and 64)')
         self.embed_dim, self.win_size, self.reso, self.in_chans = E, win_size, img_size, in_chans
         methods = [t for t in opt.degradation_embedding_method if 'all' in t]
         depths = list(depths)

@@ -31,10 +31,13 @@ def _apply_dtype(opt):
 def options_from_checkpoint(opt, sd):
     """Set on `opt` what a state_dict itself tells about the model it was saved from, so that restoring it does not depend on the
     command line repeating it: the training batch from the MoCo queue (K = 3 * batch_size, net/model.py:35 of the reference) and
-    `learnable_modulator` from the presence of the decoder blocks' `modulator.weight` tables (decoder_Uformer.py:536-537)."""
+    `learnable_modulator` from the presence of the decoder blocks' `modulator.weight` tables (decoder_Uformer.py:536-537), and the
+    Uformer decoder's width `embed_dim` from the output channels of its input projection (decoder_Uformer.py:905)."""
     if 'E.E.queue' in sd:
         opt.batch_size = sd['E.E.queue'].shape[-1] // 3
     opt.learnable_modulator = any(k.startswith('R.R.') and k.endswith('.modulator.weight') for k in sd)
+    if 'R.R.input_proj.proj.0.weight' in sd:
+        opt.embed_dim = int(sd['R.R.input_proj.proj.0.weight'].shape[0])
     return opt
 
 

@@ -32,7 +32,7 @@ _FLAGS = [
     ('--frequency_decompose_type', dict(type=str, default='none', help='should be in [%_bands, DC, none].')),
     ('--debug_mode', dict(type=bool, default=False, help='whether or not to enable debug mode.')),
     ('--encoder_embed_dim', dict(type=int, default=28, help='the embedding dimensionality of Uformer Encoder.')),
-    ('--embed_dim', dict(type=int, default=56, help='the embedding dimensionality of Uformer Decoder.')),
+    ('--embed_dim', dict(type=int, default=56, help='the embedding dimensionality of Uformer Decoder: 32, 56 or 64.')),
     ('--degradation_embedding_method', dict(nargs='+', type=str, default=['residual'],
                                             help='degradation embedding method (all_%_bands, all_DC run; see SURVEY 0.1).')),
     ('--learnable_modulator', dict(type=bool, default=False, help='add learnable modulator in Uformer decoder.')),

@@ -16,8 +16,8 @@ Loads `<output_path>ckpt/epoch_<epochs>.pth` (train.py:126) unless `--ckpt` name
 through fwair.evaluate.EvalEngine (tiles of `--crop_test_imgs_size`, test.py:47-71 averaging the RESTORED tiles; Gaussian noise of
 the denoising sets from seed 0, test.py:88) and writes `<output_path>epoch_<epochs>_results.log` in the line format of test.py:96-100.
 `--save_imgs True` also writes `<output_path>epoch_<E>_imgs/test_<task>/<name>.png` (test.py:20-26,77-78).  The model flags
-(`--degradation_embedding_method`, `--compute_dtype`, ...) must be those the checkpoint was trained with; the training batch size and
-`--learnable_modulator` are read off the checkpoint itself (net.model.options_from_checkpoint).
+(`--degradation_embedding_method`, `--compute_dtype`, ...) must be those the checkpoint was trained with; the training batch size,
+`--learnable_modulator` and `--embed_dim` are read off the checkpoint itself (net.model.options_from_checkpoint).
 """
 import argparse
 import os
@@ -98,7 +98,7 @@ def main():
     dev = torch.device('cuda', opt.cuda)
     path = _ARGS.ckpt or opt.ckpt_path + 'epoch_%s.pth' % str(opt.epochs)
     sd = torch.load(path, map_location=dev, weights_only=True)
-    options_from_checkpoint(opt, sd)                          # batch_size from the MoCo queue, learnable_modulator from the tables
+    options_from_checkpoint(opt, sd)                          # batch_size from the MoCo queue, learnable_modulator from the tables, embed_dim from the input projection
     net = AirNet(opt).to(dev)
     net.load_state_dict(sd)
     net.eval()

@@ -97,7 +97,8 @@ int fw_modulator_bwd(int dtype, const void* dy, long lddy, float* dmod, float* p
 
 /* ---- window attention (decoder_Uformer.py:240-293 with :387-409,634-651,678-686,721-729 folded in;
  *      encoder_Uformer.py:152-183 "origin", :256-310 intra / inter band attention) ---------------------
- * q/k/v: T rows = tokens of B*L images of H x W, head h at column h*D; D in {56, 28}.
+ * q/k/v: T rows = tokens of B*L images of H x W, head h at column h*D; D in {56, 28}, or {32, 64}
+ * (decoder at --embed_dim 32 / 64 and the ViT body: mode 0, nkt 1, any lfs; D = 32 is not taken with mode 1).
  * L: bands (1 for the decoder); mode 0: keys = the query's own band, 1: keys = the other L-1 bands (nkt = L-1).
  * bias: f32 [L*L][225][heads] relative-position tables; shift: cyclic shift (0 or 4).
  * lfs: 0 none; 1 P' = a P + b; 2 P' = a P + b + c B1(P) with coef f32 [B][heads][3] = (a,b,c) and lfs_tab the
