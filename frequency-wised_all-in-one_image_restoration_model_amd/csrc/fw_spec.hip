@@ -1,0 +1,222 @@
+// Band statistics of the 2-D spectrum of maps of ANY size: H x W with 8 <= H, W <= 1024 independent of each other (odd sides,
+// W % 4 != 0 included).  out[image][band] = sum over the frequency bins of the band of |DFT2(map)| or |DFT2(map)|^2, the DFT
+// un-normalised (utils/visualization_utils.py:158-184 get_frequency_distribution, and the per-band error energy of restore.py).
+//
+// The arithmetic is fw_dft.hip's: exact f32 products on v_mfma_f32_16x16x4_f32, f32 accumulation, both operands read as ready-made
+// fragments through L2, a 64 x 64 output tile per workgroup (4 waves, 2 x 2), no LDS tile.  Two passes and a fold:
+//     row pass      T^t[v][y] = sum_x src(y, x) W_W[x][v]        real in, complex out; the SOURCE is converted in the loader
+//                                                                (f32 map, u8 map, or clamp(restored, 0, 1) - clean / 255)
+//     column pass   F[u][v]   = sum_y T^t[v][y] W_H[y][u]        never written: the epilogue takes |F| or |F|^2, looks the bin's band
+//                                                                up in ring[u][v] and reduces per band -> one f32 per (map, tile, band)
+//     fold          out[n][b] = sum over the tiles, in tile order, in double
+// Half the spectrum.  The maps are real, so |F[(H - u) % H][(W - v) % W]| = |F[u][v]|: both passes compute the columns v <= W / 2 only,
+// and the epilogue adds a bin's value to the band of its mirror bin as well (looked up in the ring on its own -- the ring need not be
+// symmetric) unless the bin is its own mirror column (v = 0, or 2 v = W).
+// Edges.  Hp = 64 ceil(H / 64), Wp = 64 ceil(W / 64), Wh = 64 ceil((W / 2 + 1) / 64).  The panels come zero-filled to [3][Hp][Hp] and
+// [3][Wp][Wp], T^t is [Wh][Hp]: every panel and work-buffer access is a whole in-bounds 16-byte piece.  The row pass writes ALL of
+// T^t (a padded y meets zero data rows; the rows v > W / 2 of the last tile are computed or zero, and belong to no band), so the
+// column pass reads only what the row pass wrote.  The caller's maps and ring have pitch W: their accesses are guarded per element
+// (one 16-byte / 4-byte load where W % 4 == 0 and the base is aligned).  The contraction stops at the last 16-chunk that holds data
+// (ceil(W / 16), ceil(H / 16)), not at the tile grid.
+// No floating-point atomics anywhere: a band's sum over a wave is a fixed shuffle tree, over the workgroup a fixed four-term sum,
+// over the tiles a fixed loop -- two runs on the same input give the same bits.
+#include "fw_common.h"
+
+namespace {
+
+#define SPEC_MFMA(acc, a, b) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc, 0, 0, 0)
+
+FW_DEV f32x4 spec_frag(const float* P, int pitch, int row0, int c) {      // fragment of a padded k-contiguous f32 [.][pitch] matrix
+    const int l = lane_id();
+    return *reinterpret_cast<const f32x4*>(P + (size_t)(row0 + (l & 15)) * pitch + c * 16 + ((l >> 4) << 2));
+}
+
+// KIND 0: f32 map; 1: u8 map; 2: clamp(restored f32, 0, 1) - clean u8 / 255 (the difference eval_blend_body squares, fw_data.hip)
+template <int KIND> FW_DEV float spec_value(const float* f, const unsigned char* q, size_t i) {
+    if (KIND == 0) return f[i];
+    if (KIND == 1) return (float)q[i];
+    return fminf(fmaxf(f[i], 0.f), 1.f) - __fdiv_rn((float)q[i], 255.0f);
+}
+// a lane's 4 consecutive x of row y, zero outside the map; vec: W % 4 == 0 and aligned bases, so x < W covers x + 3
+template <int KIND> FW_DEV f32x4 spec_src_frag(const float* f, const unsigned char* q, int H, int W, int y, int x, bool vec) {
+    f32x4 r = {0.f, 0.f, 0.f, 0.f};
+    if (y >= H || x >= W) return r;
+    const size_t i = (size_t)y * W + x;
+    if (vec) {
+        f32x4 a = {0.f, 0.f, 0.f, 0.f};
+        unsigned char b[4] = {0, 0, 0, 0};
+        if (KIND != 1) a = *reinterpret_cast<const f32x4*>(f + i);
+        if (KIND != 0) *reinterpret_cast<unsigned*>(b) = *reinterpret_cast<const unsigned*>(q + i);
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            r[k] = KIND == 0 ? a[k] : KIND == 1 ? (float)b[k] : fminf(fmaxf(a[k], 0.f), 1.f) - __fdiv_rn((float)b[k], 255.0f);
+        return r;
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        if (x + k < W) r[k] = spec_value<KIND>(f, q, i + k);
+    return r;
+}
+
+// grid (Wh / 64 tiles of v, Hp / 64 tiles of y, nimg); 256 threads.  Tr, Ti: [nimg][Wh][Hp].
+template <int KIND>
+__global__ __launch_bounds__(256) void spec_row_kernel(const float* __restrict__ srcf, const unsigned char* __restrict__ srcq,
+                                                       const float* __restrict__ PW, float* __restrict__ Tr, float* __restrict__ Ti, int H,
+                                                       int W, int Hp, int Wp, int Wh, int vec) {
+    const int w = threadIdx.x >> 6, l = lane_id();
+    const size_t img = blockIdx.z;
+    const int d0 = blockIdx.y * 64 + (w >> 1) * 32, p0 = blockIdx.x * 64 + (w & 1) * 32;
+    const float* f = KIND == 1 ? nullptr : srcf + img * H * W;
+    const unsigned char* q = KIND == 0 ? nullptr : srcq + img * H * W;
+    const float* Pc = PW;
+    const float* Pn = PW + 2 * (size_t)Wp * Wp;                              // -sin: the real input into the imaginary output
+    f32x4 accr[2][2], acci[2][2];
+    zero_acc(accr); zero_acc(acci);
+    const int KC = (W + 15) / 16;
+    for (int c = 0; c < KC; ++c) {
+        f32x4 a[2], pc[2], pn[2];
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            a[t] = spec_src_frag<KIND>(f, q, H, W, d0 + 16 * t + (l & 15), c * 16 + ((l >> 4) << 2), vec != 0);
+            pc[t] = spec_frag(Pc, Wp, p0 + 16 * t, c);
+            pn[t] = spec_frag(Pn, Wp, p0 + 16 * t, c);
+        }
+#pragma unroll
+        for (int s = 0; s < 4; ++s)
+#pragma unroll
+            for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+                for (int nt = 0; nt < 2; ++nt) {
+                    SPEC_MFMA(accr[mt][nt], a[mt][s], pc[nt][s]);
+                    SPEC_MFMA(acci[mt][nt], a[mt][s], pn[nt][s]);
+                }
+    }
+    // acc element r of lane l is out[m = data row y 4 (l >> 4) + r][n = panel row v l & 15]: the transpose takes one 16-byte store
+    float* o_r = Tr + img * Wh * Hp;
+    float* o_i = Ti + img * Wh * Hp;
+#pragma unroll
+    for (int nt = 0; nt < 2; ++nt)
+#pragma unroll
+        for (int mt = 0; mt < 2; ++mt) {
+            const size_t o = (size_t)(p0 + 16 * nt + (l & 15)) * Hp + d0 + 16 * mt + ((l >> 4) << 2);
+            *reinterpret_cast<f32x4*>(o_r + o) = accr[mt][nt];
+            *reinterpret_cast<f32x4*>(o_i + o) = acci[mt][nt];
+        }
+}
+
+// grid (Hp / 64 tiles of u, Wh / 64 tiles of v, nimg); 256 threads.  part: [nimg][tiles][nbands], tile = blockIdx.y * gridDim.x + blockIdx.x.
+__global__ __launch_bounds__(256) void spec_col_kernel(const float* __restrict__ Tr, const float* __restrict__ Ti, const float* __restrict__ PH,
+                                                       const unsigned char* __restrict__ ring, float* __restrict__ part, int H, int W,
+                                                       int Hp, int Wh, int nbands, int power) {
+    __shared__ float red[4][32];
+    const int w = threadIdx.x >> 6, l = lane_id();
+    const size_t img = blockIdx.z;
+    const int d0 = blockIdx.y * 64 + (w >> 1) * 32, p0 = blockIdx.x * 64 + (w & 1) * 32;       // d: v (rows of T^t), p: u
+    const float* xr = Tr + img * Wh * Hp;
+    const float* xi = Ti + img * Wh * Hp;
+    const float* Pc = PH;
+    const float* Ps = PH + (size_t)Hp * Hp;
+    const float* Pn = PH + 2 * (size_t)Hp * Hp;
+    f32x4 accr[2][2], acci[2][2];
+    zero_acc(accr); zero_acc(acci);
+    const int KC = (H + 15) / 16;
+    for (int c = 0; c < KC; ++c) {
+        f32x4 ar[2], ai[2], pc[2], ps[2], pn[2];
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            ar[t] = spec_frag(xr, Hp, d0 + 16 * t, c);
+            ai[t] = spec_frag(xi, Hp, d0 + 16 * t, c);
+            pc[t] = spec_frag(Pc, Hp, p0 + 16 * t, c);
+            ps[t] = spec_frag(Ps, Hp, p0 + 16 * t, c);
+            pn[t] = spec_frag(Pn, Hp, p0 + 16 * t, c);
+        }
+#pragma unroll
+        for (int s = 0; s < 4; ++s)                                         // (a + i b)(C - i S) = a C + b S + i (b C - a S)
+#pragma unroll
+            for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+                for (int nt = 0; nt < 2; ++nt) {
+                    SPEC_MFMA(accr[mt][nt], ar[mt][s], pc[nt][s]);
+                    SPEC_MFMA(acci[mt][nt], ar[mt][s], pn[nt][s]);
+                    SPEC_MFMA(accr[mt][nt], ai[mt][s], ps[nt][s]);
+                    SPEC_MFMA(acci[mt][nt], ai[mt][s], pc[nt][s]);
+                }
+    }
+    // acc element r of lane l: v = d0 + 16 mt + 4 (l >> 4) + r, u = p0 + 16 nt + (l & 15)
+    float val[16];
+    unsigned char bnd[16], mir[16];                                        // the band of the bin, and of its mirror bin
+    unsigned mine = 0u;                                                    // bands this lane holds a bin of
+#pragma unroll
+    for (int nt = 0; nt < 2; ++nt)
+#pragma unroll
+        for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int k = (nt * 2 + mt) * 4 + r;
+                const int u = p0 + 16 * nt + (l & 15), v = d0 + 16 * mt + ((l >> 4) << 2) + r;
+                const float a = accr[mt][nt][r], b = acci[mt][nt][r];
+                const float e = a * a + b * b;
+                val[k] = power ? e : sqrtf(e);
+                unsigned char g = 255, gm = 255;
+                if (u < H && 2 * v <= W) {
+                    g = ring[(size_t)u * W + v];
+                    if (v != 0 && 2 * v != W) gm = ring[(size_t)(u ? H - u : 0) * W + (W - v)];
+                }
+                if (g >= nbands) g = 255;
+                if (gm >= nbands) gm = 255;
+                bnd[k] = g; mir[k] = gm;
+                if (g != 255) mine |= 1u << g;
+                if (gm != 255) mine |= 1u << gm;
+            }
+    for (int b = 0; b < nbands; ++b) {                                      // uniform over the wave
+        float s = 0.f;
+        if (__any((mine >> b) & 1u)) {
+#pragma unroll
+            for (int k = 0; k < 16; ++k) s += (bnd[k] == b ? val[k] : 0.f) + (mir[k] == b ? val[k] : 0.f);
+            s = wave_sum(s);
+        }
+        if (l == 0) red[w][b] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x < nbands) {
+        const int b = threadIdx.x;
+        const size_t tile = (size_t)blockIdx.y * gridDim.x + blockIdx.x, tiles = (size_t)gridDim.x * gridDim.y;
+        part[(img * tiles + tile) * nbands + b] = ((red[0][b] + red[1][b]) + red[2][b]) + red[3][b];
+    }
+}
+
+// grid nimg; 64 threads, one per band
+__global__ __launch_bounds__(64) void spec_fold_kernel(const float* __restrict__ part, double* __restrict__ out, int tiles, int nbands) {
+    const int b = threadIdx.x;
+    if (b >= nbands) return;
+    const float* p = part + (size_t)blockIdx.x * tiles * nbands + b;
+    double s = 0.0;
+    for (int t = 0; t < tiles; ++t) s += (double)p[(size_t)t * nbands];
+    out[(size_t)blockIdx.x * nbands + b] = s;
+}
+
+}  // namespace
+
+#define ST ((hipStream_t)stream)
+
+extern "C" int fw_band_stats(int src_kind, const void* src, const unsigned char* clean, const unsigned char* ring, const float* panels_h,
+                             const float* panels_w, float* work, double* out, int nimg, int H, int W, int nbands, int power, void* stream) {
+    FW_CHECK_ARG(src && ring && panels_h && panels_w && work && out && src_kind >= 0 && src_kind <= 2 && (src_kind != 2 || clean) &&
+                 nimg > 0 && nimg <= 65535 && H >= 8 && H <= 1024 && W >= 8 && W <= 1024 && nbands >= 1 && nbands <= 32 &&
+                 (power == 0 || power == 1));
+    FW_CHECK_ARG((((uintptr_t)panels_h | (uintptr_t)panels_w | (uintptr_t)work) & 15) == 0 && ((uintptr_t)out & 7) == 0 &&
+                 (src_kind == 1 || ((uintptr_t)src & 3) == 0));
+    const int Hp = (H + 63) / 64 * 64, Wp = (W + 63) / 64 * 64, Wh = (W / 2 + 1 + 63) / 64 * 64, tiles = (Hp / 64) * (Wh / 64);
+    const size_t per = (size_t)nimg * Hp * Wh;
+    float* Tr = work; float* Ti = work + per; float* part = work + 2 * per;
+    const float* f = src_kind == 1 ? nullptr : (const float*)src;
+    const unsigned char* q = src_kind == 1 ? (const unsigned char*)src : clean;
+    const int vec = W % 4 == 0 && (!f || ((uintptr_t)f & 15) == 0) && (!q || ((uintptr_t)q & 3) == 0);
+    const dim3 grow(Wh / 64, Hp / 64, nimg), gcol(Hp / 64, Wh / 64, nimg);
+    if (src_kind == 0) hipLaunchKernelGGL(spec_row_kernel<0>, grow, dim3(256), 0, ST, f, q, panels_w, Tr, Ti, H, W, Hp, Wp, Wh, vec);
+    else if (src_kind == 1) hipLaunchKernelGGL(spec_row_kernel<1>, grow, dim3(256), 0, ST, f, q, panels_w, Tr, Ti, H, W, Hp, Wp, Wh, vec);
+    else hipLaunchKernelGGL(spec_row_kernel<2>, grow, dim3(256), 0, ST, f, q, panels_w, Tr, Ti, H, W, Hp, Wp, Wh, vec);
+    hipLaunchKernelGGL(spec_col_kernel, gcol, dim3(256), 0, ST, Tr, Ti, panels_h, ring, part, H, W, Hp, Wh, nbands, power);
+    hipLaunchKernelGGL(spec_fold_kernel, dim3(nimg), dim3(64), 0, ST, part, out, tiles, nbands);
+    FW_LAUNCH_RET();
+}

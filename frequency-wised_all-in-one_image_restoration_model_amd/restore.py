@@ -6,6 +6,7 @@ reused: a `test.py` on sys.path shadows the standard library's `test` package).
                       [--ckpt FILE] [--save_imgs True]
     python restore.py --ckpt FILE --input PATH --output DIR          (PATH: an image or a directory of images; no ground truth, no metrics)
                       [--keep_size] [--tile_overlap N] [--self_ensemble]
+    either of them with [--band_report N]
 
 `--tile_overlap N` lets neighbouring tiles share N pixels (at most half a tile) and blends them with a linear ramp, so that the tile grid
 does not show; `--self_ensemble` averages the 8 flips / rotations of every tile; both also apply to the test sets, whose PSNR / SSIM
@@ -15,6 +16,13 @@ then are those of the blended / ensembled images.  `--input` takes images of any
 Loads `<output_path>ckpt/epoch_<epochs>.pth` (train.py:126) unless `--ckpt` names a file, restores every test set of `--test_de_type`
 through fwair.evaluate.EvalEngine (tiles of `--crop_test_imgs_size`, test.py:47-71 averaging the RESTORED tiles; Gaussian noise of
 the denoising sets from seed 0, test.py:88) and writes `<output_path>epoch_<epochs>_results.log` in the line format of test.py:96-100.
+`--band_report N` (N bands; 0, the default, turns it off) says WHERE in the spectrum the restoration errs (fwair/spectrum.py).  With test
+sets it writes `<output_path>epoch_<epochs>_bands.log`: per task one line per band -- the band's radius range as a fraction of the
+spectrum's corner radius, the mean over the images of the band's share E_b / sum_b E_b of the squared error, and PSNR_b =
+10 log10(3 H W / E_b) averaged over the images as the set's PSNR is -- and a closing line with 10 log10(3 H W / sum_b E_b), which by
+Parseval is the set's PSNR.  With `--input` (no ground truth) it writes `<output>/bands.log`: the normalised ring distribution of the
+reference's get_frequency_distribution (grey image, rings of width 1 / N of half the image width) of every input and of its restoration.
+The results log and the PNGs do not depend on the flag.
 `--save_imgs True` also writes `<output_path>epoch_<E>_imgs/test_<task>/<name>.png` (test.py:20-26,77-78).  The model flags
 (`--degradation_embedding_method`, `--compute_dtype`, ...) must be those the checkpoint was trained with; the training batch size,
 `--learnable_modulator` and `--embed_dim` are read off the checkpoint itself (net.model.options_from_checkpoint).
@@ -33,6 +41,7 @@ _own.add_argument('--no_graph', action='store_true', help='eager launches instea
 _own.add_argument('--tile_overlap', type=int, default=0, help='pixels neighbouring tiles share (at most half a tile), blended with a ramp')
 _own.add_argument('--self_ensemble', action='store_true', help='average the 8 flips / rotations of every tile (8 times the work)')
 _own.add_argument('--keep_size', action='store_true', help='--input: restore the image at its own size, not cropped to multiples of 16')
+_own.add_argument('--band_report', type=int, default=0, help='number of spectral bands of the per-band report (0: no report)')
 _ARGS, _rest = _own.parse_known_args()
 sys.argv = [sys.argv[0]] + _rest                       # option.py parses sys.argv at import (reference option.py:3)
 
@@ -60,8 +69,37 @@ def save_u8(img, path):
     Image.fromarray(img.cpu().numpy().transpose(1, 2, 0)).save(path)
 
 
-def test_by_task(net, task, epochs):
-    """test.py:17-84 -> 'PSNR/SSIM: %.2f/%.4f' (means over the images of the set, AverageMeter with N = 1 per image)."""
+def band_lines(task, clean, restored, nbands):
+    """--band_report: the lines of one test set (see the module docstring)"""
+    from fwair import spectrum
+    E = spectrum.band_report(clean, restored, nbands)                                   # [I][nbands], double
+    npix = torch.tensor([float(im.numel()) for im in clean], dtype=torch.float64, device=E.device)
+    share = (E / E.sum(1, keepdim=True)).mean(0).tolist()
+    psnr_b = (10.0 * torch.log10(npix[:, None] / E)).mean(0).tolist()
+    psnr = float((10.0 * torch.log10(npix / E.sum(1))).mean())
+    head = task + ': ' + ' ' * (25 - len(task))
+    lines = []
+    for b in range(nbands):
+        lo, hi = b / nbands, (b + 1) / nbands
+        lines.append(head + 'band %d [%.4f, %.4f%s error share: %.4f PSNR: %.2f' % (b, lo, hi, ']' if b == nbands - 1 else ')', share[b], psnr_b[b]))
+    lines.append(head + 'all %d bands PSNR: %.2f' % (nbands, psnr))
+    return lines
+
+
+def distribution_lines(names, imgs, restored, nrings):
+    """--band_report with --input: get_frequency_distribution (normalised, grey, size = 1 / nrings) of every image and its restoration"""
+    from fwair import spectrum
+    lines = []
+    for name, a, b in zip(names, imgs, restored):
+        for tag, im in (('input', a), ('restored', b)):
+            d = spectrum.frequency_distribution(spectrum.rgb2gray(im.permute(1, 2, 0)), size=1.0 / nrings, norm=True)[0].tolist()
+            lines.append('%s %s: ' % (name, tag) + ' '.join('%.6f' % v for v in d))
+    return lines
+
+
+def test_by_task(net, task, epochs, bands=None):
+    """test.py:17-84 -> 'PSNR/SSIM: %.2f/%.4f' (means over the images of the set, AverageMeter with N = 1 per image).
+    bands: a list the --band_report lines of this set are appended to."""
     print('starting testing %s...' % (task))
     dev = next(net.parameters()).device
     ts = FolderTestSet(_ARGS.data_root, task)
@@ -69,7 +107,9 @@ def test_by_task(net, task, epochs):
     for im in clean:
         H, W = im.shape[1:]
         assert H >= opt.crop_test_imgs_size and W >= opt.crop_test_imgs_size, "invalid test image size (%d, %d)" % (H, W)     # test.py:43
-    out = _engine(net).run(clean, degraded, sigma=ts.sigma, seed=0, want_u8=bool(opt.save_imgs))
+    out = _engine(net).run(clean, degraded, sigma=ts.sigma, seed=0, want_u8=bool(opt.save_imgs), want_f32=bands is not None)
+    if bands is not None:
+        bands.extend(band_lines(task, clean, out[-1], _ARGS.band_report))
     if opt.save_imgs:
         output_path = opt.output_path + 'epoch_%s_imgs/' % str(epochs) + 'test_' + task + '/'
         os.makedirs(output_path, exist_ok=True)
@@ -90,6 +130,10 @@ def restore_files(net, src, dst):
     _, _, out = _engine(net, pad_small=True).run(None, imgs, want_u8=True)
     for p, img in zip(paths, out):
         save_u8(img, os.path.join(dst, os.path.basename(p).split('.')[0] + '.png'))
+    if _ARGS.band_report:
+        with open(os.path.join(dst, 'bands.log'), 'w') as f:
+            for line in distribution_lines([os.path.basename(p) for p in paths], imgs, out, _ARGS.band_report):
+                f.write(line + '\n')
     return len(paths)
 
 
@@ -108,10 +152,15 @@ def main():
         print('restored %d images into %s' % (n, _ARGS.output))
         return
     os.makedirs(opt.output_path, exist_ok=True)
+    bands = [] if _ARGS.band_report else None
     with open(os.path.join(opt.output_path, 'epoch_%s_results.log' % str(opt.epochs)), 'w') as result_log_file:
         for task in opt.test_de_type:
-            result = test_by_task(net, task=task, epochs=opt.epochs)
+            result = test_by_task(net, task=task, epochs=opt.epochs, bands=bands)
             result_log_file.write(task + ': ' + ' ' * (25 - len(task)) + result + '\n')
+    if bands is not None:
+        with open(os.path.join(opt.output_path, 'epoch_%s_bands.log' % str(opt.epochs)), 'w') as f:
+            for line in bands:
+                f.write(line + '\n')
 
 
 if __name__ == '__main__':

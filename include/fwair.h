@@ -213,6 +213,26 @@ int fw_dft2t_bands(const float* fr, const float* fi, const float* mask_unshifted
                    int nimg, int N, int nbands, int mode, void* stream);
 int fw_dft2t_decompose(const float* img, const float* mask, const float* panels, float* work, float* out, int nimg, int N,
                        int nbands, int dc_bits, void* stream);
+/* Band statistics of the spectrum of maps of ANY size (csrc/fw_spec.hip; utils/visualization_utils.py:158-184 and restore.py's
+ * --band_report): out[n][b] = sum over the bins (u, v) with ring[u][v] == b of |F_n[u][v]| (power 0) or |F_n[u][v]|^2 (power 1),
+ * F_n = the un-normalised DFT2 of map n.  8 <= H <= 1024 and 8 <= W <= 1024, independent, any value (odd, W % 4 != 0);
+ * 1 <= nbands <= 32; nimg <= 65535; anything else is the argument error and nothing is launched.  Rows have pitch W exactly.
+ *   src_kind 0  src = f32 [nimg][H][W]                                   (clean unused, may be NULL)
+ *            1  src = u8  [nimg][H][W], the value 0..255 as a float      (clean unused, may be NULL)
+ *            2  src = restored f32 [nimg][H][W], clean = u8 [nimg][H][W]: the map is clamp(restored, 0, 1) - clean / 255, the
+ *               difference fw_eval_blend squares for the PSNR; it is formed in the first pass's loader, never written
+ *   ring      u8 [H][W], UN-shifted coordinates (bin (0, 0) is DC), shared by all maps: the band of every bin; 255, or any value
+ *             >= nbands, = the bin is in no band
+ *   panels_h  f32 [3][Hp][Hp], panels_w f32 [3][Wp][Wp], Hp = 64 ceil(H / 64), Wp = 64 ceil(W / 64): cos, sin, -sin of
+ *             2 pi i j / H (resp. W) at [i][j] for i, j < H (resp. W), ZERO elsewhere; 16-byte aligned
+ *   work      f32, nimg * (2 * Hp * Wh + (Hp / 64) * (Wh / 64) * nbands) floats with Wh = 64 ceil((W / 2 + 1) / 64) (integer W / 2: the
+ *             maps are real, so only the columns v <= W / 2 of the spectrum are computed and each stands for its mirror bin too);
+ *             16-byte aligned; need not be initialised: the launch reads only what it wrote itself
+ *   out       double [nimg][nbands], every element written.  Per-tile partial sums are f32, their fold is in double and in a fixed
+ *             order; no atomics: the same input gives the same bits.
+ * No global state; every launch goes to `stream`. */
+int fw_band_stats(int src_kind, const void* src, const unsigned char* clean, const unsigned char* ring, const float* panels_h,
+                  const float* panels_w, float* work, double* out, int nimg, int H, int W, int nbands, int power, void* stream);
 
 /* ---- encoder contrastive head: BatchNorm2d + LeakyReLU(0.1) + GAP (encoder_Uformer.py:945-951,978-984) -- */
 int fw_bn_lrelu_gap_fwd(int dtype, const void* fea, const float* gamma, const float* beta, float* rmean, float* rvar,
