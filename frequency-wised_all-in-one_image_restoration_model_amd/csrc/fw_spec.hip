@@ -20,6 +20,7 @@
 // (ceil(W / 16), ceil(H / 16)), not at the tile grid.
 // No floating-point atomics anywhere: a band's sum over a wave is a fixed shuffle tree, over the workgroup a fixed four-term sum,
 // over the tiles a fixed loop -- two runs on the same input give the same bits.
+// fw_band_split, further down, goes on from the same row pass to the bands themselves: band images, masked spectra, magnitudes.
 #include "fw_common.h"
 
 namespace {
@@ -195,6 +196,230 @@ __global__ __launch_bounds__(64) void spec_fold_kernel(const float* __restrict__
     out[(size_t)blockIdx.x * nbands + b] = s;
 }
 
+// ---- fw_band_split: the bands themselves.  The row pass above, then
+//     forward column pass   F^t[v][u] = sum_y T^t[v][y] W_H[y][u]       the half spectrum, written ONCE per map ([Wh][Hp], u contiguous)
+//     inverse column pass   G_b[y][v] = sum_u w_b[u][v] F[u][v] e^{+2 pi i u y / H}                 per band, [Hp][Wh], v contiguous
+//     inverse row pass      out_b[y][x] = 1 / (H W) sum_{v <= W / 2} Re(G_b[y][v] e^{+2 pi i v x / W})
+// w_b[u][v] = c_v / 2 ([ring[u][v] == b] + [ring[(H - u) % H][(W - v) % W] == b]) for u < H, v <= W / 2, and 0 elsewhere; c_v = 1 for v = 0
+// and 2 v = W, 2 otherwise.  Only the real part of the inverse is kept, so the Hermitian part of M_b F -- which is ((M_b[k] + M_b[-k]) / 2)
+// F[k] -- gives it exactly for ANY ring; of a Hermitian spectrum the columns v and W - v add up to twice the real part of one of
+// them.  w_b is 0, 1/2, 1 or 2: the product w_b F is exact.  The weight is applied to the F fragment as it is loaded; NB bands share a
+// workgroup's F and panel fragments.  Modes 1 and 2 need no inverse: spec_bins_kernel reads F^t (the mirror bin conjugated).
+// Padding: F^t is zero for u >= H (zero panel rows) and w_b is zero for v > W / 2, so G_b is zero there and for y >= H; every pass writes
+// the whole padded array the next one reads.
+
+// grid (Hp / 64 tiles of u, Wh / 64 tiles of v, nimg); 256 threads.  Fr, Fi: [nimg][Wh][Hp].
+__global__ __launch_bounds__(256) void spec_colf_kernel(const float* __restrict__ Tr, const float* __restrict__ Ti, const float* __restrict__ PH,
+                                                        float* __restrict__ Fr, float* __restrict__ Fi, int H, int Hp, int Wh) {
+    const int w = threadIdx.x >> 6, l = lane_id();
+    const size_t img = blockIdx.z;
+    const int d0 = blockIdx.y * 64 + (w >> 1) * 32, p0 = blockIdx.x * 64 + (w & 1) * 32;       // d: v (rows of T^t), p: u
+    const float* xr = Tr + img * Wh * Hp;
+    const float* xi = Ti + img * Wh * Hp;
+    const float* Pc = PH;
+    const float* Ps = PH + (size_t)Hp * Hp;
+    const float* Pn = PH + 2 * (size_t)Hp * Hp;
+    f32x4 accr[2][2], acci[2][2];
+    zero_acc(accr); zero_acc(acci);
+    const int KC = (H + 15) / 16;
+    for (int c = 0; c < KC; ++c) {
+        f32x4 ar[2], ai[2], pc[2], ps[2], pn[2];
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            ar[t] = spec_frag(xr, Hp, d0 + 16 * t, c);
+            ai[t] = spec_frag(xi, Hp, d0 + 16 * t, c);
+            pc[t] = spec_frag(Pc, Hp, p0 + 16 * t, c);
+            ps[t] = spec_frag(Ps, Hp, p0 + 16 * t, c);
+            pn[t] = spec_frag(Pn, Hp, p0 + 16 * t, c);
+        }
+#pragma unroll
+        for (int s = 0; s < 4; ++s)                                         // the panel is the first operand: the accumulator's 4 rows are u
+#pragma unroll
+            for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+                for (int nt = 0; nt < 2; ++nt) {
+                    SPEC_MFMA(accr[mt][nt], pc[mt][s], ar[nt][s]);
+                    SPEC_MFMA(acci[mt][nt], pn[mt][s], ar[nt][s]);
+                    SPEC_MFMA(accr[mt][nt], ps[mt][s], ai[nt][s]);
+                    SPEC_MFMA(acci[mt][nt], pc[mt][s], ai[nt][s]);
+                }
+    }
+    // acc element r of lane l: u = p0 + 16 mt + 4 (l >> 4) + r, v = d0 + 16 nt + (l & 15)
+    float* o_r = Fr + img * Wh * Hp;
+    float* o_i = Fi + img * Wh * Hp;
+#pragma unroll
+    for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+        for (int nt = 0; nt < 2; ++nt) {
+            const size_t o = (size_t)(d0 + 16 * nt + (l & 15)) * Hp + p0 + 16 * mt + ((l >> 4) << 2);
+            *reinterpret_cast<f32x4*>(o_r + o) = accr[mt][nt];
+            *reinterpret_cast<f32x4*>(o_i + o) = acci[mt][nt];
+        }
+}
+
+// grid (Hp / 64 tiles of y, Wh / 64 tiles of v, nimg); 256 threads.  The bands b0 .. b0 + NB - 1.  Gr, Gi: [NB][nimg][Hp][Wh].
+template <int NB>
+__global__ __launch_bounds__(256) void spec_coli_kernel(const float* __restrict__ Fr, const float* __restrict__ Fi, const float* __restrict__ PH,
+                                                        const unsigned char* __restrict__ ring, float* __restrict__ Gr, float* __restrict__ Gi,
+                                                        int H, int W, int Hp, int Wh, int b0) {
+    const int w = threadIdx.x >> 6, l = lane_id();
+    const size_t img = blockIdx.z, nimg = gridDim.z;
+    const int d0 = blockIdx.y * 64 + (w >> 1) * 32, p0 = blockIdx.x * 64 + (w & 1) * 32;       // d: v (rows of F^t), p: y
+    const float* xr = Fr + img * Wh * Hp;
+    const float* xi = Fi + img * Wh * Hp;
+    const float* Pc = PH;
+    const float* Ps = PH + (size_t)Hp * Hp;
+    const float* Pn = PH + 2 * (size_t)Hp * Hp;
+    f32x4 accr[NB][2][2], acci[NB][2][2];
+#pragma unroll
+    for (int j = 0; j < NB; ++j) { zero_acc(accr[j]); zero_acc(acci[j]); }
+    const int KC = (H + 15) / 16;
+    for (int c = 0; c < KC; ++c) {
+        f32x4 ar[2], ai[2], pc[2], ps[2], pn[2];
+        int g[2][4], gm[2][4];                                              // band of the bin and of its mirror bin, -1: weight 0
+        float cv[2];
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            ar[t] = spec_frag(xr, Hp, d0 + 16 * t, c);
+            ai[t] = spec_frag(xi, Hp, d0 + 16 * t, c);
+            pc[t] = spec_frag(Pc, Hp, p0 + 16 * t, c);
+            ps[t] = spec_frag(Ps, Hp, p0 + 16 * t, c);
+            pn[t] = spec_frag(Pn, Hp, p0 + 16 * t, c);
+            const int v = d0 + 16 * t + (l & 15);
+            cv[t] = (v == 0 || 2 * v == W) ? 0.5f : 1.0f;
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
+                const int u = c * 16 + ((l >> 4) << 2) + s;
+                g[t][s] = gm[t][s] = -1;
+                if (u < H && 2 * v <= W) {
+                    g[t][s] = ring[(size_t)u * W + v];
+                    gm[t][s] = ring[(size_t)(u ? H - u : 0) * W + (v ? W - v : 0)];
+                }
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < NB; ++j) {
+            f32x4 br[2], bi[2];
+#pragma unroll
+            for (int t = 0; t < 2; ++t)
+#pragma unroll
+                for (int s = 0; s < 4; ++s) {
+                    const float wt = cv[t] * ((g[t][s] == b0 + j ? 1.f : 0.f) + (gm[t][s] == b0 + j ? 1.f : 0.f));
+                    br[t][s] = wt * ar[t][s];
+                    bi[t][s] = wt * ai[t][s];
+                }
+#pragma unroll
+            for (int s = 0; s < 4; ++s)                                     // (a + i b)(C + i S) = a C - b S + i (a S + b C)
+#pragma unroll
+                for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+                    for (int nt = 0; nt < 2; ++nt) {
+                        SPEC_MFMA(accr[j][mt][nt], br[mt][s], pc[nt][s]);
+                        SPEC_MFMA(acci[j][mt][nt], br[mt][s], ps[nt][s]);
+                        SPEC_MFMA(accr[j][mt][nt], bi[mt][s], pn[nt][s]);
+                        SPEC_MFMA(acci[j][mt][nt], bi[mt][s], pc[nt][s]);
+                    }
+        }
+    }
+    // acc element r of lane l: v = d0 + 16 mt + 4 (l >> 4) + r, y = p0 + 16 nt + (l & 15)
+#pragma unroll
+    for (int j = 0; j < NB; ++j) {
+        float* o_r = Gr + ((size_t)j * nimg + img) * Hp * Wh;
+        float* o_i = Gi + ((size_t)j * nimg + img) * Hp * Wh;
+#pragma unroll
+        for (int nt = 0; nt < 2; ++nt)
+#pragma unroll
+            for (int mt = 0; mt < 2; ++mt) {
+                const size_t o = (size_t)(p0 + 16 * nt + (l & 15)) * Wh + d0 + 16 * mt + ((l >> 4) << 2);
+                *reinterpret_cast<f32x4*>(o_r + o) = accr[j][mt][nt];
+                *reinterpret_cast<f32x4*>(o_i + o) = acci[j][mt][nt];
+            }
+    }
+}
+
+// grid (Wp / 64 tiles of x, Hp / 64 tiles of y times the bands of the group, nimg); 256 threads.  out: [.][nimg][H][W] from band b0 on.
+__global__ __launch_bounds__(256) void spec_rowi_kernel(const float* __restrict__ Gr, const float* __restrict__ Gi, const float* __restrict__ PW,
+                                                        float* __restrict__ out, int H, int W, int Hp, int Wp, int Wh, int b0, float scale,
+                                                        int vec) {
+    const int w = threadIdx.x >> 6, l = lane_id();
+    const size_t img = blockIdx.z, nimg = gridDim.z;
+    const int ty = blockIdx.y % (Hp / 64), j = blockIdx.y / (Hp / 64);
+    const int d0 = ty * 64 + (w >> 1) * 32, p0 = blockIdx.x * 64 + (w & 1) * 32;               // d: y (rows of G), p: x
+    const float* xr = Gr + ((size_t)j * nimg + img) * Hp * Wh;
+    const float* xi = Gi + ((size_t)j * nimg + img) * Hp * Wh;
+    const float* Pc = PW;
+    const float* Pn = PW + 2 * (size_t)Wp * Wp;
+    f32x4 acc[2][2];
+    zero_acc(acc);
+    const int KC = (W / 2 + 1 + 15) / 16;
+    for (int c = 0; c < KC; ++c) {
+        f32x4 ar[2], ai[2], pc[2], pn[2];
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            ar[t] = spec_frag(xr, Wh, d0 + 16 * t, c);
+            ai[t] = spec_frag(xi, Wh, d0 + 16 * t, c);
+            pc[t] = spec_frag(Pc, Wp, p0 + 16 * t, c);
+            pn[t] = spec_frag(Pn, Wp, p0 + 16 * t, c);
+        }
+#pragma unroll
+        for (int s = 0; s < 4; ++s)                                         // Re((a + i b)(C + i S)) = a C - b S; the panel first: 4 rows are x
+#pragma unroll
+            for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+                for (int nt = 0; nt < 2; ++nt) {
+                    SPEC_MFMA(acc[mt][nt], pc[mt][s], ar[nt][s]);
+                    SPEC_MFMA(acc[mt][nt], pn[mt][s], ai[nt][s]);
+                }
+    }
+    // acc element r of lane l: x = p0 + 16 mt + 4 (l >> 4) + r, y = d0 + 16 nt + (l & 15); vec: W % 4 == 0 and an aligned base
+    float* o = out + ((size_t)(b0 + j) * nimg + img) * H * W;
+#pragma unroll
+    for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+        for (int nt = 0; nt < 2; ++nt) {
+            const int y = d0 + 16 * nt + (l & 15), x = p0 + 16 * mt + ((l >> 4) << 2);
+            if (y >= H || x >= W) continue;
+            f32x4 r = acc[mt][nt];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) r[k] *= scale;
+            float* q = o + (size_t)y * W + x;
+            if (vec) {
+                *reinterpret_cast<f32x4*>(q) = r;
+            } else {
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    if (x + k < W) q[k] = r[k];
+            }
+        }
+}
+
+// Modes 1 and 2: one thread per element of the output plane.  grid (ceil(H W / 256), nimg); 256 threads.
+// MODE 1: (re, im) of M_b F at [u][v]; MODE 2: |M_b F| at [(u + H / 2) % H][(v + W / 2) % W].
+template <int MODE>
+__global__ __launch_bounds__(256) void spec_bins_kernel(const float* __restrict__ Fr, const float* __restrict__ Fi,
+                                                        const unsigned char* __restrict__ ring, float* __restrict__ out, int H, int W, int Hp,
+                                                        int Wh, int nbands) {
+    const size_t img = blockIdx.y, nimg = gridDim.y;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= H * W) return;
+    int u = i / W, v = i - u * W;
+    if (MODE == 2) {                                                        // the output element (u, v) shows the bin (u - H / 2, v - W / 2)
+        u -= H / 2; if (u < 0) u += H;
+        v -= W / 2; if (v < 0) v += W;
+    }
+    const int g = ring[(size_t)u * W + v];
+    const bool half = 2 * v <= W;                                           // else the mirror bin, conjugated
+    const size_t f = img * Wh * Hp + (size_t)(half ? v : W - v) * Hp + (half ? u : (u ? H - u : 0));
+    const float re = Fr[f], im = half ? Fi[f] : -Fi[f];
+    const float mag = sqrtf(re * re + im * im);
+    for (int b = 0; b < nbands; ++b) {
+        const size_t o = ((size_t)b * nimg + img) * H * W + i;
+        const bool in = g == b;
+        if (MODE == 1) *reinterpret_cast<float2*>(out + 2 * o) = make_float2(in ? re : 0.f, in ? im : 0.f);
+        else out[o] = in ? mag : 0.f;
+    }
+}
+
 }  // namespace
 
 #define ST ((hipStream_t)stream)
@@ -218,5 +443,45 @@ extern "C" int fw_band_stats(int src_kind, const void* src, const unsigned char*
     else hipLaunchKernelGGL(spec_row_kernel<2>, grow, dim3(256), 0, ST, f, q, panels_w, Tr, Ti, H, W, Hp, Wp, Wh, vec);
     hipLaunchKernelGGL(spec_col_kernel, gcol, dim3(256), 0, ST, Tr, Ti, panels_h, ring, part, H, W, Hp, Wh, nbands, power);
     hipLaunchKernelGGL(spec_fold_kernel, dim3(nimg), dim3(64), 0, ST, part, out, tiles, nbands);
+    FW_LAUNCH_RET();
+}
+
+extern "C" int fw_band_split(int src_kind, const void* src, const unsigned char* clean, const unsigned char* ring, const float* panels_h,
+                             const float* panels_w, float* work, float* out, int nimg, int H, int W, int nbands, int mode, void* stream) {
+    FW_CHECK_ARG(src && ring && panels_h && panels_w && work && out && src_kind >= 0 && src_kind <= 2 && (src_kind != 2 || clean) &&
+                 nimg > 0 && nimg <= 65535 && H >= 8 && H <= 1024 && W >= 8 && W <= 1024 && nbands >= 1 && nbands <= 32 && mode >= 0 &&
+                 mode <= 2);
+    FW_CHECK_ARG((((uintptr_t)panels_h | (uintptr_t)panels_w | (uintptr_t)work) & 15) == 0 && ((uintptr_t)out & (mode == 1 ? 7 : 3)) == 0 &&
+                 (src_kind == 1 || ((uintptr_t)src & 3) == 0));
+    const int Hp = (H + 63) / 64 * 64, Wp = (W + 63) / 64 * 64, Wh = (W / 2 + 1 + 63) / 64 * 64;
+    const size_t per = (size_t)nimg * Hp * Wh;
+    float* Tr = work; float* Ti = work + per; float* Fr = work + 2 * per; float* Fi = work + 3 * per;
+    const float* f = src_kind == 1 ? nullptr : (const float*)src;
+    const unsigned char* q = src_kind == 1 ? (const unsigned char*)src : clean;
+    const int vec = W % 4 == 0 && (!f || ((uintptr_t)f & 15) == 0) && (!q || ((uintptr_t)q & 3) == 0);
+    const dim3 grow(Wh / 64, Hp / 64, nimg), gcol(Hp / 64, Wh / 64, nimg);
+    if (src_kind == 0) hipLaunchKernelGGL(spec_row_kernel<0>, grow, dim3(256), 0, ST, f, q, panels_w, Tr, Ti, H, W, Hp, Wp, Wh, vec);
+    else if (src_kind == 1) hipLaunchKernelGGL(spec_row_kernel<1>, grow, dim3(256), 0, ST, f, q, panels_w, Tr, Ti, H, W, Hp, Wp, Wh, vec);
+    else hipLaunchKernelGGL(spec_row_kernel<2>, grow, dim3(256), 0, ST, f, q, panels_w, Tr, Ti, H, W, Hp, Wp, Wh, vec);
+    hipLaunchKernelGGL(spec_colf_kernel, gcol, dim3(256), 0, ST, Tr, Ti, panels_h, Fr, Fi, H, Hp, Wh);
+    if (mode != 0) {
+        const dim3 gb((H * W + 255) / 256, nimg);
+        if (mode == 1) hipLaunchKernelGGL(spec_bins_kernel<1>, gb, dim3(256), 0, ST, Fr, Fi, ring, out, H, W, Hp, Wh, nbands);
+        else hipLaunchKernelGGL(spec_bins_kernel<2>, gb, dim3(256), 0, ST, Fr, Fi, ring, out, H, W, Hp, Wh, nbands);
+        FW_LAUNCH_RET();
+    }
+    // up to 4 bands at a time share the F and panel fragments of a workgroup; the group's G is reused by the next group (stream order)
+    const int NBG = nbands < 4 ? nbands : 4;
+    float* Gr = work + 4 * per; float* Gi = Gr + (size_t)NBG * nimg * Hp * Wh;
+    const int ovec = W % 4 == 0 && ((uintptr_t)out & 15) == 0;
+    const float scale = 1.0f / ((float)H * (float)W);
+    for (int b0 = 0; b0 < nbands; b0 += 4) {
+        const int nb = nbands - b0 < 4 ? nbands - b0 : 4;
+#define SPEC_COLI(NB) hipLaunchKernelGGL(spec_coli_kernel<NB>, gcol, dim3(256), 0, ST, Fr, Fi, panels_h, ring, Gr, Gi, H, W, Hp, Wh, b0)
+        if (nb == 1) SPEC_COLI(1); else if (nb == 2) SPEC_COLI(2); else if (nb == 3) SPEC_COLI(3); else SPEC_COLI(4);
+#undef SPEC_COLI
+        hipLaunchKernelGGL(spec_rowi_kernel, dim3(Wp / 64, (Hp / 64) * nb, nimg), dim3(256), 0, ST, Gr, Gi, panels_w, out, H, W, Hp, Wp, Wh, b0,
+                           scale, ovec);
+    }
     FW_LAUNCH_RET();
 }

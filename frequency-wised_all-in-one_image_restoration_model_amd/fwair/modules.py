@@ -211,10 +211,15 @@ class DecLeWinTransformerBlock(nn.Module):
             raise NotImplementedError('feature maps smaller than one 8x8 window')
         self.debug_mode = bool(debug_mode)
         if self.debug_mode:                                                     # :518-519 (no parameters, no buffers: same state_dict)
-            # stage maps of a 384-pixel model (384, 192, 96, 48, 24): 96 / 48 / 24 are sides FrequencyDecompose does not take and the
-            # constructor raises its NotImplementedError; at 128 / 256 / 512 every stage side is covered
+            # stage maps of a 384-pixel model (384, 192, 96, 48, 24): 96 / 48 / 24 are sides FrequencyDecompose does not take; they go
+            # to the any-size kernels (fwair.spectrum.BandSplit, forward only -- _spectrum detaches).  Every side FrequencyDecompose
+            # takes stays on it: the payload at 128 / 256 / 512 is bit-identical
             from net.utils.frequency_decompose import FrequencyDecompose
-            self.visual_decompose = FrequencyDecompose('frequency_decompose', 1, input_resolution[0], input_resolution[1], inverse='visual')
+            try:
+                self.visual_decompose = FrequencyDecompose('frequency_decompose', 1, input_resolution[0], input_resolution[1], inverse='visual')
+            except NotImplementedError:
+                from .spectrum import BandSplit
+                self.visual_decompose = BandSplit('frequency_decompose', 1, input_resolution[0], input_resolution[1], inverse='visual')
         # :536-539, registered before norm1 as there (same state_dict key order); nn.Embedding's own N(0, 1) initialisation stays:
         # _init_weights touches Linear and LayerNorm only
         self.modulator = nn.Embedding(WIN * WIN, dim) if modulator else None

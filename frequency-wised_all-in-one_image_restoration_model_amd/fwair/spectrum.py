@@ -1,5 +1,5 @@
 """Where in the spectrum a signal, or a restoration's error, sits: radial band statistics of images of any size on the device
-(csrc/fw_spec.hip: fw_band_stats).
+(csrc/fw_spec.hip: fw_band_stats), and the bands themselves (fw_band_split).
 
   ring_index              the band of every frequency bin: the rings of the reference's get_frequency_distribution
                           (utils/visualization_utils.py:158-184, kind 'plot') or the partition of the band decomposition
@@ -7,11 +7,16 @@
   frequency_distribution  get_frequency_distribution for device tensors
   band_report             error energy per band of restored images against their ground truth; by Parseval its bands add up to the
                           squared error the evaluation engine's PSNR is computed from
+  band_split              fw_band_split: band images, masked spectra or shifted magnitudes of maps [n, H, W] for any ring table
+  band_images             the band images of an image or a batch, 8 <= H, W <= 1024 independent of each other
+  BandSplit               the reference's FrequencyDecompose(type, size, h, w, inverse) for any such (h, w), forward only;
+                          net/utils/frequency_decompose.py keeps the square sides of the model's hot path and the autograd function
 """
 import math
 
 import numpy as np
 import torch
+from torch import nn
 
 from . import lfs
 from .lib import call
@@ -21,7 +26,7 @@ _rings, _panels = {}, {}
 
 def ring_edges(kind, size, h, w):
     """-> [(lo, hi)] radius range of every band in pixels of the shifted spectrum, and the radius the fractions refer to
-    ('plot': int(w / 2); 'bands': the corner radius)."""
+    ('plot': int(w / 2); 'bands', 'bands_1': the corner radius; 'bands_1' has DC alone, (0, 0), as band 0, then (lo, hi] rings)."""
     if kind == 'plot':
         diag = int(w / 2)
         return [(diag * (sz - size), diag * sz) for sz in np.linspace(size, 1, int(1 / size))], diag
@@ -29,6 +34,10 @@ def ring_edges(kind, size, h, w):
         rmax = math.sqrt(int(w / 2) ** 2 + int(h / 2) ** 2)
         szs = [float(s) for s in torch.linspace(size, 1, math.floor(1. / size + 0.1))]
         return [(rmax * lo, rmax * hi) for lo, hi in zip([0.0] + szs[:-1], szs)], rmax
+    if kind == 'bands_1':
+        rmax = math.sqrt(int(w / 2) ** 2 + int(h / 2) ** 2)
+        szs = [float(s) for s in torch.linspace(0, 1, math.floor(1. / size + 0.1) + 1)]
+        return [(0.0, 0.0)] + [(rmax * lo, rmax * hi) for lo, hi in zip(szs[:-1], szs[1:])], rmax
     raise ValueError(kind)
 
 
@@ -36,7 +45,8 @@ def ring_index(kind, size, h, w):
     """u8 numpy [h][w] in fftshift-ed coordinates: the band of every bin, 255 = in no band.
     'plot': ring i of get_frequency_distribution, float64 arithmetic as there: diag = int(w / 2), int(1 / size) rings over
     np.linspace(size, 1, .), diag (sz - size) <= d < diag sz, the ring with sz == 1 closed.  A bin in two rings is a ValueError (the
-    reference would count it twice).  'bands': the partition of lfs.band_masks_shifted('frequency_decompose', size, h, w)."""
+    reference would count it twice).  'bands': the partition of lfs.band_masks_shifted('frequency_decompose', size, h, w);
+    'bands_1': that of lfs.band_masks_shifted('frequency_decompose_1', size, h, w), DC alone being band 0."""
     if kind == 'plot':
         center = (int(w / 2), int(h / 2))
         Y, X = np.ogrid[:h, :w]
@@ -57,8 +67,8 @@ def ring_index(kind, size, h, w):
                 raise ValueError(f'ring_index: a bin of the {h} x {w} spectrum falls into two rings of size {size}')
             ring[m] = idx
         return ring
-    if kind == 'bands':
-        masks = torch.stack(lfs.band_masks_shifted('frequency_decompose', size, h, w))
+    if kind in ('bands', 'bands_1'):
+        masks = torch.stack(lfs.band_masks_shifted('frequency_decompose' if kind == 'bands' else 'frequency_decompose_1', size, h, w))
         if masks.shape[0] >= 255 or not bool((masks.sum(0) == 1).all()):
             raise ValueError(f'ring_index: the bands of size {size} do not partition the {h} x {w} spectrum')
         return masks.to(torch.uint8).argmax(0).to(torch.uint8).numpy()
@@ -116,6 +126,91 @@ def band_stats(src, ring, nbands, power, clean=None):
     work = torch.empty(work_floats(n, h, w, nbands), dtype=torch.float32, device=src.device)
     call('fw_band_stats', kind, src, clean, ring, panels(h, src.device), panels(w, src.device), work, out, n, h, w, nbands, power)
     return out
+
+
+def split_work_floats(nimg, h, w, nbands, mode):
+    """the work buffer of fw_band_split (include/fwair.h)"""
+    return nimg * padded(h) * padded(w // 2 + 1) * (4 + (2 * min(nbands, 4) if mode == 0 else 0))
+
+
+def band_split(src, ring, nbands, mode, clean=None):
+    """fw_band_split on src [n, H, W] (f32 or u8, contiguous; with `clean` u8 [n, H, W]: the error map of restored f32 `src`); ring: u8
+    [H, W] device table in UN-shifted coordinates.  mode 0 -> band images f32 [nbands, n, H, W]; 1 -> (re, im) of the masked spectra
+    [nbands, n, H, W, 2]; 2 -> their magnitudes in fftshift-ed coordinates [nbands, n, H, W]"""
+    if src.dim() != 3:
+        raise ValueError(f'band_split: maps [n, H, W], not {tuple(src.shape)}')
+    n, h, w = src.shape
+    kind = 2 if clean is not None else (1 if src.dtype == torch.uint8 else 0)
+    if kind != 1 and src.dtype != torch.float32:
+        raise TypeError(f'band_split: {src.dtype} maps (float32 or uint8)')
+    if clean is not None and (clean.dtype != torch.uint8 or clean.shape != src.shape):
+        raise TypeError('band_split: clean must be uint8 of the shape of the restored maps')
+    if ring.dtype != torch.uint8 or tuple(ring.shape) != (h, w):
+        raise TypeError(f'band_split: the ring must be uint8 [{h}, {w}]')
+    if mode not in (0, 1, 2):
+        raise ValueError(f'band_split: mode {mode} (0 band images, 1 masked spectra, 2 magnitudes)')
+    src = src.contiguous()
+    clean = clean.contiguous() if clean is not None else None
+    out = torch.empty((nbands, n, h, w, 2) if mode == 1 else (nbands, n, h, w), dtype=torch.float32, device=src.device)
+    work = torch.empty(split_work_floats(n, h, w, nbands, mode), dtype=torch.float32, device=src.device)
+    call('fw_band_split', kind, src, clean, ring.contiguous(), panels(h, src.device), panels(w, src.device), work, out, n, h, w, nbands, mode)
+    return out
+
+
+def band_images(img, nbands, kind='bands', clean=None):
+    """The band images of img [H, W], [n, H, W] or [B, C, H, W] (f32 or u8; 8 <= H, W <= 1024, any values): Re IDFT2 of the spectrum
+    restricted to each band of ring_index(kind, 1 / nbands) -> f32 [nb, ...the leading axes of img..., H, W] with nb = nbands ('bands')
+    or nbands + 1 ('bands_1', DC first); the bands sum to the image.  With `clean` (u8, the shape of img): the bands of the error map
+    clamp(img, 0, 1) - clean / 255.  One size per call."""
+    if img.dim() not in (2, 3, 4):
+        raise ValueError(f'band_images: a map [H, W], a batch [n, H, W] or [B, C, H, W], not {tuple(img.shape)}')
+    if clean is not None and clean.shape != img.shape:
+        raise TypeError('band_images: clean must have the shape of img')
+    h, w = img.shape[-2:]
+    ring, nb = ring_table(kind, 1.0 / nbands, h, w, img.device)
+    out = band_split(img.reshape(-1, h, w), ring, nb, 0, clean=None if clean is None else clean.reshape(-1, h, w))
+    return out.reshape((nb,) + tuple(img.shape))
+
+
+class BandSplit(nn.Module):
+    """FrequencyDecompose(type, size, h, w, inverse) of the reference (net/utils/frequency_decompose.py:5-125) for ANY 8 <= h, w <= 1024:
+        'frequency_decompose'    bands [0, s) ... [1 - s, 1]       -> [nb,     B, C, h, w]
+        'frequency_decompose_1'  DC, (0, s] ... (1 - s, 1]         -> [nb + 1, B, C, h, w]
+        'frequency_decompose_dc' mean / residual                   -> [2,      B, C, h, w]
+    inverse=False -> [..., 2] (re, im) of the masked un-shifted spectrum; inverse='visual' -> magnitudes, fftshift-ed over ALL axes as
+    the reference's dim-less fftshift does (batch and channels rolled by B // 2, C // 2).  Forward only: the training path keeps
+    net.utils.frequency_decompose.FrequencyDecompose and its autograd function."""
+
+    def __init__(self, type, size, h, w, inverse=True):
+        super().__init__()
+        self.type, self.size, self.h, self.w, self.inverse = type, size, h, w, inverse
+        assert size > 0 and size <= 1, 'invalid frequency band width(size=%s)' % (size)
+        if type not in ('frequency_decompose', 'frequency_decompose_1', 'frequency_decompose_dc'):
+            raise ValueError(type)
+        if inverse not in (True, False, 'visual'):
+            raise ValueError(f'BandSplit: inverse={inverse!r}')
+        if not (8 <= h <= 1024 and 8 <= w <= 1024):
+            raise NotImplementedError('BandSplit handles maps of 8..1024 by 8..1024 pixels, not %sx%s' % (h, w))
+        if type != 'frequency_decompose_dc':
+            self.num_bands = math.floor(1. / self.size + 0.1)
+
+    def forward(self, x):
+        if x.requires_grad and torch.is_grad_enabled():
+            raise NotImplementedError('BandSplit is forward only; FrequencyDecompose (net/utils/frequency_decompose.py) is differentiable')
+        B, C, h, w = x.shape
+        xc = x.detach().contiguous().float()
+        if self.type == 'frequency_decompose_dc':
+            out = torch.empty((2, B, C, h, w), dtype=torch.float32, device=x.device)
+            call('fw_dc_split', xc, out, B * C, h * w)
+            return out
+        assert h == self.h and w == self.w
+        ring, nb = ring_table('bands' if self.type == 'frequency_decompose' else 'bands_1', self.size, h, w, x.device)
+        mode = 0 if self.inverse is True else 1 if self.inverse is False else 2
+        out = band_split(xc.reshape(B * C, h, w), ring, nb, mode)
+        out = out.reshape((nb, B, C, h, w, 2) if mode == 1 else (nb, B, C, h, w))
+        if mode == 2:
+            out = torch.roll(out, shifts=(B // 2, C // 2), dims=(1, 2))
+        return out
 
 
 def rgb2gray(img_hwc):

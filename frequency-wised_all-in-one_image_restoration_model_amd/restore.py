@@ -6,7 +6,7 @@ reused: a `test.py` on sys.path shadows the standard library's `test` package).
                       [--ckpt FILE] [--save_imgs True]
     python restore.py --ckpt FILE --input PATH --output DIR          (PATH: an image or a directory of images; no ground truth, no metrics)
                       [--keep_size] [--tile_overlap N] [--self_ensemble]
-    either of them with [--band_report N]
+    either of them with [--band_report N] [--band_images N]
 
 `--tile_overlap N` lets neighbouring tiles share N pixels (at most half a tile) and blends them with a linear ramp, so that the tile grid
 does not show; `--self_ensemble` averages the 8 flips / rotations of every tile; both also apply to the test sets, whose PSNR / SSIM
@@ -23,6 +23,12 @@ spectrum's corner radius, the mean over the images of the band's share E_b / sum
 Parseval is the set's PSNR.  With `--input` (no ground truth) it writes `<output>/bands.log`: the normalised ring distribution of the
 reference's get_frequency_distribution (grey image, rings of width 1 / N of half the image width) of every input and of its restoration.
 The results log and the PNGs do not depend on the flag.
+`--band_images N` (0, the default, turns it off) writes the N frequency bands of every restored image next to its PNG, as
+`<name>_band<k>.png`, k = 0 .. N - 1: fwair.spectrum.band_images of the clamped f32 restoration, per colour channel, at the image's own
+size (8 to 1024 pixels a side), the bands being those of --band_report.  Band 0 holds DC and is written as clamp(b, 0, 1); the bands k >= 1
+are zero-mean and are written as clamp(0.5 + b, 0, 1); band0 + sum_k (band_k - 0.5) is the restoration again.  With `--input` the bands
+of the input are written too, as `<name>_input_band<k>.png`; with test sets the flag needs `--save_imgs True`.  Everything else
+written is the same with and without the flag.
 `--save_imgs True` also writes `<output_path>epoch_<E>_imgs/test_<task>/<name>.png` (test.py:20-26,77-78).  The model flags
 (`--degradation_embedding_method`, `--compute_dtype`, ...) must be those the checkpoint was trained with; the training batch size,
 `--learnable_modulator` and `--embed_dim` are read off the checkpoint itself (net.model.options_from_checkpoint).
@@ -42,7 +48,10 @@ _own.add_argument('--tile_overlap', type=int, default=0, help='pixels neighbouri
 _own.add_argument('--self_ensemble', action='store_true', help='average the 8 flips / rotations of every tile (8 times the work)')
 _own.add_argument('--keep_size', action='store_true', help='--input: restore the image at its own size, not cropped to multiples of 16')
 _own.add_argument('--band_report', type=int, default=0, help='number of spectral bands of the per-band report (0: no report)')
+_own.add_argument('--band_images', type=int, default=0, help='number of spectral bands written as <name>_band<k>.png (0: none)')
 _ARGS, _rest = _own.parse_known_args()
+if _ARGS.band_images < 0 or _ARGS.band_images > 32:
+    _own.error('--band_images takes 0 (off) to 32 bands')
 sys.argv = [sys.argv[0]] + _rest                       # option.py parses sys.argv at import (reference option.py:3)
 
 import torch                                            # noqa: E402
@@ -51,6 +60,9 @@ from fwair.data import FolderTestSet, load_u8          # noqa: E402
 from fwair.evaluate import EvalEngine                   # noqa: E402
 from net.model import AirNet, options_from_checkpoint   # noqa: E402
 from option import options as opt                       # noqa: E402
+
+if _ARGS.band_images and not _ARGS.input and not opt.save_imgs:
+    _own.error('--band_images with test sets needs --save_imgs True: the bands are written next to the restored PNGs')
 
 _ENGINE = {}
 
@@ -67,6 +79,17 @@ def save_u8(img, path):
     """utils/image_io.py:375-391 on the uint8 image fw_eval_blend wrote: [3, H, W] -> PNG."""
     from PIL import Image
     Image.fromarray(img.cpu().numpy().transpose(1, 2, 0)).save(path)
+
+
+def save_bands(img, stem, nbands):
+    """--band_images: img [3, H, W], f32 in [0, 1] or u8 -> <stem>_band<k>.png (see the module docstring)"""
+    from fwair import spectrum
+    x = img.float() / 255.0 if img.dtype == torch.uint8 else img.float().clamp(0, 1)
+    b = spectrum.band_images(x.contiguous(), nbands)                                    # [nbands, 3, H, W]
+    b[1:] += 0.5
+    u8 = (b.clamp(0, 1) * 255.0).round().to(torch.uint8)
+    for k in range(nbands):
+        save_u8(u8[k], '%s_band%d.png' % (stem, k))
 
 
 def band_lines(task, clean, restored, nbands):
@@ -107,7 +130,8 @@ def test_by_task(net, task, epochs, bands=None):
     for im in clean:
         H, W = im.shape[1:]
         assert H >= opt.crop_test_imgs_size and W >= opt.crop_test_imgs_size, "invalid test image size (%d, %d)" % (H, W)     # test.py:43
-    out = _engine(net).run(clean, degraded, sigma=ts.sigma, seed=0, want_u8=bool(opt.save_imgs), want_f32=bands is not None)
+    want_f32 = bands is not None or bool(_ARGS.band_images)
+    out = _engine(net).run(clean, degraded, sigma=ts.sigma, seed=0, want_u8=bool(opt.save_imgs), want_f32=want_f32)
     if bands is not None:
         bands.extend(band_lines(task, clean, out[-1], _ARGS.band_report))
     if opt.save_imgs:
@@ -115,6 +139,9 @@ def test_by_task(net, task, epochs, bands=None):
         os.makedirs(output_path, exist_ok=True)
         for name, img in zip(ts.names, out[2]):
             save_u8(img, output_path + name + '.png')
+        if _ARGS.band_images:
+            for name, img in zip(ts.names, out[-1]):
+                save_bands(img, output_path + name, _ARGS.band_images)
     result = 'PSNR/SSIM: %.2f/%.4f' % (float(out[0].mean()), float(out[1].mean()))
     print(result)
     return result
@@ -127,9 +154,15 @@ def restore_files(net, src, dst):
     dev = next(net.parameters()).device
     imgs = [torch.from_numpy(load_u8(p, crop=not _ARGS.keep_size)).to(dev) for p in paths]
     os.makedirs(dst, exist_ok=True)
-    _, _, out = _engine(net, pad_small=True).run(None, imgs, want_u8=True)
+    res = _engine(net, pad_small=True).run(None, imgs, want_u8=True, want_f32=bool(_ARGS.band_images))
+    out = res[2]
     for p, img in zip(paths, out):
         save_u8(img, os.path.join(dst, os.path.basename(p).split('.')[0] + '.png'))
+    if _ARGS.band_images:
+        for p, img, f32 in zip(paths, imgs, res[3]):
+            stem = os.path.join(dst, os.path.basename(p).split('.')[0])
+            save_bands(f32, stem, _ARGS.band_images)
+            save_bands(img, stem + '_input', _ARGS.band_images)
     if _ARGS.band_report:
         with open(os.path.join(dst, 'bands.log'), 'w') as f:
             for line in distribution_lines([os.path.basename(p) for p in paths], imgs, out, _ARGS.band_report):

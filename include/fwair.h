@@ -233,6 +233,24 @@ int fw_dft2t_decompose(const float* img, const float* mask, const float* panels,
  * No global state; every launch goes to `stream`. */
 int fw_band_stats(int src_kind, const void* src, const unsigned char* clean, const unsigned char* ring, const float* panels_h,
                   const float* panels_w, float* work, double* out, int nimg, int H, int W, int nbands, int power, void* stream);
+/* The bands themselves, of maps of ANY size (csrc/fw_spec.hip; net/utils/frequency_decompose.py:5-125 for any (h, w)).  With
+ * M_b[u][v] = (ring[u][v] == b) and F_n = the un-normalised DFT2 of map n:
+ *   mode 0  band images   out f32 [nbands][nimg][H][W]    = Re IDFT2(M_b F_n), normalised by 1 / (H W)              (inverse=True)
+ *        1  masked spectra out f32 [nbands][nimg][H][W][2] = (re, im) of M_b F_n, UN-shifted coordinates; 8-byte aligned (inverse=False)
+ *        2  magnitudes    out f32 [nbands][nimg][H][W]    = |M_b F_n| in fftshift-ed coordinates of the two map axes: the bin (u, v) at
+ *                         [(u + H / 2) % H][(v + W / 2) % W] (integer H / 2, W / 2: DC at [H / 2][W / 2], odd sides included)
+ * src_kind, src, clean, ring, panels_h, panels_w, the ranges of H, W, nbands and nimg: exactly as for fw_band_stats; mode outside
+ * 0..2, like any other argument out of range, is the argument error and nothing is launched.  The ring may be ANY table: it need not
+ * be point-symmetric (mode 0 weights each bin of the half spectrum with the mean of its own and its mirror bin's membership, which is
+ * exact for the real part) nor a partition (a bin >= nbands is in no band).
+ *   work      f32, nimg * Hp * Wh * 4 floats in modes 1 and 2, nimg * Hp * Wh * (4 + 2 * min(nbands, 4)) floats in mode 0 (Hp, Wh as
+ *             for fw_band_stats: T^t and the half spectrum F^t, re and im, and in mode 0 the column-inverted bands G of up to 4 bands
+ *             at a time); 16-byte aligned; need not be initialised: the launch reads only what it wrote itself
+ *   out       EVERY element is written, those of a band without bins with 0.
+ * f32 products and sums on the matrix cores as in fw_band_stats; no atomics: the same input gives the same bits.  No global state;
+ * every launch goes to `stream`. */
+int fw_band_split(int src_kind, const void* src, const unsigned char* clean, const unsigned char* ring, const float* panels_h,
+                  const float* panels_w, float* work, float* out, int nimg, int H, int W, int nbands, int mode, void* stream);
 
 /* ---- encoder contrastive head: BatchNorm2d + LeakyReLU(0.1) + GAP (encoder_Uformer.py:945-951,978-984) -- */
 int fw_bn_lrelu_gap_fwd(int dtype, const void* fea, const float* gamma, const float* beta, float* rmean, float* rvar,
