@@ -239,6 +239,63 @@ template <int MT, int NT> FW_DEV void zero_acc(f32x4 (&acc)[MT][NT]) {
         for (int n = 0; n < NT; ++n) acc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
 }
 
+// ---------------------------------------------------------------- one k-chunk of a complex tile contraction (fw_dft.hip, fw_spec.hip)
+// Both operands are k-contiguous f32 matrices in GLOBAL memory, read as ready-made fragments (no LDS tile).
+#define FW_MFMA_F32(acc, a, b) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc, 0, 0, 0)
+
+FW_DEV f32x4 frag_g(const float* P, int pitch, int row0, int c) {       // rows row0..row0+15, chunk c (16 floats of K) of a [.][pitch] matrix
+    const int l = lane_id();
+    return *reinterpret_cast<const f32x4*>(P + (size_t)(row0 + (l & 15)) * pitch + c * 16 + ((l >> 4) << 2));
+}
+
+// A wave's 32 x 32 quadrant of out = data . P over one chunk: data (ar + i ai) rows d0.., panel rows p0.. of P = W = C - iS or conj(W).
+// p1 carries the imaginary input into the real output, p2 the real input into the imaginary output: (S, -S) for W, (-S, S) for
+// conj(W).  The first MFMA operand's tile index is the accumulator's first index, and its rows are the accumulator's 4 registers:
+// the data rows, or with PANEL_FIRST the panel rows.  mac() is THE order of accumulation ("accumulation order"): chunks in
+// order, inside a chunk k = 4 (l >> 4) + s for s = 0..3, per accumulator the real input's product before the imaginary input's.
+// ar / ai are plain members: a kernel may fill them itself (a converted source, a masked or band-weighted spectrum).
+template <bool REAL_IN, bool REAL_OUT, bool PANEL_FIRST> struct DftChunk {
+    f32x4 ar[2], ai[2], pc[2], p1[2], p2[2];
+    // The loaders take the 16-row tile t = 0, 1 of the quadrant: a kernel that fills or scales the data fragments itself calls them
+    // from its own loop over t, and the loads keep one order everywhere -- tile by tile, data before panels.
+    FW_MEM void load_panels(int t, const float* P, int pitch, int p0, int c, bool conj) {   // P: [3][pitch][pitch] cos, sin, -sin
+        const size_t plane = (size_t)pitch * pitch;
+        pc[t] = frag_g(P, pitch, p0 + 16 * t, c);
+        if (!REAL_IN) p1[t] = frag_g(P + (conj ? 2 : 1) * plane, pitch, p0 + 16 * t, c);
+        if (!REAL_OUT) p2[t] = frag_g(P + (conj ? 1 : 2) * plane, pitch, p0 + 16 * t, c);
+    }
+    FW_MEM void load_data(int t, const float* xr, const float* xi, int pitch, int d0, int c) {
+        ar[t] = frag_g(xr, pitch, d0 + 16 * t, c);
+        if (!REAL_IN) ai[t] = frag_g(xi, pitch, d0 + 16 * t, c);
+    }
+    FW_MEM void load(const float* xr, const float* xi, int dpitch, int d0, const float* P, int ppitch, int p0, int c, bool conj) {
+#pragma unroll
+        for (int t = 0; t < 2; ++t) {
+            load_data(t, xr, xi, dpitch, d0, c);
+            load_panels(t, P, ppitch, p0, c, conj);
+        }
+    }
+    FW_MEM void mac(f32x4 (&accr)[2][2], f32x4 (&acci)[2][2]) const {
+#pragma unroll
+        for (int s = 0; s < 4; ++s)                                         // consecutive MFMAs go to different accumulators
+#pragma unroll
+            for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+                for (int nt = 0; nt < 2; ++nt) {
+                    const int d = PANEL_FIRST ? nt : mt, p = PANEL_FIRST ? mt : nt;
+#define FW_CHUNK_MAC(acc, x, pn) FW_MFMA_F32(acc, PANEL_FIRST ? pn[p][s] : x[d][s], PANEL_FIRST ? x[d][s] : pn[p][s])
+                    FW_CHUNK_MAC(accr[mt][nt], ar, pc);
+                    if (!REAL_OUT) FW_CHUNK_MAC(acci[mt][nt], ar, p2);
+                    if (!REAL_IN) {
+                        FW_CHUNK_MAC(accr[mt][nt], ai, p1);
+                        if (!REAL_OUT) FW_CHUNK_MAC(acci[mt][nt], ai, pc);
+                    }
+#undef FW_CHUNK_MAC
+                }
+    }
+    FW_MEM void mac(f32x4 (&acc)[2][2]) const { mac(acc, acc); }            // REAL_OUT: the imaginary accumulator is never touched
+};
+
 // ---------------------------------------------------------------- host-side helpers
 #define FW_CHECK_ARG(cond)                                                                   \
     do {                                                                                     \

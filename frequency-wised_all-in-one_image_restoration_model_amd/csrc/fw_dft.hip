@@ -21,33 +21,29 @@ extern "C" int fw_band_residual(const float* img, float* out, int nimg, int N, i
 
 namespace {
 
-FW_DEV f32x4 dft_frag(const float* P, int N, int row0, int c) {           // fragment of a global k-contiguous f32 [.][N] matrix
-    const int l = lane_id();
-    return *reinterpret_cast<const f32x4*>(P + (size_t)(row0 + (l & 15)) * N + c * 16 + ((l >> 4) << 2));
-}
-
-template <bool REAL_IN, bool MASKED> struct DftFrags {
-    f32x4 ar[2], ai[2], pc[2], p1[2], p2[2];
+// dft_pass_kernel's chunk: DftChunk (fw_common.h) -- the fragments and mac(), the order of MFMAs -- with a loader of its own, which
+// multiplies the mask in and takes the three planes as pointers (null: not loaded).  The loader stays here because the kernel's
+// schedule follows it: on DftChunk's load_data / load_panels the same kernel needed 4 to 8 more VGPRs and ran slower
+// (profiles/r16_dft_tile_ab.json, profiles/r16_dft_tile_meta.txt).
+template <bool REAL_IN, bool REAL_OUT, bool MASKED> struct DftFrags : DftChunk<REAL_IN, REAL_OUT, false> {
     // d0 / p0: the wave's first data row / panel row.  P1 carries the imaginary input into the real output, P2 the real input
     // into the imaginary output: (S, -S) for W, (-S, S) for conj(W).
     FW_MEM void load(const float* inr, const float* ini, const float* M, const float* Pc, const float* P1, const float* P2, int N, int d0,
                      int p0, int c) {
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
-            ar[t] = dft_frag(inr, N, d0 + 16 * t, c);
-            if (!REAL_IN) ai[t] = dft_frag(ini, N, d0 + 16 * t, c);
+            this->ar[t] = frag_g(inr, N, d0 + 16 * t, c);
+            if (!REAL_IN) this->ai[t] = frag_g(ini, N, d0 + 16 * t, c);
             if (MASKED) {
-                const f32x4 m = dft_frag(M, N, d0 + 16 * t, c);
-                ar[t] *= m; ai[t] *= m;
+                const f32x4 m = frag_g(M, N, d0 + 16 * t, c);
+                this->ar[t] *= m; this->ai[t] *= m;
             }
-            pc[t] = dft_frag(Pc, N, p0 + 16 * t, c);
-            if (P1) p1[t] = dft_frag(P1, N, p0 + 16 * t, c);
-            if (P2) p2[t] = dft_frag(P2, N, p0 + 16 * t, c);
+            this->pc[t] = frag_g(Pc, N, p0 + 16 * t, c);
+            if (P1) this->p1[t] = frag_g(P1, N, p0 + 16 * t, c);
+            if (P2) this->p2[t] = frag_g(P2, N, p0 + 16 * t, c);
         }
     }
 };
-
-#define DFT_MFMA(acc, a, b) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc, 0, 0, 0)
 
 // grid (N/64 panel-row tiles, N/64 data-row tiles, nimg * nbands); 256 threads.  Map z = band * nimg + image.
 //   MASKED: every band reads the SAME input map (image z % nimg) through its own mask; otherwise input map z.
@@ -85,23 +81,11 @@ __global__ __launch_bounds__(256) void dft_pass_kernel(const float* __restrict__
     f32x4 accr[2][2], acci[2][2];
     zero_acc(accr); zero_acc(acci);
     const int KC = N / 16;
-    DftFrags<REAL_IN, MASKED> cur, nxt;
+    DftFrags<REAL_IN, REAL_OUT, MASKED> cur, nxt;
     cur.load(xr, xi, M, Pc, P1, P2, N, d0, p0, 0);
     for (int c = 0; c < KC; ++c) {
         if (c + 1 < KC) nxt.load(xr, xi, M, Pc, P1, P2, N, d0, p0, c + 1);  // the next chunk's fragments fly under this chunk's MFMAs
-#pragma unroll
-        for (int s = 0; s < 4; ++s)                                         // consecutive MFMAs go to different accumulators
-#pragma unroll
-            for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-                for (int nt = 0; nt < 2; ++nt) {
-                    DFT_MFMA(accr[mt][nt], cur.ar[mt][s], cur.pc[nt][s]);
-                    if (!REAL_OUT) DFT_MFMA(acci[mt][nt], cur.ar[mt][s], cur.p2[nt][s]);
-                    if (!REAL_IN) {
-                        DFT_MFMA(accr[mt][nt], cur.ai[mt][s], cur.p1[nt][s]);
-                        if (!REAL_OUT) DFT_MFMA(acci[mt][nt], cur.ai[mt][s], cur.pc[nt][s]);
-                    }
-                }
+        cur.mac(accr, acci);                                                // consecutive MFMAs go to different accumulators
         cur = nxt;
     }
     // acc element r of lane l is out[m = data row 4 (l >> 4) + r][n = panel row l & 15]: the transpose takes one 16-byte store

@@ -25,12 +25,7 @@
 
 namespace {
 
-#define SPEC_MFMA(acc, a, b) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, acc, 0, 0, 0)
-
-FW_DEV f32x4 spec_frag(const float* P, int pitch, int row0, int c) {      // fragment of a padded k-contiguous f32 [.][pitch] matrix
-    const int l = lane_id();
-    return *reinterpret_cast<const f32x4*>(P + (size_t)(row0 + (l & 15)) * pitch + c * 16 + ((l >> 4) << 2));
-}
+// Every pass below is a chunk loop over DftChunk (fw_common.h): data and panels loaded per 16-float chunk, single-buffered, then mac().
 
 // KIND 0: f32 map; 1: u8 map; 2: clamp(restored f32, 0, 1) - clean u8 / 255 (the difference eval_blend_body squares, fw_data.hip)
 template <int KIND> FW_DEV float spec_value(const float* f, const unsigned char* q, size_t i) {
@@ -59,6 +54,18 @@ template <int KIND> FW_DEV f32x4 spec_src_frag(const float* f, const unsigned ch
     return r;
 }
 
+FW_DEV int mirror_index(int n, int k) { return k ? n - k : 0; }             // (n - k) % n for k < n
+// g: the band of the bin (u, v); gm: the band of its mirror bin ((H - u) % H, (W - v) % W), looked up on its own -- the ring need not be
+// symmetric.  255: none (outside u < H, 2 v <= W; gm also in the bin's own mirror column, v = 0 or 2 v = W, unless own_column).
+// T: spec_col_kernel takes bytes, whose compares in its band reduction then stay byte-wide (with int the kernel was measurably slower
+// on one map, profiles/r16_dft_tile_meta.txt); spec_coli_kernel takes int.
+template <typename T> FW_DEV void ring_pair(const unsigned char* ring, int H, int W, int u, int v, bool own_column, T& g, T& gm) {
+    g = gm = 255;
+    if (u >= H || 2 * v > W) return;
+    g = ring[(size_t)u * W + v];
+    if (own_column || (v != 0 && 2 * v != W)) gm = ring[(size_t)mirror_index(H, u) * W + mirror_index(W, v)];
+}
+
 // grid (Wh / 64 tiles of v, Hp / 64 tiles of y, nimg); 256 threads.  Tr, Ti: [nimg][Wh][Hp].
 template <int KIND>
 __global__ __launch_bounds__(256) void spec_row_kernel(const float* __restrict__ srcf, const unsigned char* __restrict__ srcq,
@@ -69,28 +76,17 @@ __global__ __launch_bounds__(256) void spec_row_kernel(const float* __restrict__
     const int d0 = blockIdx.y * 64 + (w >> 1) * 32, p0 = blockIdx.x * 64 + (w & 1) * 32;
     const float* f = KIND == 1 ? nullptr : srcf + img * H * W;
     const unsigned char* q = KIND == 0 ? nullptr : srcq + img * H * W;
-    const float* Pc = PW;
-    const float* Pn = PW + 2 * (size_t)Wp * Wp;                              // -sin: the real input into the imaginary output
     f32x4 accr[2][2], acci[2][2];
     zero_acc(accr); zero_acc(acci);
     const int KC = (W + 15) / 16;
     for (int c = 0; c < KC; ++c) {
-        f32x4 a[2], pc[2], pn[2];
+        DftChunk<true, false, false> ch;                                    // real in, W: -sin carries it into the imaginary output
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
-            a[t] = spec_src_frag<KIND>(f, q, H, W, d0 + 16 * t + (l & 15), c * 16 + ((l >> 4) << 2), vec != 0);
-            pc[t] = spec_frag(Pc, Wp, p0 + 16 * t, c);
-            pn[t] = spec_frag(Pn, Wp, p0 + 16 * t, c);
+            ch.ar[t] = spec_src_frag<KIND>(f, q, H, W, d0 + 16 * t + (l & 15), c * 16 + ((l >> 4) << 2), vec != 0);
+            ch.load_panels(t, PW, Wp, p0, c, false);
         }
-#pragma unroll
-        for (int s = 0; s < 4; ++s)
-#pragma unroll
-            for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-                for (int nt = 0; nt < 2; ++nt) {
-                    SPEC_MFMA(accr[mt][nt], a[mt][s], pc[nt][s]);
-                    SPEC_MFMA(acci[mt][nt], a[mt][s], pn[nt][s]);
-                }
+        ch.mac(accr, acci);
     }
     // acc element r of lane l is out[m = data row y 4 (l >> 4) + r][n = panel row v l & 15]: the transpose takes one 16-byte store
     float* o_r = Tr + img * Wh * Hp;
@@ -115,33 +111,13 @@ __global__ __launch_bounds__(256) void spec_col_kernel(const float* __restrict__
     const int d0 = blockIdx.y * 64 + (w >> 1) * 32, p0 = blockIdx.x * 64 + (w & 1) * 32;       // d: v (rows of T^t), p: u
     const float* xr = Tr + img * Wh * Hp;
     const float* xi = Ti + img * Wh * Hp;
-    const float* Pc = PH;
-    const float* Ps = PH + (size_t)Hp * Hp;
-    const float* Pn = PH + 2 * (size_t)Hp * Hp;
     f32x4 accr[2][2], acci[2][2];
     zero_acc(accr); zero_acc(acci);
     const int KC = (H + 15) / 16;
     for (int c = 0; c < KC; ++c) {
-        f32x4 ar[2], ai[2], pc[2], ps[2], pn[2];
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            ar[t] = spec_frag(xr, Hp, d0 + 16 * t, c);
-            ai[t] = spec_frag(xi, Hp, d0 + 16 * t, c);
-            pc[t] = spec_frag(Pc, Hp, p0 + 16 * t, c);
-            ps[t] = spec_frag(Ps, Hp, p0 + 16 * t, c);
-            pn[t] = spec_frag(Pn, Hp, p0 + 16 * t, c);
-        }
-#pragma unroll
-        for (int s = 0; s < 4; ++s)                                         // (a + i b)(C - i S) = a C + b S + i (b C - a S)
-#pragma unroll
-            for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-                for (int nt = 0; nt < 2; ++nt) {
-                    SPEC_MFMA(accr[mt][nt], ar[mt][s], pc[nt][s]);
-                    SPEC_MFMA(acci[mt][nt], ar[mt][s], pn[nt][s]);
-                    SPEC_MFMA(accr[mt][nt], ai[mt][s], ps[nt][s]);
-                    SPEC_MFMA(acci[mt][nt], ai[mt][s], pc[nt][s]);
-                }
+        DftChunk<false, false, false> ch;                                   // (a + i b)(C - i S) = a C + b S + i (b C - a S)
+        ch.load(xr, xi, Hp, d0, PH, Hp, p0, c, false);
+        ch.mac(accr, acci);
     }
     // acc element r of lane l: v = d0 + 16 mt + 4 (l >> 4) + r, u = p0 + 16 nt + (l & 15)
     float val[16];
@@ -158,11 +134,8 @@ __global__ __launch_bounds__(256) void spec_col_kernel(const float* __restrict__
                 const float a = accr[mt][nt][r], b = acci[mt][nt][r];
                 const float e = a * a + b * b;
                 val[k] = power ? e : sqrtf(e);
-                unsigned char g = 255, gm = 255;
-                if (u < H && 2 * v <= W) {
-                    g = ring[(size_t)u * W + v];
-                    if (v != 0 && 2 * v != W) gm = ring[(size_t)(u ? H - u : 0) * W + (W - v)];
-                }
+                unsigned char g, gm;                                        // bytes, as the table's: the compares below stay byte-wide
+                ring_pair(ring, H, W, u, v, false, g, gm);                  // a bin in its own mirror column counts once
                 if (g >= nbands) g = 255;
                 if (gm >= nbands) gm = 255;
                 bnd[k] = g; mir[k] = gm;
@@ -216,33 +189,13 @@ __global__ __launch_bounds__(256) void spec_colf_kernel(const float* __restrict_
     const int d0 = blockIdx.y * 64 + (w >> 1) * 32, p0 = blockIdx.x * 64 + (w & 1) * 32;       // d: v (rows of T^t), p: u
     const float* xr = Tr + img * Wh * Hp;
     const float* xi = Ti + img * Wh * Hp;
-    const float* Pc = PH;
-    const float* Ps = PH + (size_t)Hp * Hp;
-    const float* Pn = PH + 2 * (size_t)Hp * Hp;
     f32x4 accr[2][2], acci[2][2];
     zero_acc(accr); zero_acc(acci);
     const int KC = (H + 15) / 16;
     for (int c = 0; c < KC; ++c) {
-        f32x4 ar[2], ai[2], pc[2], ps[2], pn[2];
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            ar[t] = spec_frag(xr, Hp, d0 + 16 * t, c);
-            ai[t] = spec_frag(xi, Hp, d0 + 16 * t, c);
-            pc[t] = spec_frag(Pc, Hp, p0 + 16 * t, c);
-            ps[t] = spec_frag(Ps, Hp, p0 + 16 * t, c);
-            pn[t] = spec_frag(Pn, Hp, p0 + 16 * t, c);
-        }
-#pragma unroll
-        for (int s = 0; s < 4; ++s)                                         // the panel is the first operand: the accumulator's 4 rows are u
-#pragma unroll
-            for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-                for (int nt = 0; nt < 2; ++nt) {
-                    SPEC_MFMA(accr[mt][nt], pc[mt][s], ar[nt][s]);
-                    SPEC_MFMA(acci[mt][nt], pn[mt][s], ar[nt][s]);
-                    SPEC_MFMA(accr[mt][nt], ps[mt][s], ai[nt][s]);
-                    SPEC_MFMA(acci[mt][nt], pc[mt][s], ai[nt][s]);
-                }
+        DftChunk<false, false, true> ch;                                    // the panel is the first operand: the accumulator's 4 rows are u
+        ch.load(xr, xi, Hp, d0, PH, Hp, p0, c, false);
+        ch.mac(accr, acci);
     }
     // acc element r of lane l: u = p0 + 16 mt + 4 (l >> 4) + r, v = d0 + 16 nt + (l & 15)
     float* o_r = Fr + img * Wh * Hp;
@@ -267,58 +220,36 @@ __global__ __launch_bounds__(256) void spec_coli_kernel(const float* __restrict_
     const int d0 = blockIdx.y * 64 + (w >> 1) * 32, p0 = blockIdx.x * 64 + (w & 1) * 32;       // d: v (rows of F^t), p: y
     const float* xr = Fr + img * Wh * Hp;
     const float* xi = Fi + img * Wh * Hp;
-    const float* Pc = PH;
-    const float* Ps = PH + (size_t)Hp * Hp;
-    const float* Pn = PH + 2 * (size_t)Hp * Hp;
     f32x4 accr[NB][2][2], acci[NB][2][2];
 #pragma unroll
     for (int j = 0; j < NB; ++j) { zero_acc(accr[j]); zero_acc(acci[j]); }
     const int KC = (H + 15) / 16;
     for (int c = 0; c < KC; ++c) {
-        f32x4 ar[2], ai[2], pc[2], ps[2], pn[2];
-        int g[2][4], gm[2][4];                                              // band of the bin and of its mirror bin, -1: weight 0
+        DftChunk<false, false, false> ch;                                   // conj(W): (a + i b)(C + i S) = a C - b S + i (a S + b C)
+        f32x4 fr[2], fi[2];                                                 // the F fragments every band of the group weights
+        int g[2][4], gm[2][4];                                              // band of the bin and of its mirror bin, 255: weight 0
         float cv[2];
 #pragma unroll
         for (int t = 0; t < 2; ++t) {
-            ar[t] = spec_frag(xr, Hp, d0 + 16 * t, c);
-            ai[t] = spec_frag(xi, Hp, d0 + 16 * t, c);
-            pc[t] = spec_frag(Pc, Hp, p0 + 16 * t, c);
-            ps[t] = spec_frag(Ps, Hp, p0 + 16 * t, c);
-            pn[t] = spec_frag(Pn, Hp, p0 + 16 * t, c);
+            fr[t] = frag_g(xr, Hp, d0 + 16 * t, c);
+            fi[t] = frag_g(xi, Hp, d0 + 16 * t, c);
+            ch.load_panels(t, PH, Hp, p0, c, true);
             const int v = d0 + 16 * t + (l & 15);
-            cv[t] = (v == 0 || 2 * v == W) ? 0.5f : 1.0f;
+            cv[t] = (v == 0 || 2 * v == W) ? 0.5f : 1.0f;                   // its own mirror column: both lookups, half the weight
 #pragma unroll
-            for (int s = 0; s < 4; ++s) {
-                const int u = c * 16 + ((l >> 4) << 2) + s;
-                g[t][s] = gm[t][s] = -1;
-                if (u < H && 2 * v <= W) {
-                    g[t][s] = ring[(size_t)u * W + v];
-                    gm[t][s] = ring[(size_t)(u ? H - u : 0) * W + (v ? W - v : 0)];
-                }
-            }
+            for (int s = 0; s < 4; ++s) ring_pair(ring, H, W, c * 16 + ((l >> 4) << 2) + s, v, true, g[t][s], gm[t][s]);
         }
 #pragma unroll
         for (int j = 0; j < NB; ++j) {
-            f32x4 br[2], bi[2];
 #pragma unroll
             for (int t = 0; t < 2; ++t)
 #pragma unroll
                 for (int s = 0; s < 4; ++s) {
                     const float wt = cv[t] * ((g[t][s] == b0 + j ? 1.f : 0.f) + (gm[t][s] == b0 + j ? 1.f : 0.f));
-                    br[t][s] = wt * ar[t][s];
-                    bi[t][s] = wt * ai[t][s];
+                    ch.ar[t][s] = wt * fr[t][s];
+                    ch.ai[t][s] = wt * fi[t][s];
                 }
-#pragma unroll
-            for (int s = 0; s < 4; ++s)                                     // (a + i b)(C + i S) = a C - b S + i (a S + b C)
-#pragma unroll
-                for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-                    for (int nt = 0; nt < 2; ++nt) {
-                        SPEC_MFMA(accr[j][mt][nt], br[mt][s], pc[nt][s]);
-                        SPEC_MFMA(acci[j][mt][nt], br[mt][s], ps[nt][s]);
-                        SPEC_MFMA(accr[j][mt][nt], bi[mt][s], pn[nt][s]);
-                        SPEC_MFMA(acci[j][mt][nt], bi[mt][s], pc[nt][s]);
-                    }
+            ch.mac(accr[j], acci[j]);
         }
     }
     // acc element r of lane l: v = d0 + 16 mt + 4 (l >> 4) + r, y = p0 + 16 nt + (l & 15)
@@ -347,29 +278,13 @@ __global__ __launch_bounds__(256) void spec_rowi_kernel(const float* __restrict_
     const int d0 = ty * 64 + (w >> 1) * 32, p0 = blockIdx.x * 64 + (w & 1) * 32;               // d: y (rows of G), p: x
     const float* xr = Gr + ((size_t)j * nimg + img) * Hp * Wh;
     const float* xi = Gi + ((size_t)j * nimg + img) * Hp * Wh;
-    const float* Pc = PW;
-    const float* Pn = PW + 2 * (size_t)Wp * Wp;
     f32x4 acc[2][2];
     zero_acc(acc);
     const int KC = (W / 2 + 1 + 15) / 16;
     for (int c = 0; c < KC; ++c) {
-        f32x4 ar[2], ai[2], pc[2], pn[2];
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            ar[t] = spec_frag(xr, Wh, d0 + 16 * t, c);
-            ai[t] = spec_frag(xi, Wh, d0 + 16 * t, c);
-            pc[t] = spec_frag(Pc, Wp, p0 + 16 * t, c);
-            pn[t] = spec_frag(Pn, Wp, p0 + 16 * t, c);
-        }
-#pragma unroll
-        for (int s = 0; s < 4; ++s)                                         // Re((a + i b)(C + i S)) = a C - b S; the panel first: 4 rows are x
-#pragma unroll
-            for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-                for (int nt = 0; nt < 2; ++nt) {
-                    SPEC_MFMA(acc[mt][nt], pc[mt][s], ar[nt][s]);
-                    SPEC_MFMA(acc[mt][nt], pn[mt][s], ai[nt][s]);
-                }
+        DftChunk<false, true, true> ch;                                     // Re((a + i b)(C + i S)) = a C - b S; the panel first: 4 rows are x
+        ch.load(xr, xi, Wh, d0, PW, Wp, p0, c, true);
+        ch.mac(acc);
     }
     // acc element r of lane l: x = p0 + 16 mt + 4 (l >> 4) + r, y = d0 + 16 nt + (l & 15); vec: W % 4 == 0 and an aligned base
     float* o = out + ((size_t)(b0 + j) * nimg + img) * H * W;
@@ -409,7 +324,7 @@ __global__ __launch_bounds__(256) void spec_bins_kernel(const float* __restrict_
     }
     const int g = ring[(size_t)u * W + v];
     const bool half = 2 * v <= W;                                           // else the mirror bin, conjugated
-    const size_t f = img * Wh * Hp + (size_t)(half ? v : W - v) * Hp + (half ? u : (u ? H - u : 0));
+    const size_t f = img * Wh * Hp + (size_t)(half ? v : mirror_index(W, v)) * Hp + (half ? u : mirror_index(H, u));
     const float re = Fr[f], im = half ? Fi[f] : -Fi[f];
     const float mag = sqrtf(re * re + im * im);
     for (int b = 0; b < nbands; ++b) {
@@ -424,45 +339,54 @@ __global__ __launch_bounds__(256) void spec_bins_kernel(const float* __restrict_
 
 #define ST ((hipStream_t)stream)
 
+// What fw_band_stats and fw_band_split share: the argument checks, the padded geometry, the source as the row pass reads it
+// (vec: W % 4 == 0 and aligned bases) and per, the floats of one [nimg][Wh][Hp] work array.
+struct SpecGeom { int Hp, Wp, Wh, vec; size_t per; const float* f; const unsigned char* q; };
+static int spec_geom(SpecGeom& g, int src_kind, const void* src, const unsigned char* clean, const float* panels_h, const float* panels_w,
+                     const float* work, int nimg, int H, int W, int nbands) {
+    FW_CHECK_ARG(src && panels_h && panels_w && work && src_kind >= 0 && src_kind <= 2 && (src_kind != 2 || clean) && nimg > 0 &&
+                 nimg <= 65535 && H >= 8 && H <= 1024 && W >= 8 && W <= 1024 && nbands >= 1 && nbands <= 32);
+    FW_CHECK_ARG((((uintptr_t)panels_h | (uintptr_t)panels_w | (uintptr_t)work) & 15) == 0 && (src_kind == 1 || ((uintptr_t)src & 3) == 0));
+    g.Hp = (H + 63) / 64 * 64; g.Wp = (W + 63) / 64 * 64; g.Wh = (W / 2 + 1 + 63) / 64 * 64;
+    g.per = (size_t)nimg * g.Hp * g.Wh;
+    g.f = src_kind == 1 ? nullptr : (const float*)src;
+    g.q = src_kind == 1 ? (const unsigned char*)src : clean;
+    g.vec = W % 4 == 0 && (!g.f || ((uintptr_t)g.f & 15) == 0) && (!g.q || ((uintptr_t)g.q & 3) == 0);
+    return 0;
+}
+static void spec_launch_row(const SpecGeom& g, int src_kind, const float* panels_w, float* Tr, float* Ti, int nimg, int H, int W, void* stream) {
+#define SPEC_ROW(KIND)                                                                                                              \
+    hipLaunchKernelGGL(spec_row_kernel<KIND>, dim3(g.Wh / 64, g.Hp / 64, nimg), dim3(256), 0, ST, g.f, g.q, panels_w, Tr, Ti, H, W, g.Hp, \
+                       g.Wp, g.Wh, g.vec)
+    if (src_kind == 0) SPEC_ROW(0); else if (src_kind == 1) SPEC_ROW(1); else SPEC_ROW(2);
+#undef SPEC_ROW
+}
+
 extern "C" int fw_band_stats(int src_kind, const void* src, const unsigned char* clean, const unsigned char* ring, const float* panels_h,
                              const float* panels_w, float* work, double* out, int nimg, int H, int W, int nbands, int power, void* stream) {
-    FW_CHECK_ARG(src && ring && panels_h && panels_w && work && out && src_kind >= 0 && src_kind <= 2 && (src_kind != 2 || clean) &&
-                 nimg > 0 && nimg <= 65535 && H >= 8 && H <= 1024 && W >= 8 && W <= 1024 && nbands >= 1 && nbands <= 32 &&
-                 (power == 0 || power == 1));
-    FW_CHECK_ARG((((uintptr_t)panels_h | (uintptr_t)panels_w | (uintptr_t)work) & 15) == 0 && ((uintptr_t)out & 7) == 0 &&
-                 (src_kind == 1 || ((uintptr_t)src & 3) == 0));
-    const int Hp = (H + 63) / 64 * 64, Wp = (W + 63) / 64 * 64, Wh = (W / 2 + 1 + 63) / 64 * 64, tiles = (Hp / 64) * (Wh / 64);
-    const size_t per = (size_t)nimg * Hp * Wh;
-    float* Tr = work; float* Ti = work + per; float* part = work + 2 * per;
-    const float* f = src_kind == 1 ? nullptr : (const float*)src;
-    const unsigned char* q = src_kind == 1 ? (const unsigned char*)src : clean;
-    const int vec = W % 4 == 0 && (!f || ((uintptr_t)f & 15) == 0) && (!q || ((uintptr_t)q & 3) == 0);
-    const dim3 grow(Wh / 64, Hp / 64, nimg), gcol(Hp / 64, Wh / 64, nimg);
-    if (src_kind == 0) hipLaunchKernelGGL(spec_row_kernel<0>, grow, dim3(256), 0, ST, f, q, panels_w, Tr, Ti, H, W, Hp, Wp, Wh, vec);
-    else if (src_kind == 1) hipLaunchKernelGGL(spec_row_kernel<1>, grow, dim3(256), 0, ST, f, q, panels_w, Tr, Ti, H, W, Hp, Wp, Wh, vec);
-    else hipLaunchKernelGGL(spec_row_kernel<2>, grow, dim3(256), 0, ST, f, q, panels_w, Tr, Ti, H, W, Hp, Wp, Wh, vec);
-    hipLaunchKernelGGL(spec_col_kernel, gcol, dim3(256), 0, ST, Tr, Ti, panels_h, ring, part, H, W, Hp, Wh, nbands, power);
+    SpecGeom g;
+    const int rc = spec_geom(g, src_kind, src, clean, panels_h, panels_w, work, nimg, H, W, nbands);
+    if (rc) return rc;
+    FW_CHECK_ARG(ring && out && (power == 0 || power == 1) && ((uintptr_t)out & 7) == 0);
+    const int Hp = g.Hp, Wh = g.Wh, tiles = (Hp / 64) * (Wh / 64);
+    float* Tr = work; float* Ti = work + g.per; float* part = work + 2 * g.per;
+    spec_launch_row(g, src_kind, panels_w, Tr, Ti, nimg, H, W, stream);
+    hipLaunchKernelGGL(spec_col_kernel, dim3(Hp / 64, Wh / 64, nimg), dim3(256), 0, ST, Tr, Ti, panels_h, ring, part, H, W, Hp, Wh, nbands, power);
     hipLaunchKernelGGL(spec_fold_kernel, dim3(nimg), dim3(64), 0, ST, part, out, tiles, nbands);
     FW_LAUNCH_RET();
 }
 
 extern "C" int fw_band_split(int src_kind, const void* src, const unsigned char* clean, const unsigned char* ring, const float* panels_h,
                              const float* panels_w, float* work, float* out, int nimg, int H, int W, int nbands, int mode, void* stream) {
-    FW_CHECK_ARG(src && ring && panels_h && panels_w && work && out && src_kind >= 0 && src_kind <= 2 && (src_kind != 2 || clean) &&
-                 nimg > 0 && nimg <= 65535 && H >= 8 && H <= 1024 && W >= 8 && W <= 1024 && nbands >= 1 && nbands <= 32 && mode >= 0 &&
-                 mode <= 2);
-    FW_CHECK_ARG((((uintptr_t)panels_h | (uintptr_t)panels_w | (uintptr_t)work) & 15) == 0 && ((uintptr_t)out & (mode == 1 ? 7 : 3)) == 0 &&
-                 (src_kind == 1 || ((uintptr_t)src & 3) == 0));
-    const int Hp = (H + 63) / 64 * 64, Wp = (W + 63) / 64 * 64, Wh = (W / 2 + 1 + 63) / 64 * 64;
-    const size_t per = (size_t)nimg * Hp * Wh;
+    SpecGeom g;
+    const int rc = spec_geom(g, src_kind, src, clean, panels_h, panels_w, work, nimg, H, W, nbands);
+    if (rc) return rc;
+    FW_CHECK_ARG(ring && out && mode >= 0 && mode <= 2 && ((uintptr_t)out & (mode == 1 ? 7 : 3)) == 0);
+    const int Hp = g.Hp, Wp = g.Wp, Wh = g.Wh;
+    const size_t per = g.per;
     float* Tr = work; float* Ti = work + per; float* Fr = work + 2 * per; float* Fi = work + 3 * per;
-    const float* f = src_kind == 1 ? nullptr : (const float*)src;
-    const unsigned char* q = src_kind == 1 ? (const unsigned char*)src : clean;
-    const int vec = W % 4 == 0 && (!f || ((uintptr_t)f & 15) == 0) && (!q || ((uintptr_t)q & 3) == 0);
-    const dim3 grow(Wh / 64, Hp / 64, nimg), gcol(Hp / 64, Wh / 64, nimg);
-    if (src_kind == 0) hipLaunchKernelGGL(spec_row_kernel<0>, grow, dim3(256), 0, ST, f, q, panels_w, Tr, Ti, H, W, Hp, Wp, Wh, vec);
-    else if (src_kind == 1) hipLaunchKernelGGL(spec_row_kernel<1>, grow, dim3(256), 0, ST, f, q, panels_w, Tr, Ti, H, W, Hp, Wp, Wh, vec);
-    else hipLaunchKernelGGL(spec_row_kernel<2>, grow, dim3(256), 0, ST, f, q, panels_w, Tr, Ti, H, W, Hp, Wp, Wh, vec);
+    const dim3 gcol(Hp / 64, Wh / 64, nimg);
+    spec_launch_row(g, src_kind, panels_w, Tr, Ti, nimg, H, W, stream);
     hipLaunchKernelGGL(spec_colf_kernel, gcol, dim3(256), 0, ST, Tr, Ti, panels_h, Fr, Fi, H, Hp, Wh);
     if (mode != 0) {
         const dim3 gb((H * W + 255) / 256, nimg);

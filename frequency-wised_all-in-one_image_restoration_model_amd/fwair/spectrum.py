@@ -111,17 +111,21 @@ def work_floats(nimg, h, w, nbands):
     return nimg * (2 * padded(h) * wh + (padded(h) // 64) * (wh // 64) * nbands)
 
 
+def _source(name, src, clean):
+    """the source of fw_band_stats / fw_band_split checked -> (source kind, src, clean), both contiguous"""
+    kind = 2 if clean is not None else (1 if src.dtype == torch.uint8 else 0)
+    if kind != 1 and src.dtype != torch.float32:
+        raise TypeError(f'{name}: {src.dtype} maps (float32 or uint8)')
+    if clean is not None and (clean.dtype != torch.uint8 or clean.shape != src.shape):
+        raise TypeError(f'{name}: clean must be uint8 of the shape of the restored maps')
+    return kind, src.contiguous(), clean.contiguous() if clean is not None else None
+
+
 def band_stats(src, ring, nbands, power, clean=None):
     """fw_band_stats on src [n, H, W] (f32 or u8, contiguous; with `clean` u8 [n, H, W]: the error map of restored f32 `src`).
     -> double [n, nbands]"""
     n, h, w = src.shape
-    kind = 2 if clean is not None else (1 if src.dtype == torch.uint8 else 0)
-    if kind != 1 and src.dtype != torch.float32:
-        raise TypeError(f'band_stats: {src.dtype} maps (float32 or uint8)')
-    if clean is not None and (clean.dtype != torch.uint8 or clean.shape != src.shape):
-        raise TypeError('band_stats: clean must be uint8 of the shape of the restored maps')
-    src = src.contiguous()
-    clean = clean.contiguous() if clean is not None else None
+    kind, src, clean = _source('band_stats', src, clean)
     out = torch.empty((n, nbands), dtype=torch.float64, device=src.device)
     work = torch.empty(work_floats(n, h, w, nbands), dtype=torch.float32, device=src.device)
     call('fw_band_stats', kind, src, clean, ring, panels(h, src.device), panels(w, src.device), work, out, n, h, w, nbands, power)
@@ -140,17 +144,11 @@ def band_split(src, ring, nbands, mode, clean=None):
     if src.dim() != 3:
         raise ValueError(f'band_split: maps [n, H, W], not {tuple(src.shape)}')
     n, h, w = src.shape
-    kind = 2 if clean is not None else (1 if src.dtype == torch.uint8 else 0)
-    if kind != 1 and src.dtype != torch.float32:
-        raise TypeError(f'band_split: {src.dtype} maps (float32 or uint8)')
-    if clean is not None and (clean.dtype != torch.uint8 or clean.shape != src.shape):
-        raise TypeError('band_split: clean must be uint8 of the shape of the restored maps')
+    kind, src, clean = _source('band_split', src, clean)
     if ring.dtype != torch.uint8 or tuple(ring.shape) != (h, w):
         raise TypeError(f'band_split: the ring must be uint8 [{h}, {w}]')
     if mode not in (0, 1, 2):
         raise ValueError(f'band_split: mode {mode} (0 band images, 1 masked spectra, 2 magnitudes)')
-    src = src.contiguous()
-    clean = clean.contiguous() if clean is not None else None
     out = torch.empty((nbands, n, h, w, 2) if mode == 1 else (nbands, n, h, w), dtype=torch.float32, device=src.device)
     work = torch.empty(split_work_floats(n, h, w, nbands, mode), dtype=torch.float32, device=src.device)
     call('fw_band_split', kind, src, clean, ring.contiguous(), panels(h, src.device), panels(w, src.device), work, out, n, h, w, nbands, mode)
