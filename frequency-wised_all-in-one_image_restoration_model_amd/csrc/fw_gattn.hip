@@ -24,7 +24,7 @@
 // Any other N = 64 nt up to 1024 (N = 576 at 384x384, 1024 at 512x512): gattn_stream_fwd_kernel walks the key tiles with an online
 // softmax, and the backward body runs with a run-time tile count (NT = 0).  The band re-weighting with N x N masks exists there at
 // N = 576 and N = 1024 only: 'DC' as a second, unrescaled accumulator of the streaming forward (the affine form of N = 256), <n>_bands
-// as LDS-free 64x64-tile DFT passes between a probabilities and an apply kernel (bandsn_pass_kernel, fw_gattn_bandsn_fwd / bwd).
+// as LDS-free 64x64-tile DFT passes between a probabilities and an apply kernel (bandsn_pass_kernel; fw_gattn_bands_fwd / bwd serve all three N).
 #include "fw_common.h"
 
 namespace {
@@ -1098,7 +1098,9 @@ __global__ __launch_bounds__(NTH) void bands_out_kernel(float* __restrict__ map,
         }
 }
 
-// dvec[row] = sum_j P[row][j] dA[row][j]; one wave per row of 256
+// dvec[row] = sum_j P[row][j] dA[row][j]; one wave per row of 256.  Not gattn_rowdotn_kernel with N = 256: the compiler contracts this
+// one expression to an FMA chain and the loop body there to packed multiplies and adds, so the two round differently and each
+// size keeps the kernel its pinned bytes came from (tests/test_spec_bits_gpu.py, group gattn_bands).
 __global__ __launch_bounds__(NTH) void gattn_rowdot_kernel(const float* __restrict__ P, const float* __restrict__ dA, float* __restrict__ dvec) {
     const long row = (long)blockIdx.x * 4 + wave_id();
     const int l = lane_id();
@@ -1160,22 +1162,20 @@ template <typename T> static int bands_bwd(const GAttnArgs& a, float* work, hipS
 //     output pass   map[r][c] += Re sum_u Z^t[c][u] conj(W)[u][r] / N^2
 // The four partial sums (re C, im S, im C, re S) keep their own accumulators and meet at the end with the signs of W or conj(W), so
 // the cos | sin panels of the N = 256 passes serve unchanged.  The tile walk is generic in N / 64.
-FW_DEV f32x4 gfrag(const float* P, int N, int row0, int c) {              // fragment of a global k-contiguous f32 [.][N] matrix
-    const int l = lane_id();
-    return *reinterpret_cast<const f32x4*>(P + (size_t)(row0 + (l & 15)) * N + c * 16 + ((l >> 4) << 2));
-}
+// This is NOT DftChunk::mac (fw_common.h), on purpose: on DftChunk -- two accumulator sets, a third -sin plane, five fragments per
+// tile and chunk where this form loads four -- the complex passes ran 6 to 9 % slower (profiles/r17_gattn_bands_ab.json).
+// The fragment loader and the MFMA are fw_common.h's (::frag_g: the frag_g of this file reads the 64x64 panels of the N = 64 filter).
 struct BnFrags { f32x4 ar[2], ai[2], pc[2], ps[2]; };
 template <bool REAL_IN>
 FW_DEV void bn_load(BnFrags& f, const float* xr, const float* xi, const float* Pc, const float* Ps, int N, int d0, int p0, int c) {
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
-        f.ar[t] = gfrag(xr, N, d0 + 16 * t, c);
-        if (!REAL_IN) f.ai[t] = gfrag(xi, N, d0 + 16 * t, c);
-        f.pc[t] = gfrag(Pc, N, p0 + 16 * t, c);
-        f.ps[t] = gfrag(Ps, N, p0 + 16 * t, c);
+        f.ar[t] = ::frag_g(xr, N, d0 + 16 * t, c);
+        if (!REAL_IN) f.ai[t] = ::frag_g(xi, N, d0 + 16 * t, c);
+        f.pc[t] = ::frag_g(Pc, N, p0 + 16 * t, c);
+        f.ps[t] = ::frag_g(Ps, N, p0 + 16 * t, c);
     }
 }
-#define BN_MFMA(acc, x, y) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(x, y, acc, 0, 0, 0)
 enum { E_PLAIN = 0, E_WEIGHT = 1, E_WEIGHT_DL = 2 };
 // grid (N/64 panel-row tiles, N/64 data-row tiles, maps); 256 threads.  REAL_OUT adds scale * Re(.) to outr (the map) in place.
 // EPI: E_WEIGHT multiplies the result by lamb[band(p, d)]; E_WEIGHT_DL first reduces d lamb against the spectrum (pr, pi) of P.
@@ -1213,11 +1213,11 @@ __global__ __launch_bounds__(NTH) void bandsn_pass_kernel(const float* __restric
             for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
                 for (int nt = 0; nt < 2; ++nt) {
-                    BN_MFMA(rc[mt][nt], cur.ar[mt][s], cur.pc[nt][s]);
-                    if (!REAL_OUT) BN_MFMA(is[mt][nt], cur.ar[mt][s], cur.ps[nt][s]);
+                    FW_MFMA_F32(rc[mt][nt], cur.ar[mt][s], cur.pc[nt][s]);
+                    if (!REAL_OUT) FW_MFMA_F32(is[mt][nt], cur.ar[mt][s], cur.ps[nt][s]);
                     if (!REAL_IN) {
-                        BN_MFMA(rs[mt][nt], cur.ai[mt][s], cur.ps[nt][s]);
-                        if (!REAL_OUT) BN_MFMA(ic[mt][nt], cur.ai[mt][s], cur.pc[nt][s]);
+                        FW_MFMA_F32(rs[mt][nt], cur.ai[mt][s], cur.ps[nt][s]);
+                        if (!REAL_OUT) FW_MFMA_F32(ic[mt][nt], cur.ai[mt][s], cur.pc[nt][s]);
                     }
                 }
         cur = nxt;
@@ -1482,26 +1482,39 @@ static bool common_ok(const GAttnArgs& a, int dtype) {
     }
     return true;
 }
-// <n>_bands on the 256x256 map: the tables are required (that is what tells it from the table-free 'DC' form of fw_gattn_fwd)
+// <n>_bands on the N x N map, N in {256, 576, 1024}: the tables are required (that is what tells it from the table-free 'DC' form of
+// fw_gattn_fwd); the tiled passes put the maps on the grid's z axis
 static bool bands_ok(const GAttnArgs& a, int dtype) {
     const int sz = dtype == FW_DT_BF16 ? 2 : 4;
+    if (!(a.N == 256 || ((a.N == 576 || a.N == 1024) && (long)a.B * a.heads <= 65535))) return false;
     if (!(a.q && a.k && a.v && a.lse && a.B > 0 && a.heads > 0)) return false;
     if ((a.ld * sz) % 16 || ((uintptr_t)a.q | (uintptr_t)a.k | (uintptr_t)a.v) % 16) return false;
     if (a.thresh && !a.seed) return false;
     return a.lamb && a.bandidx && a.panels && (uintptr_t)a.panels % 16 == 0 && (uintptr_t)a.bandidx % 4 == 0 && a.nb >= 1 && a.nb <= 16 &&
            (a.lamb_batch == 1 || a.lamb_batch == a.B);
 }
+template <typename T> static int bands_dispatch(const GAttnArgs& a, float* work, bool bwd, hipStream_t st) {
+    if (a.N == 256) return bwd ? bands_bwd<T>(a, work, st) : bands_fwd<T>(a, work, st);
+    return bwd ? bandsn_bwd<T>(a, work, st) : bandsn_fwd<T>(a, work, st);
+}
+// what the four entries share: operands, geometry, Dropout, lamb and its tables
+static GAttnArgs common_args(const void* q, const void* k, const void* v, long ld, int B, int heads, int N, float scale, const void* seed,
+                             int site, float drop_p, const float* lamb, int nb, int lamb_batch, const void* bandidx, const float* panels) {
+    GAttnArgs a{};
+    a.q = (const char*)q; a.k = (const char*)k; a.v = (const char*)v; a.ld = ld;
+    a.B = B; a.heads = heads; a.N = N; a.scale = scale;
+    a.seed = (const unsigned*)seed; a.site = (unsigned)site; a.thresh = drop_p > 0.f ? fw_drop_thresh(drop_p) : 0u;
+    a.inv_keep = drop_p > 0.f ? 1.0f / (1.0f - drop_p) : 1.0f;
+    a.lamb = lamb; a.nb = nb; a.lamb_batch = lamb_batch; a.bandidx = (const unsigned char*)bandidx; a.panels = panels;
+    return a;
+}
 }  // namespace
 
 extern "C" int fw_gattn_fwd(int dtype, const void* q, const void* k, const void* v, long ld, void* out, long ldo, float* lse, int B, int heads,
                             int N, float scale, const void* seed, int site, float drop_p, const float* lamb, int nb, int lamb_batch,
                             const void* bandidx, const float* panels, void* stream) {
-    GAttnArgs a{};
-    a.q = (const char*)q; a.k = (const char*)k; a.v = (const char*)v; a.ld = ld; a.out = (char*)out; a.ldo = ldo; a.lse = lse;
-    a.B = B; a.heads = heads; a.N = N; a.scale = scale;
-    a.seed = (const unsigned*)seed; a.site = (unsigned)site; a.thresh = drop_p > 0.f ? fw_drop_thresh(drop_p) : 0u;
-    a.inv_keep = drop_p > 0.f ? 1.0f / (1.0f - drop_p) : 1.0f;
-    a.lamb = lamb; a.nb = nb; a.lamb_batch = lamb_batch; a.bandidx = (const unsigned char*)bandidx; a.panels = panels;
+    GAttnArgs a = common_args(q, k, v, ld, B, heads, N, scale, seed, site, drop_p, lamb, nb, lamb_batch, bandidx, panels);
+    a.out = (char*)out; a.ldo = ldo; a.lse = lse;
     const int sz = dtype == FW_DT_BF16 ? 2 : 4;
     FW_CHECK_ARG(dtype == FW_DT_BF16 || dtype == FW_DT_F32);
     FW_CHECK_ARG(common_ok(a, dtype) && out && (ldo * sz) % 16 == 0 && (uintptr_t)out % 16 == 0 && drop_p >= 0.f && drop_p < 1.f);
@@ -1512,14 +1525,10 @@ extern "C" int fw_gattn_bwd(int dtype, const void* q, const void* k, const void*
                             const float* lse, float* dvec, void* dq, void* dk, void* dv, long ldd, int B, int heads, int N, float scale,
                             const void* seed, int site, float drop_p, const float* lamb, float* dlamb, int nb, int lamb_batch,
                             const void* bandidx, const float* panels, void* stream) {
-    GAttnArgs a{};
-    a.q = (const char*)q; a.k = (const char*)k; a.v = (const char*)v; a.ld = ld; a.o = (const char*)o; a.ldo = ldo;
+    GAttnArgs a = common_args(q, k, v, ld, B, heads, N, scale, seed, site, drop_p, lamb, nb, lamb_batch, bandidx, panels);
+    a.o = (const char*)o; a.ldo = ldo;
     a.dout = (const char*)dout; a.lddo = lddo; a.lse = const_cast<float*>(lse); a.dvec = dvec;
-    a.dq = (char*)dq; a.dk = (char*)dk; a.dv = (char*)dv; a.ldd = ldd;
-    a.B = B; a.heads = heads; a.N = N; a.scale = scale;
-    a.seed = (const unsigned*)seed; a.site = (unsigned)site; a.thresh = drop_p > 0.f ? fw_drop_thresh(drop_p) : 0u;
-    a.inv_keep = drop_p > 0.f ? 1.0f / (1.0f - drop_p) : 1.0f;
-    a.lamb = lamb; a.dlamb = dlamb; a.nb = nb; a.lamb_batch = lamb_batch; a.bandidx = (const unsigned char*)bandidx; a.panels = panels;
+    a.dq = (char*)dq; a.dk = (char*)dk; a.dv = (char*)dv; a.ldd = ldd; a.dlamb = dlamb;
     const int sz = dtype == FW_DT_BF16 ? 2 : 4;
     FW_CHECK_ARG(dtype == FW_DT_BF16 || dtype == FW_DT_F32);
     FW_CHECK_ARG(common_ok(a, dtype) && o && dout && dq && dk && dv && (lamb ? dlamb != nullptr : dvec != nullptr));
@@ -1529,81 +1538,31 @@ extern "C" int fw_gattn_bwd(int dtype, const void* q, const void* k, const void*
     return dtype == FW_DT_BF16 ? dispatch<bf16raw>(a, true, (hipStream_t)stream) : dispatch<float>(a, true, (hipStream_t)stream);
 }
 
-// <n>_bands with N x N masks at N = 256 (see fwair.h): probs -> row / col / out passes -> apply
+// <n>_bands with N x N masks at N = 256 / 576 / 1024 (see fwair.h): probs -> the filter passes of that N -> apply
 extern "C" int fw_gattn_bands_fwd(int dtype, const void* q, const void* k, const void* v, long ld, void* out, long ldo, float* lse, int B, int heads,
-                                  float scale, const void* seed, int site, float drop_p, const float* lamb, int nb, int lamb_batch,
+                                  int N, float scale, const void* seed, int site, float drop_p, const float* lamb, int nb, int lamb_batch,
                                   const void* bandidx, const float* panels, float* amap, float* work, void* stream) {
-    GAttnArgs a{};
-    a.q = (const char*)q; a.k = (const char*)k; a.v = (const char*)v; a.ld = ld; a.out = (char*)out; a.ldo = ldo; a.lse = lse;
-    a.B = B; a.heads = heads; a.N = 256; a.scale = scale;
-    a.seed = (const unsigned*)seed; a.site = (unsigned)site; a.thresh = drop_p > 0.f ? fw_drop_thresh(drop_p) : 0u;
-    a.inv_keep = drop_p > 0.f ? 1.0f / (1.0f - drop_p) : 1.0f;
-    a.lamb = lamb; a.nb = nb; a.lamb_batch = lamb_batch; a.bandidx = (const unsigned char*)bandidx; a.panels = panels; a.map = amap;
+    GAttnArgs a = common_args(q, k, v, ld, B, heads, N, scale, seed, site, drop_p, lamb, nb, lamb_batch, bandidx, panels);
+    a.out = (char*)out; a.ldo = ldo; a.lse = lse; a.map = amap;
     const int sz = dtype == FW_DT_BF16 ? 2 : 4;
     FW_CHECK_ARG(dtype == FW_DT_BF16 || dtype == FW_DT_F32);
     FW_CHECK_ARG(bands_ok(a, dtype) && out && amap && work && (ldo * sz) % 16 == 0 && drop_p >= 0.f && drop_p < 1.f);
     FW_CHECK_ARG(((uintptr_t)out | (uintptr_t)amap | (uintptr_t)work) % 16 == 0);
-    return dtype == FW_DT_BF16 ? bands_fwd<bf16raw>(a, work, (hipStream_t)stream) : bands_fwd<float>(a, work, (hipStream_t)stream);
+    return dtype == FW_DT_BF16 ? bands_dispatch<bf16raw>(a, work, false, (hipStream_t)stream) : bands_dispatch<float>(a, work, false, (hipStream_t)stream);
 }
 
 extern "C" int fw_gattn_bands_bwd(int dtype, const void* q, const void* k, const void* v, long ld, const void* dout, long lddo, const float* lse,
-                                  float* dvec, void* dq, void* dk, void* dv, long ldd, int B, int heads, float scale, const void* seed, int site,
-                                  float drop_p, const float* lamb, float* dlamb, int nb, int lamb_batch, const void* bandidx, const float* panels,
-                                  const float* amap, float* pmap, float* gmap, float* work, void* stream) {
-    GAttnArgs a{};
-    a.q = (const char*)q; a.k = (const char*)k; a.v = (const char*)v; a.ld = ld;
+                                  float* dvec, void* dq, void* dk, void* dv, long ldd, int B, int heads, int N, float scale, const void* seed,
+                                  int site, float drop_p, const float* lamb, float* dlamb, int nb, int lamb_batch, const void* bandidx,
+                                  const float* panels, const float* amap, float* pmap, float* gmap, float* work, void* stream) {
+    GAttnArgs a = common_args(q, k, v, ld, B, heads, N, scale, seed, site, drop_p, lamb, nb, lamb_batch, bandidx, panels);
     a.dout = (const char*)dout; a.lddo = lddo; a.lse = const_cast<float*>(lse); a.dvec = dvec;
-    a.dq = (char*)dq; a.dk = (char*)dk; a.dv = (char*)dv; a.ldd = ldd;
-    a.B = B; a.heads = heads; a.N = 256; a.scale = scale;
-    a.seed = (const unsigned*)seed; a.site = (unsigned)site; a.thresh = drop_p > 0.f ? fw_drop_thresh(drop_p) : 0u;
-    a.inv_keep = drop_p > 0.f ? 1.0f / (1.0f - drop_p) : 1.0f;
-    a.lamb = lamb; a.dlamb = dlamb; a.nb = nb; a.lamb_batch = lamb_batch; a.bandidx = (const unsigned char*)bandidx; a.panels = panels;
+    a.dq = (char*)dq; a.dk = (char*)dk; a.dv = (char*)dv; a.ldd = ldd; a.dlamb = dlamb;
     a.map = const_cast<float*>(amap); a.pmap = pmap; a.map2 = gmap;
     const int sz = dtype == FW_DT_BF16 ? 2 : 4;
     FW_CHECK_ARG(dtype == FW_DT_BF16 || dtype == FW_DT_F32);
     FW_CHECK_ARG(bands_ok(a, dtype) && dout && dq && dk && dv && dvec && dlamb && amap && pmap && gmap && work);
     FW_CHECK_ARG((lddo * sz) % 16 == 0 && (ldd * sz) % 16 == 0 && drop_p >= 0.f && drop_p < 1.f);
     FW_CHECK_ARG(((uintptr_t)dout | (uintptr_t)dq | (uintptr_t)dk | (uintptr_t)dv | (uintptr_t)amap | (uintptr_t)pmap | (uintptr_t)gmap | (uintptr_t)work) % 16 == 0);
-    return dtype == FW_DT_BF16 ? bands_bwd<bf16raw>(a, work, (hipStream_t)stream) : bands_bwd<float>(a, work, (hipStream_t)stream);
-}
-
-// <n>_bands with N x N masks at N = 576 / 1024 (see fwair.h): probs -> row / column / inverse / output passes -> apply
-static bool bandsn_ok(const GAttnArgs& a, int dtype) {
-    return (a.N == 576 || a.N == 1024) && bands_ok(a, dtype) && (long)a.B * a.heads <= 65535;
-}
-extern "C" int fw_gattn_bandsn_fwd(int dtype, const void* q, const void* k, const void* v, long ld, void* out, long ldo, float* lse, int B, int heads,
-                                   int N, float scale, const void* seed, int site, float drop_p, const float* lamb, int nb, int lamb_batch,
-                                   const void* bandidx, const float* panels, float* amap, float* work, void* stream) {
-    GAttnArgs a{};
-    a.q = (const char*)q; a.k = (const char*)k; a.v = (const char*)v; a.ld = ld; a.out = (char*)out; a.ldo = ldo; a.lse = lse;
-    a.B = B; a.heads = heads; a.N = N; a.scale = scale;
-    a.seed = (const unsigned*)seed; a.site = (unsigned)site; a.thresh = drop_p > 0.f ? fw_drop_thresh(drop_p) : 0u;
-    a.inv_keep = drop_p > 0.f ? 1.0f / (1.0f - drop_p) : 1.0f;
-    a.lamb = lamb; a.nb = nb; a.lamb_batch = lamb_batch; a.bandidx = (const unsigned char*)bandidx; a.panels = panels; a.map = amap;
-    const int sz = dtype == FW_DT_BF16 ? 2 : 4;
-    FW_CHECK_ARG(dtype == FW_DT_BF16 || dtype == FW_DT_F32);
-    FW_CHECK_ARG(bandsn_ok(a, dtype) && out && amap && work && (ldo * sz) % 16 == 0 && drop_p >= 0.f && drop_p < 1.f);
-    FW_CHECK_ARG(((uintptr_t)out | (uintptr_t)amap | (uintptr_t)work) % 16 == 0);
-    return dtype == FW_DT_BF16 ? bandsn_fwd<bf16raw>(a, work, (hipStream_t)stream) : bandsn_fwd<float>(a, work, (hipStream_t)stream);
-}
-
-extern "C" int fw_gattn_bandsn_bwd(int dtype, const void* q, const void* k, const void* v, long ld, const void* dout, long lddo, const float* lse,
-                                   float* dvec, void* dq, void* dk, void* dv, long ldd, int B, int heads, int N, float scale, const void* seed,
-                                   int site, float drop_p, const float* lamb, float* dlamb, int nb, int lamb_batch, const void* bandidx,
-                                   const float* panels, const float* amap, float* pmap, float* gmap, float* work, void* stream) {
-    GAttnArgs a{};
-    a.q = (const char*)q; a.k = (const char*)k; a.v = (const char*)v; a.ld = ld;
-    a.dout = (const char*)dout; a.lddo = lddo; a.lse = const_cast<float*>(lse); a.dvec = dvec;
-    a.dq = (char*)dq; a.dk = (char*)dk; a.dv = (char*)dv; a.ldd = ldd;
-    a.B = B; a.heads = heads; a.N = N; a.scale = scale;
-    a.seed = (const unsigned*)seed; a.site = (unsigned)site; a.thresh = drop_p > 0.f ? fw_drop_thresh(drop_p) : 0u;
-    a.inv_keep = drop_p > 0.f ? 1.0f / (1.0f - drop_p) : 1.0f;
-    a.lamb = lamb; a.dlamb = dlamb; a.nb = nb; a.lamb_batch = lamb_batch; a.bandidx = (const unsigned char*)bandidx; a.panels = panels;
-    a.map = const_cast<float*>(amap); a.pmap = pmap; a.map2 = gmap;
-    const int sz = dtype == FW_DT_BF16 ? 2 : 4;
-    FW_CHECK_ARG(dtype == FW_DT_BF16 || dtype == FW_DT_F32);
-    FW_CHECK_ARG(bandsn_ok(a, dtype) && dout && dq && dk && dv && dvec && dlamb && amap && pmap && gmap && work);
-    FW_CHECK_ARG((lddo * sz) % 16 == 0 && (ldd * sz) % 16 == 0 && drop_p >= 0.f && drop_p < 1.f);
-    FW_CHECK_ARG(((uintptr_t)dout | (uintptr_t)dq | (uintptr_t)dk | (uintptr_t)dv | (uintptr_t)amap | (uintptr_t)pmap | (uintptr_t)gmap | (uintptr_t)work) % 16 == 0);
-    return dtype == FW_DT_BF16 ? bandsn_bwd<bf16raw>(a, work, (hipStream_t)stream) : bandsn_bwd<float>(a, work, (hipStream_t)stream);
+    return dtype == FW_DT_BF16 ? bands_dispatch<bf16raw>(a, work, true, (hipStream_t)stream) : bands_dispatch<float>(a, work, true, (hipStream_t)stream);
 }

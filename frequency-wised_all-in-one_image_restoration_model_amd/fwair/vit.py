@@ -19,7 +19,7 @@ are dim_head x dim_head, :56,60); at any other size both raise.  `opt.vit_band_g
 map instead (N x N; identical at N = 64): at N = 256 'DC' then runs as an affine map of the softmax (csrc/fw_gattn.hip dc_coef)
 and '<n>_bands' as a multi-pass 256x256 2-D DFT on the f32 MFMA between a probabilities and an apply kernel (fw_gattn_bands_fwd / bwd).
 At N = 576 / 1024 (384x384 / 512x512 inputs) 'DC' is the same affine map inside the streaming forward and '<n>_bands' the LDS-free
-tiled N x N DFT passes (fw_gattn_bandsn_fwd / bwd); a band re-weighting at any other streaming N has no kernel and raises.
+tiled N x N DFT passes behind the same entry pair; a band re-weighting at any other streaming N has no kernel and raises.
 """
 import math
 import zlib
@@ -166,14 +166,9 @@ class GlobalAttnFn(torch.autograd.Function):
         amap = None
         if N != 64 and lam is not None and bidx is not None:             # <n>_bands on the N x N grid: the map leaves the workgroup
             amap = torch.empty((B * heads, N, N), dtype=torch.float32, device=qkv.device)          # P + filter(P): kept for backward
-            if N == 256:
-                work = torch.empty((B * heads, 2, N, N), dtype=torch.float32, device=qkv.device)
-                call('fw_gattn_bands_fwd', dt(qkv.dtype), qkv, qkv[:, inner:], qkv[:, 2 * inner:], qkv.stride(0), out, out.stride(0), lse, B,
-                     heads, 64 ** -0.5, seed, site, float(p), lam, nb, lb, bidx, panels, amap, work)
-            else:                                                        # N = 576 / 1024: the tiled passes
-                work = torch.empty((4, B * heads, N, N), dtype=torch.float32, device=qkv.device)
-                call('fw_gattn_bandsn_fwd', dt(qkv.dtype), qkv, qkv[:, inner:], qkv[:, 2 * inner:], qkv.stride(0), out, out.stride(0), lse, B,
-                     heads, N, 64 ** -0.5, seed, site, float(p), lam, nb, lb, bidx, panels, amap, work)
+            work = torch.empty((2 if N == 256 else 4, B * heads, N, N), dtype=torch.float32, device=qkv.device)     # fwair.h: planes per map
+            call('fw_gattn_bands_fwd', dt(qkv.dtype), qkv, qkv[:, inner:], qkv[:, 2 * inner:], qkv.stride(0), out, out.stride(0), lse, B,
+                 heads, N, 64 ** -0.5, seed, site, float(p), lam, nb, lb, bidx, panels, amap, work)
         else:
             call('fw_gattn_fwd', dt(qkv.dtype), qkv, qkv[:, inner:], qkv[:, 2 * inner:], qkv.stride(0), out, out.stride(0), lse, B, heads, N,
                  64 ** -0.5, seed, site, float(p), lam, nb, lb, bidx, panels)
@@ -199,16 +194,10 @@ class GlobalAttnFn(torch.autograd.Function):
         nb, lb = (lam.shape[0], lam.shape[1]) if lam is not None else (0, 1)
         if amap is not None:
             pmap, gmap = torch.empty_like(amap), torch.empty_like(amap)
-            if N == 256:
-                work = torch.empty((2, B * heads, 2, N, N), dtype=torch.float32, device=qkv.device)
-                call('fw_gattn_bands_bwd', dt(qkv.dtype), qkv, qkv[:, inner:], qkv[:, 2 * inner:], qkv.stride(0), dout, dout.stride(0), lse, dvec,
-                     dqkv, dqkv[:, inner:], dqkv[:, 2 * inner:], dqkv.stride(0), B, heads, 64 ** -0.5, seed, site, float(p), lam, dlam, nb, lb,
-                     bidx, panels, amap, pmap, gmap, work)
-            else:
-                work = torch.empty((6, B * heads, N, N), dtype=torch.float32, device=qkv.device)
-                call('fw_gattn_bandsn_bwd', dt(qkv.dtype), qkv, qkv[:, inner:], qkv[:, 2 * inner:], qkv.stride(0), dout, dout.stride(0), lse,
-                     dvec, dqkv, dqkv[:, inner:], dqkv[:, 2 * inner:], dqkv.stride(0), B, heads, N, 64 ** -0.5, seed, site, float(p), lam,
-                     dlam, nb, lb, bidx, panels, amap, pmap, gmap, work)
+            work = torch.empty((4 if N == 256 else 6, B * heads, N, N), dtype=torch.float32, device=qkv.device)
+            call('fw_gattn_bands_bwd', dt(qkv.dtype), qkv, qkv[:, inner:], qkv[:, 2 * inner:], qkv.stride(0), dout, dout.stride(0), lse, dvec,
+                 dqkv, dqkv[:, inner:], dqkv[:, 2 * inner:], dqkv.stride(0), B, heads, N, 64 ** -0.5, seed, site, float(p), lam, dlam, nb, lb,
+                 bidx, panels, amap, pmap, gmap, work)
             return dqkv, rl, None
         call('fw_gattn_bwd', dt(qkv.dtype), qkv, qkv[:, inner:], qkv[:, 2 * inner:], qkv.stride(0), out, out.stride(0), dout, dout.stride(0),
              lse, dvec, dqkv, dqkv[:, inner:], dqkv[:, 2 * inner:], dqkv.stride(0), B, heads, N, 64 ** -0.5, seed, site, float(p),

@@ -353,8 +353,8 @@ int fw_small_linear_bwd(const float* dy, const float* y, const float* x, const f
  * N in {256, 576, 1024} with lamb: only the 'DC' decomposition on the N x N grid (encoder_ViT.py:59-60 'frequency_decompose_dc' with
  * masks sized by the map): nb = 2, bandidx = panels = NULL; band 0 is the mean of the map, 1 / N for softmax rows, so the kernel
  * evaluates attn' = (1 + lamb[1]) attn + (lamb[0] - lamb[1]) / N without a transform (at 576 / 1024 the streaming forward keeps a
- * second, unrescaled accumulator for the constant term); `<n>_bands` is fw_gattn_bands_fwd / bwd at N = 256 and fw_gattn_bandsn_fwd /
- * bwd at N = 576 / 1024, which require the tables.  Every other lamb / N combination (any lamb at N not in {64, 256, 576, 1024}
+ * second, unrescaled accumulator for the constant term); `<n>_bands` is fw_gattn_bands_fwd / bwd at N = 256 / 576 /
+ * 1024, which require the tables.  Every other lamb / N combination (any lamb at N not in {64, 256, 576, 1024}
  * included) and every other N is an argument error. */
 int fw_gattn_fwd(int dtype, const void* q, const void* k, const void* v, long ld, void* out, long ldo, float* lse, int B, int heads, int N,
                  float scale, const void* seed, int site, float drop_p, const float* lamb, int nb, int lamb_batch, const void* bandidx,
@@ -366,39 +366,28 @@ int fw_gattn_bwd(int dtype, const void* q, const void* k, const void* v, long ld
                  const float* lse, float* dvec, void* dq, void* dk, void* dv, long ldd, int B, int heads, int N, float scale,
                  const void* seed, int site, float drop_p, const float* lamb, float* dlamb, int nb, int lamb_batch, const void* bandidx,
                  const float* panels, void* stream);
-/* The same attention with `<n>_bands` masks sized by the map (N = 256 only; encoder_ViT.py:55-56,85-92 with FrequencyDecompose(
- * 'frequency_decompose', 1/nb, N, N) in place of the dim_head-sized masks that do not fit a 256x256 map).  bandidx: u8 [256][256]
- * (symmetric), panels: f32 cos[256][256], sin[256][256] of 2 pi u i / 256.  The map leaves the workgroup: a probabilities kernel,
- * a row / column / output pass of a batched 256x256 2-D DFT on the f32 MFMA, and an apply kernel (Dropout, attn v).
- * amap: f32 [B*heads][256][256], receives attn' = attn + filter(attn) (before Dropout) and is what the backward pass needs;
- * work: f32 [B*heads][2][256][256] scratch. */
+/* The same attention with `<n>_bands` masks sized by the map, N in {256, 576, 1024} (256x256 / 384x384 / 512x512 inputs) -- any other
+ * N is an argument error; encoder_ViT.py:55-56,85-92 with FrequencyDecompose('frequency_decompose', 1/nb, N, N) in place of the
+ * dim_head-sized masks.  bandidx: u8 [N][N] (symmetric); panels: f32 [2][N][N], cos then sin of 2 pi u i / N.  The map leaves the
+ * workgroup: a probabilities kernel, the passes of a batched N x N 2-D DFT on the f32 MFMA (attn += Re IDFT2(W . DFT2(attn))), and an
+ * apply kernel (Dropout, attn v).
+ *   N = 256: row / column / output passes through LDS.
+ *   N = 576 / 1024: four LDS-free 64x64-tile passes (row, column with the lamb weights, inverse column, output) after a probabilities
+ *     kernel that walks the key tiles twice (online lse, then attn = exp(s scale - lse) as f32); B * heads <= 65535.
+ * amap: f32 [B*heads][N][N], receives attn' = attn + filter(attn) (before Dropout) and is what the backward pass needs.
+ * work: scratch of W * B*heads * N * N floats, W planes per map:   forward  W = 2 at N = 256, 4 at N = 576 / 1024
+ *                                                                  backward W = 4 at N = 256, 6 at N = 576 / 1024
+ *   (the transform planes, and in the backward pass the spectrum of the probabilities that lamb is differentiated against). */
 int fw_gattn_bands_fwd(int dtype, const void* q, const void* k, const void* v, long ld, void* out, long ldo, float* lse, int B, int heads,
-                       float scale, const void* seed, int site, float drop_p, const float* lamb, int nb, int lamb_batch, const void* bandidx,
-                       const float* panels, float* amap, float* work, void* stream);
-/* amap: as the forward pass left it; pmap, gmap: f32 [B*heads][256][256] scratch (the probabilities rebuilt from lse; the map
- * gradient, filtered in place: the filter is self-adjoint); work: f32 [2][B*heads][2][256][256] scratch; dvec: f32 [B][heads][256]
- * scratch; dlamb accumulated: sum over band of Re(X_P conj(X_G)) / N^2, one atomic per workgroup and band. */
+                       int N, float scale, const void* seed, int site, float drop_p, const float* lamb, int nb, int lamb_batch,
+                       const void* bandidx, const float* panels, float* amap, float* work, void* stream);
+/* amap: as the forward pass left it; pmap, gmap: f32 [B*heads][N][N] scratch (the probabilities rebuilt from lse; the map gradient,
+ * filtered in place: the filter is self-adjoint); work: as above; dvec: f32 [B][heads][N] scratch; dlamb accumulated: sum over band
+ * of Re(X_P conj(X_G)) / N^2, one atomic per workgroup and band. */
 int fw_gattn_bands_bwd(int dtype, const void* q, const void* k, const void* v, long ld, const void* dout, long lddo, const float* lse,
-                       float* dvec, void* dq, void* dk, void* dv, long ldd, int B, int heads, float scale, const void* seed, int site,
+                       float* dvec, void* dq, void* dk, void* dv, long ldd, int B, int heads, int N, float scale, const void* seed, int site,
                        float drop_p, const float* lamb, float* dlamb, int nb, int lamb_batch, const void* bandidx, const float* panels,
                        const float* amap, float* pmap, float* gmap, float* work, void* stream);
-/* `<n>_bands` masks sized by the map at N = 576 (384x384 inputs) and N = 1024 (512x512) -- any other N is an argument error;
- * encoder_ViT.py:55-56,85-92 with FrequencyDecompose('frequency_decompose', 1/nb, N, N).  The arguments of fw_gattn_bands_fwd plus
- * N; bandidx: u8 [N][N] (symmetric), panels: f32 cos[N][N], sin[N][N] of 2 pi u i / N.  A probabilities kernel (two walks over the
- * key tiles: online lse, then attn = exp(s scale - lse) as f32), four LDS-free 64x64-tile passes of a batched N x N 2-D DFT on the
- * f32 MFMA (row, column with the lamb weights, inverse column, output: attn += Re IDFT2(W . DFT2(attn))), and an apply kernel
- * (Dropout, attn v).  amap: f32 [B*heads][N][N], kept for the backward pass; work: 4 * B*heads * N * N floats of scratch
- * ([4][B*heads][N][N]); B * heads <= 65535. */
-int fw_gattn_bandsn_fwd(int dtype, const void* q, const void* k, const void* v, long ld, void* out, long ldo, float* lse, int B, int heads,
-                        int N, float scale, const void* seed, int site, float drop_p, const float* lamb, int nb, int lamb_batch,
-                        const void* bandidx, const float* panels, float* amap, float* work, void* stream);
-/* The arguments of fw_gattn_bands_bwd plus N (576 | 1024).  pmap, gmap: f32 [B*heads][N][N] scratch; work: 6 * B*heads * N * N floats
- * of scratch ([6][B*heads][N][N]: the two pairs of transform planes of the forward, and the spectrum of the probabilities that
- * encoder_ViT.py:85-92 differentiates lamb against); dvec: f32 [B][heads][N]; dlamb accumulated, one atomic per workgroup and band. */
-int fw_gattn_bandsn_bwd(int dtype, const void* q, const void* k, const void* v, long ld, const void* dout, long lddo, const float* lse,
-                        float* dvec, void* dq, void* dk, void* dv, long ldd, int B, int heads, int N, float scale, const void* seed,
-                        int site, float drop_p, const float* lamb, float* dlamb, int nb, int lamb_batch, const void* bandidx,
-                        const float* panels, const float* amap, float* pmap, float* gmap, float* work, void* stream);
 /* nn.Dropout call sites of the ViT (encoder_ViT.py:31,33,73,158,189) with the same counter-based masks.  mode 0: y = drop(x) (f32);
  * 1: y = res + drop(x) (f32); 2: y = drop(gelu(x)) (T); 3: y = drop(x) * gelu'(aux) (T, backward of 2); 4: y = drop(x + aux[i % period])
  * (f32: pos_embedding add + emb dropout, encoder_ViT.py:187-189).  n = elements of the contiguous tensor; p = 0: identity masks. */

@@ -1,7 +1,8 @@
 """What tests/golden/make_spec_bits.py and tests/test_spec_bits_gpu.py share: the cases whose output BYTES are pinned (fixture
 spec_bits.json, SHA-256 per case) for the entries built on the shared tile-contraction chunk (DftChunk, csrc/fw_common.h), whose order of
 accumulation is a contract -- fw_band_stats, fw_band_split (csrc/fw_spec.hip) and fw_dft2t_fwd / fw_dft2t_bands /
-fw_dft2t_decompose (csrc/fw_dft.hip).
+fw_dft2t_decompose (csrc/fw_dft.hip) -- and, group gattn_bands, for the attention-map band filter's entry pair fw_gattn_bands_fwd / bwd
+(csrc/fw_gattn.hip) where its bytes do not depend on the tiled passes' order of accumulation (see gattn_bands()).
 
 Every input comes from numpy.random.RandomState's uniform and integer draws (and band_split_cases.random_ring, integer draws of a
 seeded torch generator): no libm call of the host takes part, so the inputs are the same bytes wherever the test runs.  That goes
@@ -23,10 +24,11 @@ from fwair.lib import call
 
 DEV = 'cuda'
 SHAPES = [(8, 8), (9, 8), (63, 65), (65, 130)]
-GROUPS = ['band_stats', 'band_split', 'dft2t']
+GROUPS = ['band_stats', 'band_split', 'dft2t', 'gattn_bands']
 STATS_NIMG, STATS_NB = 3, 5
 SPLIT_NIMG, SPLIT_NBANDS = 2, (1, 2, 3, 4, 5)           # every spec_coli_kernel<NB>; 5 bands: a second group with b0 = 4
 DFT_N, DFT_NIMG, DFT_NB = 192, 2, 3
+GATTN_B, GATTN_HEADS, GATTN_NB, GATTN_P, GATTN_SEED, GATTN_SITE = 1, 2, 3, 0.1, 777, 41
 
 
 def toolchain():
@@ -64,7 +66,10 @@ def sources(h, w, n):
 
 
 def sha(t):
-    return hashlib.sha256(t.detach().cpu().contiguous().numpy().tobytes()).hexdigest()
+    t = t.detach().cpu().contiguous()
+    if t.dtype == torch.bfloat16:
+        t = t.view(torch.int16)                                                 # numpy has no bf16: the same bytes
+    return hashlib.sha256(t.numpy().tobytes()).hexdigest()
 
 
 def band_stats():
@@ -120,7 +125,49 @@ def dft2t():
     return out
 
 
+def gattn_bands():
+    """out and dqkv of vit.GlobalAttnFn with '<n>_bands' on the N x N map (dlamb is summed with f32 atomics across workgroups: its
+    bytes are not reproducible, it stays under the tolerance tests).
+      N = 256, lamb != 0: a seeded symmetric band table and seeded uniform [2][256][256] panels -- the 256 kernels, the entry pair,
+        the argument filling, the row-dot kernel.
+      N = 576 (the smallest tiled N; nine tiles a side), lamb = 0, the tables of _spectral_tables: the filter adds +-0 to a map of
+        non-negative probabilities and to G, whose dropped entries are +0, so out and dqkv depend neither on the panels nor on the
+        order of accumulation of the tiled passes -- the probabilities, apply, rows, row-dot and dQ / dK / dV kernels and the
+        plumbing of the tiled path."""
+    from fwair import functional as Fn
+    from fwair import vit as V
+    B, heads, p, nb = GATTN_B, GATTN_HEADS, GATTN_P, GATTN_NB
+    out = {}
+    for N in (256, 576):
+        if N == 256:
+            r = _rs('specbits.gattn.bidx').randint(0, nb, (N, N)).astype(np.uint8)
+            bidx = torch.from_numpy(np.triu(r) + np.triu(r, 1).T)
+            assert bool((bidx == bidx.t()).all()) and int(bidx.max()) < nb
+            spec = (bidx.to(DEV), uniform('specbits.gattn.panels', (2, N, N)).to(DEV))
+            lamb0 = uniform('specbits.gattn.lamb', (nb, 1, heads), -0.5, 0.5)
+        else:
+            spec = V._spectral_tables('bands', nb, torch.device(DEV), n=N)
+            lamb0 = torch.zeros(nb, 1, heads)
+        for name, dtype in (('fp32', torch.float32), ('bf16', torch.bfloat16)):
+            qkv = uniform(f'specbits.gattn.qkv.{N}', (B * N, 3 * heads * 64)).to(dtype).to(DEV).requires_grad_(True)
+            dout = uniform(f'specbits.gattn.dout.{N}', (B * N, heads * 64), -0.5, 0.5).to(dtype).to(DEV)
+            lamb = torch.nn.Parameter(lamb0.to(DEV))
+            direct = Fn.config.direct_grads
+            Fn.config.direct_grads = False
+            Fn.set_dropout_seed(GATTN_SEED, DEV, frozen=True)
+            try:
+                res = V.GlobalAttnFn.apply(qkv, lamb, (B, N, heads, p, GATTN_SITE, spec))
+                res.backward(dout)
+                torch.cuda.synchronize()
+            finally:
+                Fn.set_dropout_seed(1, DEV, frozen=False)
+                Fn.config.direct_grads = direct
+            assert bool(torch.isfinite(lamb.grad).all())
+            out[f'N{N}|{name}|out'], out[f'N{N}|{name}|dqkv'] = sha(res), sha(qkv.grad)
+    return out
+
+
 def digests(group):
-    res = {'band_stats': band_stats, 'band_split': band_split, 'dft2t': dft2t}[group]()
+    res = {'band_stats': band_stats, 'band_split': band_split, 'dft2t': dft2t, 'gattn_bands': gattn_bands}[group]()
     torch.cuda.synchronize()
     return res

@@ -3,7 +3,8 @@ tests/spec_bits_cases.py against tests/golden/spec_bits.json, which tests/golden
 the fixture names.  Equality, never a tolerance: dft_pass_kernel of csrc/fw_dft.hip and the contracting kernels of csrc/fw_spec.hip
 stand on one chunk type (csrc/fw_common.h, DftChunk) whose order of MFMAs per accumulator is a contract; a digest that
 differs means an operation changed place -- the MFMA order, where a band's weight multiplies the fragment, the `s +=` of the band
-reduction, where the scale is applied.  The digests hold for one compiler: under another `hipcc --version` the tests skip and say so
+reduction, where the scale is applied.  Group gattn_bands pins out and dqkv of the attention-map band filter (fw_gattn_bands_fwd /
+bwd through vit.GlobalAttnFn) at N = 256 and, with lamb = 0, at N = 576 (spec_bits_cases.gattn_bands).  The digests hold for one compiler: under another `hipcc --version` the tests skip and say so
 (a hipcc that cannot be run at all is an error)."""
 import json
 import os
@@ -25,7 +26,7 @@ def pinned():
     return fx['digests']
 
 
-@pytest.mark.parametrize('group', ['band_stats', 'band_split', 'dft2t'])
+@pytest.mark.parametrize('group', ['band_stats', 'band_split', 'dft2t', 'gattn_bands'])
 def test_output_bytes(pinned, group):
     import spec_bits_cases as PC
     got, want = PC.digests(group), pinned[group]

@@ -1,6 +1,6 @@
 """GPU parity of `--vit_band_grid tokens` at N = 576 and N = 1024 tokens (384x384 / 512x512 inputs): the ViT's band re-weighting with
 masks sized by the attention map on the streaming sizes.  '<n>_bands' runs the tiled N x N DFT filter between a probabilities and an
-apply kernel (csrc/fw_gattn.hip bandsn_pass_kernel, fw_gattn_bandsn_fwd / bwd), 'DC' the affine form inside the streaming forward
+apply kernel (csrc/fw_gattn.hip bandsn_pass_kernel, fw_gattn_bands_fwd / bwd), 'DC' the affine form inside the streaming forward
 (gattn_stream_fwd_kernel<T, true>, gattn_dc_rows_kernel / gattn_dc_bwd_kernel with a run-time tile count).
 
   1  kernel against the f64 FFT statement of encoder_ViT.py:85-92 with N x N masks (convnets_oracle.attn_band_masks(type, N)) and the
@@ -206,11 +206,11 @@ def test_padded_layout(dt, ftype):
         amap = torch.full((maps * N * N + 64,), 7.0, dtype=torch.float32, device=DEV)
         pmap, gmap = torch.full_like(amap, 7.0), torch.full_like(amap, 7.0)
         work = torch.full((6 * maps * N * N + 64,), 7.0, dtype=torch.float32, device=DEV)
-        call('fw_gattn_bandsn_fwd', dtc(dtype), q, k, v, buf.stride(0), out, out.stride(0), lse, B, HEADS, N, 64 ** -0.5, seed, SITE, p,
+        call('fw_gattn_bands_fwd', dtc(dtype), q, k, v, buf.stride(0), out, out.stride(0), lse, B, HEADS, N, 64 ** -0.5, seed, SITE, p,
              lam, nb, 1, bidx, panels, amap, work)
         torch.cuda.synchronize()
         assert bool((work[4 * maps * N * N:] == 7.0).all()), 'the forward wrote past its 4 * maps * N * N floats of work'
-        call('fw_gattn_bandsn_bwd', dtc(dtype), q, k, v, buf.stride(0), dob, dob.stride(0), lse, dvec, dqkv, dqkv[:, inner:],
+        call('fw_gattn_bands_bwd', dtc(dtype), q, k, v, buf.stride(0), dob, dob.stride(0), lse, dvec, dqkv, dqkv[:, inner:],
              dqkv[:, 2 * inner:], dqkv.stride(0), B, HEADS, N, 64 ** -0.5, seed, SITE, p, lam, dlam, nb, 1, bidx, panels, amap, pmap,
              gmap, work)
         torch.cuda.synchronize()
@@ -267,11 +267,11 @@ def test_domain_of_the_library():
         maps = [torch.empty((HEADS, N, N), device=DEV) for _ in range(3)]
         work = torch.empty((6, HEADS, N, N), device=DEV)
         with pytest.raises(RuntimeError, match='argument check'):
-            call('fw_gattn_bandsn_fwd', 0, qkv, qkv[:, inner:], qkv[:, 2 * inner:], qkv.stride(0), out, out.stride(0), lse, 1, HEADS, N,
+            call('fw_gattn_bands_fwd', 0, qkv, qkv[:, inner:], qkv[:, 2 * inner:], qkv.stride(0), out, out.stride(0), lse, 1, HEADS, N,
                  64 ** -0.5, None, SITE, 0.0, lamb, 3, 1, bidx, panels, maps[0], work)
         dqkv, dvec, dlamb = torch.empty_like(qkv), torch.empty_like(lse), torch.zeros_like(lamb)
         with pytest.raises(RuntimeError, match='argument check'):
-            call('fw_gattn_bandsn_bwd', 0, qkv, qkv[:, inner:], qkv[:, 2 * inner:], qkv.stride(0), out, out.stride(0), lse, dvec, dqkv,
+            call('fw_gattn_bands_bwd', 0, qkv, qkv[:, inner:], qkv[:, 2 * inner:], qkv.stride(0), out, out.stride(0), lse, dvec, dqkv,
                  dqkv[:, inner:], dqkv[:, 2 * inner:], dqkv.stride(0), 1, HEADS, N, 64 ** -0.5, None, SITE, 0.0, lamb, dlamb, 3, 1, bidx,
                  panels, maps[0], maps[1], maps[2], work)
     dc = torch.zeros((2, 1, HEADS), device=DEV)

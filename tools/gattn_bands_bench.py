@@ -3,7 +3,7 @@
 us per forward / backward launch group for lamb = None, 'DC' (affine form) and '3_bands' (row / column / output DFT passes), bf16,
 at B * heads = 48 and 192, and the f32-MFMA rate of the filter (0.40 GFLOP per map forward: 2 + 4 + 4 + 2 real 256^3 products;
 backward 0.60: one more row pass and half a column pass for the spectrum of P).   python tools/gattn_bands_bench.py [out.json]
-`--tokens 576` / `--tokens 1024` (384x384 / 512x512 inputs) time the tiled passes of fw_gattn_bandsn_fwd / bwd the same way, at
+`--tokens 576` / `--tokens 1024` (384x384 / 512x512 inputs) time the tiled passes behind the same entry pair (fw_gattn_bands_fwd / bwd) the same way, at
 B * heads = 24 and 96 / 12 and 48 maps, with 12 N^3 (forward) and 18 N^3 (backward) multiply-adds per map."""
 import argparse
 import json
