@@ -5,6 +5,9 @@
 //     one of the 7 flip / rotation modes per crop (utils/image_utils.py:133-182 `random_augmentation`), ToTensor scaling (:134-135).
 //     No host round trip: crop origins and modes come from one device tensor of random integers, the noise is counter-based
 //     (fw_common.h hash -> Box-Muller), so both crops see the same noisy image although that image is never materialised.
+//   * fw_train_batch_synth -- the same batch with rain, haze and motion blur synthesised per slot in the launch (integer arithmetic on two
+//     small tables, fresh per batch, one degraded image for both crops of a sample); fw_synth_image writes that image out for inspection.
+//     Stand-ins for the paired training sets, not models of them.
 //   * fw_tile_gather / fw_tile_blend -- test.py:47-71: cut a test image into tiles (stride = tile, last tile flush with the border),
 //     and average the RESTORED tiles over their overlap (gather form: at most two tiles per axis cover a pixel; no atomics).
 //   * fw_ssim7 -- structural similarity as utils/val_utils.py:50-66 calls it (skimage.metrics.structural_similarity defaults: 7x7
@@ -502,6 +505,136 @@ __global__ void restore_blend_kernel(const long long* __restrict__ itab, const l
     acc = block_sum(acc, red);
     if (threadIdx.x == 0) atomicAdd(sse + im, acc);
 }
+
+// ---- training batch with rain, haze and motion blur synthesised in the launch -------------------------------------------------------
+// prm[b] = {code, p1, p2, p3, p4, 0, 0, 0}: code 0 = train_batch_kernel's rule (degraded pointer, or noise, or clean); 1 rain {angle a,
+// length L, density16, strength S8}; 2 haze {beta index j, airlight A8}; 3 motion blur {angle a, odd tap count n}.  ray: int8
+// [32][32][2] = (dy, dx) of step t along angle a; hazet: uint16 [16][256] transmission * 65535 (fwair/augment.py builds both in f64).
+// Every degraded value is integer arithmetic on the SOURCE pixel of the full image, so the two crops of a slot, whatever their modes,
+// cut one degraded image that is never stored.  Parameters are clamped to the tables' extent: a malformed record reads nothing outside.
+struct SynthSlot {
+    int code, a, n, dens, s8;                         // n: taps (blur), length (rain), airlight (haze); a: angle or beta index
+};
+FW_DEV SynthSlot synth_slot(const int* __restrict__ p) {
+    SynthSlot s;
+    s.code = p[0];
+    s.a = s.code == 2 ? (p[1] & 15) : (p[1] & 31);
+    if (s.code == 1) s.n = min(max(p[2], 1), 32);
+    else if (s.code == 2) s.n = min(max(p[2], 0), 255);
+    else s.n = (min(max(p[2], 1), 25) - 1) | 1;       // odd, 1..25
+    s.dens = min(max(p[3], 0), 65536);
+    s.s8 = min(max(p[4], 0), 255);
+    return s;
+}
+// steps 0..31 of the slot's angle into LDS (dy[t], dx[t]); every thread of the block calls it
+FW_DEV void stage_ray(const signed char* __restrict__ ray, int a, int* sdy, int* sdx) {
+    if (threadIdx.x < 32) {
+        sdy[threadIdx.x] = ray[(a * 32 + threadIdx.x) * 2 + 0];
+        sdx[threadIdx.x] = ray[(a * 32 + threadIdx.x) * 2 + 1];
+    }
+    __syncthreads();
+}
+// degraded values d[0..2] (0..255) of source pixel (y, x) of the full image for codes 1..3; g[c] = clean[c][y][x]
+FW_DEV void synth_px(const SynthSlot& s, const unsigned char* __restrict__ clean, int H, int W, int y, int x, const int* g, unsigned key,
+                     const int* sdy, const int* sdx, const unsigned short* __restrict__ hazet, int* d) {
+    if (s.code == 1) {                                                               // rain: the brightest streak that reaches (y, x)
+        int m = 0;
+        for (int t = 0; t < s.n; ++t) {
+            const int qy = y - sdy[t], qx = x - sdx[t];
+            if ((unsigned)qy >= (unsigned)H || (unsigned)qx >= (unsigned)W) continue;
+            const unsigned h = fw_hash32((unsigned)(qy * W + qx) ^ key);             // one hash per pixel: the same streaks in all channels
+            if ((int)(h & 0xFFFFu) < s.dens) m = max(m, (int)(128u + ((h >> 16) & 127u)) * (s.n - t));
+        }
+        const int add = m * s.s8 / (256 * s.n);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) d[c] = min(255, g[c] + add);
+    } else if (s.code == 2) {                                                        // haze: depth = a vertical ramp, far at the top
+        const int k = H > 1 ? y * 255 / (H - 1) : 0;
+        const int T = hazet[s.a * 256 + k];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) d[c] = (g[c] * T + s.n * (65535 - T) + 32767) / 65535;
+    } else {                                                                         // motion blur: n taps along the ray, clamped at the IMAGE border
+        int sum[3] = {g[0], g[1], g[2]};
+        const long plane = (long)H * W;
+        for (int t = 1; t <= (s.n - 1) / 2; ++t) {
+            const int dy = sdy[t], dx = sdx[t];
+            const long pa = (long)min(max(y + dy, 0), H - 1) * W + min(max(x + dx, 0), W - 1);
+            const long pb = (long)min(max(y - dy, 0), H - 1) * W + min(max(x - dx, 0), W - 1);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) sum[c] += (int)clean[c * plane + pa] + (int)clean[c * plane + pb];
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) d[c] = (2 * sum[c] + s.n) / (2 * s.n);
+    }
+}
+// One (slot, view) per blockIdx.y; a thread owns an output pixel in all three channels, so the rain hashes and the blur offsets are
+// evaluated once per pixel.  Stores run along ox in every mode.
+__global__ void train_batch_synth_kernel(const long long* __restrict__ tab, const int* __restrict__ rnd, const float* __restrict__ sigma,
+                                         const int* __restrict__ prm, const signed char* __restrict__ ray,
+                                         const unsigned short* __restrict__ hazet, const unsigned* __restrict__ seed, unsigned site,
+                                         float* __restrict__ d1, float* __restrict__ d2, float* __restrict__ c1, float* __restrict__ c2, int S) {
+    __shared__ int sdy[32], sdx[32];
+    const int b = blockIdx.y >> 1, v = blockIdx.y & 1;
+    const unsigned char* clean = reinterpret_cast<const unsigned char*>(tab[b * 4 + 0]);
+    const unsigned char* degr = reinterpret_cast<const unsigned char*>(tab[b * 4 + 1]);
+    const int H = (int)tab[b * 4 + 2], W = (int)tab[b * 4 + 3];
+    if (!clean || H < S || W < S) return;                                            // a malformed row reads and writes nothing
+    const SynthSlot s = synth_slot(prm + b * 8);
+    const bool synth = s.code >= 1 && s.code <= 3;
+    if (synth && s.code != 2) stage_ray(ray, s.a, sdy, sdx);                         // uniform in the block
+    const int* r = rnd + b * 6 + v * 3;
+    const int y0 = (int)((unsigned)r[0] % (unsigned)(H - S + 1)), x0 = (int)((unsigned)r[1] % (unsigned)(W - S + 1));
+    const int mode = 1 + (int)((unsigned)r[2] % 7u);
+    const unsigned key = fw_site_key(seed[0], site + (unsigned)b);
+    const float sg = sigma[b];
+    const long plane = (long)H * W;
+    float* dout = (v ? d2 : d1) + (long)b * 3 * S * S;
+    float* cout = (v ? c2 : c1) + (long)b * 3 * S * S;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < S * S; i += gridDim.x * blockDim.x) {
+        const int ox = i % S, oy = i / S;
+        int py, px;
+        mode_preimage(mode, S, oy, ox, py, px);
+        const int y = y0 + py, x = x0 + px;
+        const long pi = (long)y * W + x;
+        int g[3], d[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) g[c] = clean[c * plane + pi];
+        if (synth) synth_px(s, clean, H, W, y, x, g, key, sdy, sdx, hazet, d);
+        else {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                if (degr) d[c] = degr[c * plane + pi];
+                else if (sg > 0.f) d[c] = (int)noisy_u8((float)g[c], sg, key, c * plane + pi);
+                else d[c] = g[c];
+            }
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            dout[(long)c * S * S + i] = __fdiv_rn((float)d[c], 255.0f);
+            cout[(long)c * S * S + i] = __fdiv_rn((float)g[c], 255.0f);
+        }
+    }
+}
+// The degraded image itself (uint8 [3][H][W]) of one sample, by synth_px: for inspection.  Codes 1..3 only.
+__global__ void synth_image_kernel(const unsigned char* __restrict__ clean, const int* __restrict__ prm, const signed char* __restrict__ ray,
+                                   const unsigned short* __restrict__ hazet, const unsigned* __restrict__ seed, unsigned site,
+                                   unsigned char* __restrict__ out, int H, int W) {
+    __shared__ int sdy[32], sdx[32];
+    const SynthSlot s = synth_slot(prm);
+    if (s.code < 1 || s.code > 3) return;
+    stage_ray(ray, s.code == 2 ? 0 : s.a, sdy, sdx);
+    const unsigned key = fw_site_key(seed[0], site);
+    const long plane = (long)H * W;
+    for (long i = gtid(); i < plane; i += gstride()) {
+        const int x = (int)(i % W), y = (int)(i / W);
+        int g[3], d[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) g[c] = clean[c * plane + i];
+        synth_px(s, clean, H, W, y, x, g, key, sdy, sdx, hazet, d);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) out[c * plane + i] = (unsigned char)d[c];
+    }
+}
 }  // namespace
 
 #define ST ((hipStream_t)stream)
@@ -510,6 +643,21 @@ extern "C" int fw_train_batch(const void* tab, const int* rnd, const float* sigm
     FW_CHECK_ARG(tab && rnd && sigma && seed && d1 && d2 && c1 && c2 && B > 0 && S > 0);
     hipLaunchKernelGGL(train_batch_kernel, dim3(grid_for((long)B * 6 * S * S)), dim3(TPB), 0, ST, (const long long*)tab, rnd, sigma,
                        (const unsigned*)seed, (unsigned)site, d1, d2, c1, c2, B, S);
+    FW_LAUNCH_RET();
+}
+extern "C" int fw_train_batch_synth(const void* tab, const int* rnd, const float* sigma, const int* prm, const void* ray, const void* hazet,
+                                    const void* seed, int site, float* d1, float* d2, float* c1, float* c2, int B, int S, void* stream) {
+    FW_CHECK_ARG(tab && rnd && sigma && prm && ray && hazet && seed && d1 && d2 && c1 && c2 && B > 0 && B <= 32767 && S > 0 && S <= 4096);
+    hipLaunchKernelGGL(train_batch_synth_kernel, dim3((unsigned)((S * S + TPB - 1) / TPB), (unsigned)(2 * B)), dim3(TPB), 0, ST,
+                       (const long long*)tab, rnd, sigma, prm, (const signed char*)ray, (const unsigned short*)hazet, (const unsigned*)seed,
+                       (unsigned)site, d1, d2, c1, c2, S);
+    FW_LAUNCH_RET();
+}
+extern "C" int fw_synth_image(const void* clean, const int* prm, const void* ray, const void* hazet, const void* seed, int site, void* out,
+                              int H, int W, void* stream) {
+    FW_CHECK_ARG(clean && prm && ray && hazet && seed && out && H > 0 && W > 0 && (long)H * W < (1L << 31));
+    hipLaunchKernelGGL(synth_image_kernel, dim3(grid_for((long)H * W)), dim3(TPB), 0, ST, (const unsigned char*)clean, prm,
+                       (const signed char*)ray, (const unsigned short*)hazet, (const unsigned*)seed, (unsigned)site, (unsigned char*)out, H, W);
     FW_LAUNCH_RET();
 }
 extern "C" int fw_tile_gather(const float* img, const int* ys, const int* xs, float* tiles, int C, int H, int W, int ny, int nx, int T,

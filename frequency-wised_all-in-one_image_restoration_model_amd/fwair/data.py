@@ -124,19 +124,31 @@ class FolderTrainSet:
     fwair.augment.DeviceBatcher serves all tasks -- denoising noise is synthesised in the kernel, paired tasks pass the degraded image
     read from disk.  `epoch(e)` yields (degrad_patch_1, degrad_patch_2, clean_patch_1) per step.  Every rank builds the same
     TaskSchedule (same seed) and takes its slice of each global step; crop origins and flip / rotation modes come from a device
-    generator seeded with seed + 7919 * rank.  The schedule runs on from epoch to epoch as the reference's dataset object does."""
+    generator seeded with seed + 7919 * rank.  The schedule runs on from epoch to epoch as the reference's dataset object does.
+    synthesize: tasks of de_type ('deraining', 'dehazing', 'deblurring') that need no Input/ folder: their clean images are
+    <task>_train/GT if that exists, else denoising_train/GT (decoded once, shared), and their degraded crops are made inside the batch
+    launch (DeviceBatcher synth='kernel': stand-ins for the paired sets, new streaks / haze / blur every batch)."""
 
-    def __init__(self, root, de_type, patch_size, device, rank=0, world=1, per_gpu_batch=None, items_per_task=400, seed=0, cache_gb=48):
+    def __init__(self, root, de_type, patch_size, device, rank=0, world=1, per_gpu_batch=None, items_per_task=400, seed=0, cache_gb=48,
+                 synthesize=()):
         import torch
-        from .augment import DeviceBatcher
+        from .augment import SYNTH_CODES, DeviceBatcher
         self.de_type = list(de_type)
         self.rank, self.world = int(rank), int(world)
         self.B = int(per_gpu_batch or len(self.de_type))
         self.items_per_task = int(items_per_task)
         self.device = torch.device(device)
+        self.synthesize = [t for t in self.de_type if t in set(synthesize)]
+        unknown = sorted(set(synthesize) - set(SYNTH_CODES))
+        if unknown:
+            raise ValueError(f'fwair.data: no in-kernel synthesis for {unknown} (known: {sorted(SYNTH_CODES)})')
         ids = []
         for task in self.de_type:
-            gt, inp = pair_ids(_task_dir(root, task, 'train'), 'denoising' in task)
+            if task in self.synthesize:              # clean images only: the task's own GT/ if it has one, else the denoising set's
+                own = _task_dir(root, task, 'train')
+                gt, inp = pair_ids(own if os.path.isdir(own + 'GT/') else _task_dir(root, 'denoising_0', 'train'), True)
+            else:
+                gt, inp = pair_ids(_task_dir(root, task, 'train'), 'denoising' in task)
             if not gt:
                 raise FileNotFoundError(f'fwair.data: no training images for {task!r} under {_task_dir(root, task, "train")}')
             ids.append(list(zip(gt, inp)))
@@ -175,7 +187,11 @@ class FolderTrainSet:
         self.counts = [len(ok) for ok in kept]
         self.schedule = TaskSchedule(self.de_type, self.counts, seed)
         self.generator = torch.Generator(device=self.device).manual_seed(int(seed) + 7919 * self.rank)
-        self.batcher = DeviceBatcher(images, tasks, patch_size, degraded_u8=degraded)
+        if self.synthesize:
+            # a listed task's samples have no pair; an unlisted paired task always has one, so 'kernel' touches the listed ones only
+            self.batcher = DeviceBatcher(images, tasks, patch_size, degraded_u8=degraded, synth='kernel')
+        else:
+            self.batcher = DeviceBatcher(images, tasks, patch_size, degraded_u8=degraded)
         self.steps = steps_per_epoch(self.items_per_task, len(self.de_type), self.B, self.world)
 
     def indices(self, items):
@@ -187,6 +203,7 @@ class FolderTrainSet:
             items = self.schedule.take(self.B * self.world)
             if len(self.batcher._tables) > 1024:              # the batcher caches a pointer table per index list; a shuffled stream never repeats one
                 self.batcher._tables.clear()
+                self.batcher._ptables.clear()
             d1, d2, c1, _ = self.batcher.batch(self.indices(shard(items, self.rank, self.B)), generator=self.generator)
             yield d1, d2, c1
 

@@ -19,6 +19,10 @@ fw_train_batch launch (fwair.data.FolderTrainSet), and the per-epoch evaluation 
 fwair.evaluate.EvalEngine.
 
     python train_ddp.py --data_root data/ --de_type denoising_15 denoising_25 denoising_50 deraining dehazing ... [--items_per_task 400]
+
+`--synthesize_tasks deraining dehazing deblurring` makes rain, haze and motion blur inside the batch kernel (fw_train_batch_synth, new
+per batch; stand-ins for the paired sets), so the default `4tasks` list trains from clean images alone -- from `denoising_train/GT` with
+`--data_root`, from a synthetic pool with `--synthetic_steps`.
 """
 import argparse
 import os
@@ -35,6 +39,11 @@ _own.add_argument('--no_eval', action='store_true', help='skip the per-epoch eva
 _own.add_argument('--data_root', type=str, default='', help='train and evaluate on the image folders of this directory (fwair/data.py)')
 _own.add_argument('--items_per_task', type=int, default=400, help='items per task and epoch with --data_root (dataset_utils.py:144)')
 _own.add_argument('--data_cache_gb', type=float, default=48, help='device memory the decoded training set may take with --data_root')
+_own.add_argument('--synthesize_tasks', nargs='*', default=[], choices=['deraining', 'dehazing', 'deblurring'],
+                  help='make the degraded crops of these tasks inside the batch kernel, fresh per batch (stand-ins for the paired sets). '
+                       'With --data_root they need no <task>_train/Input folder (clean images: <task>_train/GT, else denoising_train/GT); '
+                       'with --synthetic_steps every batch comes from a fixed pool of synthetic clean images.  The per-epoch evaluation '
+                       'of such a task still needs its <task>_test folder: pass --no_eval or a narrower --test_de_type without one')
 _ARGS, _rest = _own.parse_known_args()
 sys.argv = [sys.argv[0]] + _rest                       # option.py parses sys.argv at import (reference option.py:3)
 
@@ -69,8 +78,26 @@ def batches(epoch, rank, world, B, dev):
         if 'train' not in _FOLDERS:
             from fwair.data import FolderTrainSet
             _FOLDERS['train'] = FolderTrainSet(_ARGS.data_root, opt.de_type, opt.patch_size, dev, rank=rank, world=world, per_gpu_batch=B,
-                                               items_per_task=_ARGS.items_per_task, seed=1234, cache_gb=_ARGS.data_cache_gb)
+                                               items_per_task=_ARGS.items_per_task, seed=1234, cache_gb=_ARGS.data_cache_gb,
+                                               synthesize=_ARGS.synthesize_tasks)
         yield from _FOLDERS['train'].epoch(epoch)
+        return
+    if _ARGS.synthetic_steps > 0 and _ARGS.synthesize_tasks:
+        # a fixed pool of synthetic clean images at 1.5 x the patch size, one per slot and task; sample i carries task i % len(de_type)
+        # (dataset_utils.py:99) and the listed tasks are degraded inside the batch launch, anew in every batch
+        if 'pool' not in _FOLDERS:
+            from fwair.augment import DeviceBatcher
+            tasks = [opt.de_type[i % len(opt.de_type)] for i in range(B * len(opt.de_type))]
+            clean, _, _ = synth_batch(len(tasks), opt.patch_size * 3 // 2, 0, 1234 + rank, dev)
+            pool = list((clean * 255.0).round().to(torch.uint8))
+            _FOLDERS['pool'] = (DeviceBatcher(pool, tasks, opt.patch_size, generator=torch.Generator().manual_seed(1234 + rank), synth='kernel'),
+                                torch.Generator(device=dev).manual_seed(1234 + 7919 * rank))
+        bt, g = _FOLDERS['pool']
+        n = len(bt.images) // B
+        for i in range(_ARGS.synthetic_steps):
+            k = (epoch * _ARGS.synthetic_steps + i) % n
+            d1, d2, c1, _ = bt.batch(list(range(k * B, (k + 1) * B)), generator=g)
+            yield d1, d2, c1
         return
     if _ARGS.synthetic_steps > 0:
         sig = [sigma_of(t) for t in opt.de_type] or [25]

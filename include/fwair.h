@@ -405,6 +405,23 @@ int fw_rng_tick(void* seed, void* stream);
  * clean crop 1 / 2. */
 int fw_train_batch(const void* tab, const int* rnd, const float* sigma, const void* seed, int site, float* d1, float* d2, float* c1,
                    float* c2, int B, int S, void* stream);
+/* fw_train_batch with rain, haze and motion blur synthesised in the launch (stand-ins for the paired sets, fwair/augment.py).  prm: device
+ * int32 [B][8] = {code, p1, p2, p3, p4, 0, 0, 0}; code 0: the slot behaves as in fw_train_batch.  ray: device int8 [32][32][2], (dy, dx) =
+ * (round(t sin), round(t cos)) of step t at angle pi a / 32; hazet: device uint16 [16][256] = round(65535 exp(-beta_j (1 - 0.9 k / 255))).
+ * With g = the clean value of source pixel (c, y, x) of the full H x W image, all in integers:
+ *   1 rain {a, L <= 32, density16, S8}: q is a seed iff (h & 0xFFFF) < density16, h = hash32((qy W + qx) ^ key(seed[0], site + b)), of
+ *     amplitude A(q) = 128 + ((h >> 16) & 127); m = max over t < L, q = (y, x) - ray[a][t] inside the image and a seed, of A(q) (L - t);
+ *     d = min(255, g + m S8 / (256 L)).
+ *   2 haze {j, A8}: k = 255 y / (H - 1), T = hazet[j][k], d = (g T + A8 (65535 - T) + 32767) / 65535.
+ *   3 motion blur {a, n odd <= 25}: d = (2 sum + n) / (2 n), sum over s = -(n-1)/2 .. (n-1)/2 of the clean value at (y, x) + sign(s)
+ *     ray[a][|s|], clamped at the image border.
+ * Both crops of a slot cut the same degraded image; the rain layer is new in every slot and call (site).  Parameters outside the tables'
+ * extent are clamped. */
+int fw_train_batch_synth(const void* tab, const int* rnd, const float* sigma, const int* prm, const void* ray, const void* hazet,
+                         const void* seed, int site, float* d1, float* d2, float* c1, float* c2, int B, int S, void* stream);
+/* The degraded image of ONE sample as uint8 [3][H][W], by the same per-pixel code (prm: one record of code 1..3; key(seed[0], site)). */
+int fw_synth_image(const void* clean, const int* prm, const void* ray, const void* hazet, const void* seed, int site, void* out, int H,
+                   int W, void* stream);
 /* test.py:47-57: tiles[t = a * nx + b][c][i][j] = img[c][ys[a] + i][xs[b] + j]  (ys / xs: device int32 tile origins) */
 int fw_tile_gather(const float* img, const int* ys, const int* xs, float* tiles, int C, int H, int W, int ny, int nx, int T, void* stream);
 /* test.py:61-71 with the RESTORED tiles: out[c][y][x] = mean of the tiles covering (y, x) */
