@@ -462,8 +462,32 @@ __global__ __launch_bounds__(NTH, 2) void attn_bwd_kernel(AttnArgs a) {
 //     they are older in the vmcnt queue, so waiting for them never waits for a store;
 //   * backward, bf16: the two applications of the band filter (on P and on dP') run as ONE pass over two tiles -- half the
 //     barriers, every panel fragment used twice.
-// One workgroup of 4 waves per CU (backward; LDS 111 KB) or two (forward, 77 KB): with nothing left to wait for, occupancy is not
-// what hides latency any more.
+// What is left per window is still a latency chain (25-118 s_waitcnt, 2-8 barriers, a few hundred VALU instructions around 8-136
+// MFMAs; the waves issue 30-46 % of the time), and resident waves are what hides it.  Two things decide how many there are:
+//   * the register budget.  Under __launch_bounds__(NTH, 1) a wave may use 512 registers and hipcc keeps the MFMA accumulators in
+//     AGPRs, copying every value the softmax / filter code touches out with v_accvgpr_read_b32 (24-240 copies per window).  From two
+//     waves per SIMD on (256 registers) the MFMAs take their VGPR form and the copies are gone.  *_waves() below give every
+//     instantiation the largest bound at which it needs no scratch memory (profiles/r19_attn_kernel_meta.txt), but no more than
+//     max(2, what its LDS bytes admit): a tighter budget than LDS can fill buys nothing.
+//   * the grid.  A CU holds min(LDS, registers) workgroups of a kernel -- one (backward, LFS, 56 / 64 wide) to six (forward,
+//     encoder) -- and walk_chunks() launches that many per CU, as the runtime's occupancy query reports them for the compiled
+//     kernel; more workgroups walk fewer windows each.
+// Waves per SIMD (= workgroups per CU: a workgroup puts one wave on each SIMD) a v2 kernel is compiled for.  Read off the code
+// objects: hipcc, gfx950, bounds 1 .. 6.  f32 is parity mode; its wide backward forms need more than 256 registers and stay at 1.
+template <typename T, int D, int LFS> constexpr int fwd2_waves() {
+    if (LFS == 2) return 2;                                  // LDS admits two (bf16) or one (f32); scratch-free up to 3 / 2
+    if (sizeof(T) == 4) return D <= 32 ? 3 : 2;              // LDS admits no more
+    return D <= 32 ? 5 : 4;                                  // 79-82 / 110-114 registers; scratch from 6 / 5 on
+}
+template <typename T, int D, int LFS> constexpr int bwd2_waves() {
+    if (sizeof(T) == 4) return (LFS == 2 || (LFS == 1 && D > 32)) ? 1 : 2;
+    if (LFS == 2) return 2;                                  // <56, 2> / <64, 2>: 246 / 254 registers in their lean form (Smem2::LEAN_BWD)
+    return (LFS == 0 && D <= 32) ? 3 : 2;                    // <28, 0> / <32, 0>: 152 / 157 registers, LDS admits three
+}
+template <typename T> constexpr int x2_waves(bool bwd) {     // attn2x_*: bf16 137 / 226 registers, f32 158 / 360
+    return sizeof(T) == 2 ? (bwd ? 2 : 3) : (bwd ? 1 : 2);
+}
+
 template <typename T> struct FiltTab {
     static constexpr int SZ = TT<T>::SZ;
     static constexpr int LDP = 64 * SZ + 16;
@@ -652,6 +676,14 @@ struct BiasRegs {
             }
     }
     FW_MEM float get(int jt, int r, unsigned m) const { return b[jt][r] + (((m >> (jt * 4 + r)) & 1) ? -100.0f : 0.0f); }
+    // The same value with the bias read back from the staged table (for a kernel with no 16 registers to spare; b[] is then never
+    // used and costs none).  j = 16 jt + 4 (l >> 4) + r, so j >> 3 = 2 jt + (l >> 5) and j & 7 = 4 ((l >> 4) & 1) + r: the lane's 16
+    // bins lie at the constant offsets -30 jt - r from that of (jt, r) = (0, 0), which lane_bins() returns.
+    static FW_MEM const float* lane_bins(const float* bins, int i) {
+        const int a = lane_id() >> 4;
+        return bins + ((i >> 3) - (a >> 1) + 7) * 15 + (i & 7) - 4 * (a & 1) + 7;
+    }
+    static FW_MEM float get_lds(const float* bl, int jt, int r, unsigned m) { return bl[-30 * jt - r] + (((m >> (jt * 4 + r)) & 1) ? -100.0f : 0.0f); }
     FW_MEM unsigned mask(bool last_y, bool last_x) const { return (last_y ? dy : 0u) | (last_x ? dx : 0u); }
 };
 
@@ -664,11 +696,16 @@ template <typename T, int D, int LFS> struct Smem2 {
     static constexpr int OFF_T = TAB + 1024;                                          // tiles start here
     static constexpr int RA = SCR > G::TILE_D ? SCR : G::TILE_D;                      // fwd: Q -> P' / scratch A
     static constexpr int FWD_BYTES = OFF_T + RA + RA + G::TILE_D;                     // | A | B (K, scratch B, O staging) | V
-    static constexpr int BWD_BYTES = OFF_T + 4 * G::TILE_D + 2 * NTF * SCR;           // Q dO K V | (X, Y) per filter tile
+    // The wide bf16 LFS backward needs 306-310 registers; what does not fit 256 would go to scratch memory.  Its lean form keeps the
+    // lane's 16 dbias accumulators in LDS (f32x4 [4][NTH], own words only: no barrier) and reads its biases back from the staged table;
+    // values and the order of every addition are those of the register form.
+    static constexpr bool LEAN_BWD = LFS == 2 && sizeof(T) == 2 && D > 32;
+    static constexpr int OFF_DB = OFF_T + 4 * G::TILE_D + 2 * NTF * SCR;             // Q dO K V | (X, Y) per filter tile | dbias accumulators
+    static constexpr int BWD_BYTES = OFF_DB + (LEAN_BWD ? 4 * NTH * 16 : 0);
 };
 
 template <typename T, int D, int LFS>
-__global__ __launch_bounds__(NTH, 1) void attn2_fwd_kernel(AttnArgs a) {
+__global__ __launch_bounds__(NTH, (fwd2_waves<T, D, LFS>())) void attn2_fwd_kernel(AttnArgs a) {
     using G = Geo<T, D>;
     using S = Smem2<T, D, LFS>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -777,7 +814,7 @@ __global__ __launch_bounds__(NTH, 1) void attn2_fwd_kernel(AttnArgs a) {
 }
 
 template <typename T, int D, int LFS>
-__global__ __launch_bounds__(NTH, 1) void attn2_bwd_kernel(AttnArgs a) {
+__global__ __launch_bounds__(NTH, (bwd2_waves<T, D, LFS>())) void attn2_bwd_kernel(AttnArgs a) {
     using G = Geo<T, D>;
     using S = Smem2<T, D, LFS>;
     constexpr int NTF = S::NTF;
@@ -801,9 +838,13 @@ __global__ __launch_bounds__(NTH, 1) void attn2_bwd_kernel(AttnArgs a) {
         const float* tb = a.bias + (size_t)(lq * a.L + lq) * 225 * a.heads + h;
         for (int idx = threadIdx.x; idx < 225; idx += NTH) bins[idx] = tb[(size_t)idx * a.heads];
     }
-    f32x4 dbacc[4];
+    constexpr bool LEAN = S::LEAN_BWD;
+    f32x4 dbacc[4];                                                            // dbias of the lane's 16 (i, j) pairs, summed over the walk
+    f32x4* dbl = reinterpret_cast<f32x4*>(smem + S::OFF_DB) + threadIdx.x;    // LEAN: the same sums, in LDS
 #pragma unroll
-    for (int jt = 0; jt < 4; ++jt) dbacc[jt] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int jt = 0; jt < 4; ++jt) {
+        if constexpr (LEAN) dbl[jt * NTH] = f32x4{0.f, 0.f, 0.f, 0.f}; else dbacc[jt] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
     float cs1 = 0.f, cs2 = 0.f, cs3 = 0.f, ca = 1.f, cb = 0.f, cc = 0.f;
     int cs_b = -1;
     auto flush_coef = [&]() {
@@ -832,6 +873,7 @@ __global__ __launch_bounds__(NTH, 1) void attn2_bwd_kernel(AttnArgs a) {
     lds_barrier();                          // biases staged
     BiasRegs br;
     br.init(bins, i, a.shift);
+    const float* bl = BiasRegs::lane_bins(bins, i);
     float lse_next = a.lse[(((size_t)win_begin * a.L + lq) * a.heads + h) * 64 + i];
     for (int win = win_begin; win < win_end; ++win) {
         const int b = win / nW, wi = win % nW, wy = wi / nWx, wx = wi % nWx;
@@ -866,7 +908,7 @@ __global__ __launch_bounds__(NTH, 1) void attn2_bwd_kernel(AttnArgs a) {
 #pragma unroll
         for (int jt = 0; jt < 4; ++jt)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) pd[0][jt][r] = __expf(pd[0][jt][r] * a.scale + br.get(jt, r, msk) - lse);
+            for (int r = 0; r < 4; ++r) pd[0][jt][r] = __expf(pd[0][jt][r] * a.scale + (LEAN ? BiasRegs::get_lds(bl, jt, r, msk) : br.get(jt, r, msk)) - lse);
         f32x4 fg[2][4];                      // [0] = B1(P), [1] = B1(dP')
         if constexpr (LFS == 2) {
             if constexpr (NTF == 2) {
@@ -930,7 +972,7 @@ __global__ __launch_bounds__(NTH, 1) void attn2_bwd_kernel(AttnArgs a) {
             for (int jt = 0; jt < 4; ++jt) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) pd[1][jt][r] = pd[0][jt][r] * (pd[1][jt][r] - di);
-                dbacc[jt] += pd[1][jt];
+                if constexpr (LEAN) dbl[jt * NTH] += pd[1][jt]; else dbacc[jt] += pd[1][jt];
             }
         }
         lds_barrier();                    // every wave is done reading P' (sX) and its dV staging rows (sY)
@@ -966,12 +1008,14 @@ __global__ __launch_bounds__(NTH, 1) void attn2_bwd_kernel(AttnArgs a) {
     for (int idx = threadIdx.x; idx < 225; idx += NTH) fold[idx] = 0.f;
     lds_barrier();
 #pragma unroll
-    for (int jt = 0; jt < 4; ++jt)
+    for (int jt = 0; jt < 4; ++jt) {
+        if constexpr (LEAN) dbacc[jt] = dbl[jt * NTH];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int j = jt * 16 + ((l >> 4) << 2) + r;
             atomicAdd(&fold[((i >> 3) - (j >> 3) + 7) * 15 + (i & 7) - (j & 7) + 7], dbacc[jt][r]);
         }
+    }
     lds_barrier();
     float* dst = a.dbias + (size_t)(lq * a.L + lq) * 225 * a.heads;
     for (int idx = threadIdx.x; idx < 225; idx += NTH) atomicAdd(dst + idx * a.heads + h, fold[idx]);
@@ -996,7 +1040,7 @@ template <typename T, int D> struct Smem2X {
 };
 
 template <typename T, int D>
-__global__ __launch_bounds__(NTH, 1) void attn2x_fwd_kernel(AttnArgs a) {
+__global__ __launch_bounds__(NTH, x2_waves<T>(false)) void attn2x_fwd_kernel(AttnArgs a) {
     using G = Geo<T, D>;
     using S = Smem2X<T, D>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1108,7 +1152,7 @@ __global__ __launch_bounds__(NTH, 1) void attn2x_fwd_kernel(AttnArgs a) {
 }
 
 template <typename T, int D>
-__global__ __launch_bounds__(NTH, 1) void attn2x_bwd_kernel(AttnArgs a) {
+__global__ __launch_bounds__(NTH, x2_waves<T>(true)) void attn2x_bwd_kernel(AttnArgs a) {
     using G = Geo<T, D>;
     using S = Smem2X<T, D>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -1286,41 +1330,56 @@ __global__ __launch_bounds__(NTH, 1) void attn2x_bwd_kernel(AttnArgs a) {
     }
 }
 
-template <typename T, int D>
-int x2_launch(bool bwd, const AttnArgs& a, hipStream_t st) {
-    using S = Smem2X<T, D>;
-    const int bytes = bwd ? S::BWD_BYTES : S::FWD_BYTES;
-    if (bwd) { FW_SET_LDS_ONCE((attn2x_bwd_kernel<T, D>), S::BWD_BYTES); } else { FW_SET_LDS_ONCE((attn2x_fwd_kernel<T, D>), S::FWD_BYTES); }
-    const int per_cu = 2 * bytes <= 160 * 1024 ? 2 : 1;
-    int chunks = (256 * per_cu) / (a.heads * a.L);
-    if (chunks < 1) chunks = 1;
-    if (chunks > a.nwin) chunks = a.nwin;
-    if (bwd) hipLaunchKernelGGL((attn2x_bwd_kernel<T, D>), dim3(chunks, a.heads, a.L), dim3(NTH), bytes, st, a);
-    else hipLaunchKernelGGL((attn2x_fwd_kernel<T, D>), dim3(chunks, a.heads, a.L), dim3(NTH), bytes, st, a);
+// Workgroups of one v2 instantiation (KERN with BYTES of dynamic LDS) that a CU holds at once: what its LDS bytes AND its compiled
+// register count admit, asked of the runtime once per instantiation, after the dynamic-LDS limit is raised.  The first call of an
+// instantiation is a warm-up step or fw_attn_chunks(), never inside a capture (FW_SET_LDS_ONCE relies on the same).  0: the query failed.
+template <auto KERN, int BYTES> int resident_per_cu() {
+    static const int n = [] {
+        FW_SET_LDS_ONCE(KERN, BYTES);
+        int v = 0;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, reinterpret_cast<const void*>(KERN), NTH, BYTES) != hipSuccess) v = 0;
+        return v;
+    }();
+    return n;
+}
+// grid.x of a v2 launch: the 256 CUs filled once, every (head, band) walking its windows in `chunks` contiguous ranges.
+// BWD: a backward workgroup ends with an LDS fold and 225 global atomics per bias table, so a third workgroup per CU pays only while
+// every walk keeps BWD_MIN_WALK windows (measured, DESIGN.md lesson 30); below that the launch stays at two per CU.
+constexpr int BWD_MIN_WALK = 4;
+template <auto KERN, int BYTES, bool BWD> int walk_chunks(const AttnArgs& a) {
+    int per_cu = resident_per_cu<KERN, BYTES>();
+    if (per_cu < 1) return 0;
+    auto rule = [&](int wgs) {
+        int chunks = (256 * wgs) / (a.heads * a.L);
+        if (chunks < 1) chunks = 1;
+        return chunks > a.nwin ? a.nwin : chunks;
+    };
+    int chunks = rule(per_cu);
+    if (BWD && per_cu > 2 && fw_cdiv(a.nwin, chunks) < BWD_MIN_WALK) chunks = rule(2);
+    return chunks;
+}
+// grid_only: store grid.x there and launch nothing (fw_attn_chunks)
+template <auto KERN, int BYTES, bool BWD> int walk_launch(const AttnArgs& a, hipStream_t st, int* grid_only) {
+    const int chunks = walk_chunks<KERN, BYTES, BWD>(a);
+    if (chunks < 1) return (int)hipErrorLaunchFailure;      // no occupancy figure: an error, not a guess
+    if (grid_only) { *grid_only = chunks; return 0; }
+    hipLaunchKernelGGL(KERN, dim3(chunks, a.heads, a.L), dim3(NTH), BYTES, st, a);
     FW_LAUNCH_RET();
 }
 
-template <typename T, int D, int LFS>
-int fwd2_launch(const AttnArgs& a, hipStream_t st) {
-    using S = Smem2<T, D, LFS>;
-    FW_SET_LDS_ONCE((attn2_fwd_kernel<T, D, LFS>), S::FWD_BYTES);
-    const int per_cu = 2 * S::FWD_BYTES <= 160 * 1024 ? 2 : 1;
-    int chunks = (256 * per_cu) / (a.heads * a.L);
-    if (chunks < 1) chunks = 1;
-    if (chunks > a.nwin) chunks = a.nwin;
-    hipLaunchKernelGGL((attn2_fwd_kernel<T, D, LFS>), dim3(chunks, a.heads, a.L), dim3(NTH), S::FWD_BYTES, st, a);
-    FW_LAUNCH_RET();
+template <typename T, int D>
+int x2_launch(bool bwd, const AttnArgs& a, hipStream_t st, int* grid_only) {
+    using S = Smem2X<T, D>;
+    return bwd ? walk_launch<attn2x_bwd_kernel<T, D>, S::BWD_BYTES, true>(a, st, grid_only)
+               : walk_launch<attn2x_fwd_kernel<T, D>, S::FWD_BYTES, false>(a, st, grid_only);
 }
 template <typename T, int D, int LFS>
-int bwd2_launch(const AttnArgs& a, hipStream_t st) {
-    using S = Smem2<T, D, LFS>;
-    FW_SET_LDS_ONCE((attn2_bwd_kernel<T, D, LFS>), S::BWD_BYTES);
-    const int per_cu = 2 * S::BWD_BYTES <= 160 * 1024 ? 2 : 1;
-    int chunks = (256 * per_cu) / (a.heads * a.L);
-    if (chunks < 1) chunks = 1;
-    if (chunks > a.nwin) chunks = a.nwin;
-    hipLaunchKernelGGL((attn2_bwd_kernel<T, D, LFS>), dim3(chunks, a.heads, a.L), dim3(NTH), S::BWD_BYTES, st, a);
-    FW_LAUNCH_RET();
+int fwd2_launch(const AttnArgs& a, hipStream_t st, int* grid_only) {
+    return walk_launch<attn2_fwd_kernel<T, D, LFS>, Smem2<T, D, LFS>::FWD_BYTES, false>(a, st, grid_only);
+}
+template <typename T, int D, int LFS>
+int bwd2_launch(const AttnArgs& a, hipStream_t st, int* grid_only) {
+    return walk_launch<attn2_bwd_kernel<T, D, LFS>, Smem2<T, D, LFS>::BWD_BYTES, true>(a, st, grid_only);
 }
 
 template <typename T, int D>
@@ -1340,20 +1399,21 @@ int bwd_launch(const AttnArgs& a, hipStream_t st) {
 }
 
 template <typename T>
-int dispatch(bool bwd, int D, int nkt, int lfs, const AttnArgs& a, hipStream_t st) {
+int dispatch(bool bwd, int D, int nkt, int lfs, const AttnArgs& a, hipStream_t st, int* grid_only = nullptr) {
     // one key tile over the query's own band (decoder W-MSA + LFS, encoder intra / origin, ViT): the v2 kernels
 #define FW_ATT2(DD, FF)                                                                        \
     if (D == DD && nkt == 1 && a.mode == 0 && lfs == FF)                                       \
-        return bwd ? bwd2_launch<T, DD, FF>(a, st) : fwd2_launch<T, DD, FF>(a, st);
+        return bwd ? bwd2_launch<T, DD, FF>(a, st, grid_only) : fwd2_launch<T, DD, FF>(a, st, grid_only);
     FW_ATT2(56, 0) FW_ATT2(56, 1) FW_ATT2(56, 2) FW_ATT2(28, 0) FW_ATT2(64, 0)
     // the decoder at --embed_dim 32 / 64 (head_dim = embed_dim at every stage).  Geo<T, 64> is Geo<T, 56> without the padding granule
     // (CH == SL); Geo<T, 32> is the D = 28 tile (KC 1 / 2, DT 2) without padding and with 16-byte granules in bf16, one TileLoad
     // round per tile.  The filter scratch (Smem2::SCR) does not depend on D and covers TILE_D at both widths, so the O / dV / dK
-    // staging rows fit; dq_pad is 0 (heads * D % 8 == 0).  Two workgroups per CU where 2 x LDS bytes <= 160 KB (fwd2_ / bwd2_launch).
+    // staging rows fit; dq_pad is 0 (heads * D % 8 == 0).
     FW_ATT2(64, 1) FW_ATT2(64, 2) FW_ATT2(32, 0) FW_ATT2(32, 1) FW_ATT2(32, 2)
 #undef FW_ATT2
     // inter-band, three bands: both key tiles in one pass
-    if (D == 28 && nkt == 2 && a.mode == 1 && a.L == 3 && lfs == 0) return x2_launch<T, 28>(bwd, a, st);
+    if (D == 28 && nkt == 2 && a.mode == 1 && a.L == 3 && lfs == 0) return x2_launch<T, 28>(bwd, a, st, grid_only);
+    if (grid_only) return -1000;      // the v1 kernels do not walk by this rule
     // what is left for the v1 kernels: inter-band with two bands (mode 1, one key tile of the other band, no frequency selection)
 #define FW_ATT(DD)                                                                             \
     if (D == DD && nkt == 1 && lfs == 0)                                                       \
@@ -1388,6 +1448,20 @@ extern "C" int fw_attn_fwd(int dtype, int D, int nkt, int lfs, const void* q, co
     a.nwin = B * (H / 8) * (W / 8);
     hipStream_t st = (hipStream_t)stream;
     return dtype == FW_DT_BF16 ? dispatch<bf16raw>(false, D, nkt, lfs, a, st) : dispatch<float>(false, D, nkt, lfs, a, st);
+}
+
+// grid.x of the v2 launch fw_attn_fwd (backward = 0) / fw_attn_bwd (1) makes for these arguments: the number of contiguous window
+// ranges every (head, band) is walked in.  nkt 1: mode 0 (attn2_*); nkt 2: inter-band over L = 3 (attn2x_*).  Negative: argument
+// error, or a combination the v2 kernels do not take.  Call it outside stream captures (it may ask the runtime for the occupancy).
+extern "C" int fw_attn_chunks(int dtype, int D, int nkt, int lfs, int backward, int nwin, int heads, int L) {
+    FW_CHECK_ARG((dtype == FW_DT_BF16 || dtype == FW_DT_F32) && nwin > 0 && heads > 0 && L >= 1 && L <= 3);
+    FW_CHECK_ARG((nkt == 1 || (nkt == 2 && L == 3)) && (lfs == 0 || (nkt == 1 && L == 1)));
+    AttnArgs a = {};
+    a.heads = heads; a.L = L; a.nwin = nwin; a.mode = nkt == 1 ? 0 : 1;
+    int chunks = 0;
+    const int rc = dtype == FW_DT_BF16 ? dispatch<bf16raw>(backward != 0, D, nkt, lfs, a, nullptr, &chunks)
+                                       : dispatch<float>(backward != 0, D, nkt, lfs, a, nullptr, &chunks);
+    return rc == 0 ? chunks : (rc < 0 ? rc : -rc);
 }
 
 // Backward.  dq/dk/dv: rows = tokens, head h at column h*D, row stride ldd (one [T][3C] buffer works:

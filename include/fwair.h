@@ -116,6 +116,15 @@ int fw_attn_bwd(int dtype, int D, int nkt, int lfs, const void* q, const void* k
                 long ldo, const void* dout, long lddo, const float* lse, const float* bias, const float* coef,
                 const void* lfs_tab, void* dq, void* dk, void* dv, void* dk2, void* dv2, long ldd, float* dbias,
                 float* dcoef, int B, int H, int W, int heads, int L, int mode, int shift, float scale, int dq_pad, void* stream);
+/* grid.x of the launch fw_attn_fwd (backward = 0) / fw_attn_bwd (1) makes for a problem of nwin = B * (H/8) * (W/8) windows: every
+ * (head, band) is walked in that many contiguous window ranges of ceil(nwin / grid.x) windows (the last ones may be short or empty).
+ * It is 256 CUs times the workgroups of the chosen kernel one CU holds -- bounded by its LDS bytes and its compiled register
+ * count, as the runtime reports them -- over heads * L, clamped to [1, nwin].  nkt 1: mode 0; nkt 2: the inter-band form over
+ * L = 3.  Negative: argument error, or a combination served by the kernels that do not walk by this rule (mode 1 over two bands:
+ * forward one workgroup per item up to 4096, backward 1024 / (heads * L) ranges).  dbias receives one atomic addition per busy
+ * workgroup and dcoef one per wave of every workgroup holding windows of the image, so their summation ORDER follows this figure;
+ * out, lse, dq, dk, dv do not depend on it.  Not to be called inside a stream capture. */
+int fw_attn_chunks(int dtype, int D, int nkt, int lfs, int backward, int nwin, int heads, int L);
 
 /* ---- LeFF depthwise 3x3 (net/utils/leff.py:104-111).
  * fwd: h2 = dwconv(GELU?(in)) + bias, g2 = GELU(h2).  in_gelu = 1: `in` is the PRE-activation h1 of linear1 and its GELU (leff.py:100) is
