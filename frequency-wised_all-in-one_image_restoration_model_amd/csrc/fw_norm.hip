@@ -4,7 +4,8 @@
 // loads, G lanes per row (G = 16/32/64 by width) so narrow rows (C = 28, 56) do not idle a wave.
 //   fwd : y[T] = (x - mean) * rstd * gamma + beta ; saves mean, rstd (fp32)
 //   bwd : dx[f32] = (dres?) + rstd * (g - mean(g) - xhat * mean(g*xhat)),  g = dy * gamma
-//         dgamma += sum_rows dy * xhat ; dbeta += sum_rows dy      (block partials -> atomicAdd)
+//         dgamma += sum_rows dy * xhat ; dbeta += sum_rows dy      (block partials by plain stores -> fw_slab_reduce)
+//         dy: T rows, or the unfolded f32 slab of the split-K input-gradient GEMM in front (fw_layernorm_bwd_slab)
 //   learnable window modulator of the decoder blocks (decoder_Uformer.py:536-539,687-691):
 //   fwd : y[T] = LN(x) * gamma + beta + mod[window position of the row]      (a compile-time branch of the forward kernel)
 //   bwd : dmod[p] += sum of dy over the rows at window position p            (slices by plain stores -> fw_slab_reduce, no atomics)
@@ -125,15 +126,54 @@ __global__ __launch_bounds__(256) void ln_fwd_kernel(const float* __restrict__ x
     }
 }
 
+// dy of one lane vector summed from the nz slices of a split-K slab (p: the vector in slice 0, zs: floats between slices), in the
+// association of slab_reduce_kernel (fw_elem.hip) with the whole z range in one block: partial sum j takes slices j, j + 4, ..., each
+// started from zero and advanced by the same unrolled pairing, and the total is s0 + ((s1 + s2) + s3) -- the same bits as the fold.
+// nz <= 4 (the deep stages split 2 or 3 ways) is one independent load per slice under wave-uniform branches.
+FW_DEV f32x4 slab_dy_sum(const float* __restrict__ p, int nz, long zs) {
+    f32x4 s[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) s[j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (nz <= 4) {
+        s[0] += *reinterpret_cast<const f32x4*>(p);
+        if (nz > 1) s[1] += *reinterpret_cast<const f32x4*>(p + zs);
+        if (nz > 2) s[2] += *reinterpret_cast<const f32x4*>(p + 2 * zs);
+        if (nz > 3) s[3] += *reinterpret_cast<const f32x4*>(p + 3 * zs);
+    } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            int z = j;
+            for (; z + 12 < nz; z += 16) {
+                const f32x4 a0 = *reinterpret_cast<const f32x4*>(p + (long)z * zs);
+                const f32x4 a1 = *reinterpret_cast<const f32x4*>(p + (long)(z + 4) * zs);
+                const f32x4 a2 = *reinterpret_cast<const f32x4*>(p + (long)(z + 8) * zs);
+                const f32x4 a3 = *reinterpret_cast<const f32x4*>(p + (long)(z + 12) * zs);
+                s[j] += (a0 + a1) + (a2 + a3);
+            }
+            for (; z < nz; z += 4) s[j] += *reinterpret_cast<const f32x4*>(p + (long)z * zs);
+        }
+    }
+    return s[0] + ((s[1] + s[2]) + s[3]);
+}
+template <typename T> FW_DEV void raw_from_sum(RawV<T>& r, const f32x4& s);
+template <> FW_SPEC void raw_from_sum<float>(RawV<float>& r, const f32x4& s) { r.v = s; }                     // parity mode: no rounding
+template <> FW_SPEC void raw_from_sum<bf16raw>(RawV<bf16raw>& r, const f32x4& s) {                            // as cast_rows_kernel rounds
+    r.v = make_uint2(pack_bf2(s[0], s[1]), pack_bf2(s[2], s[3]));
+}
+
 // Each block walks row groups blockIdx.x, blockIdx.x + gridDim.x, ... of RPB * U rows; column partial sums stay in registers.
-template <typename T, int G, int NV, int U>
-__global__ __launch_bounds__(256) void ln_bwd_kernel(const T* __restrict__ dy, long lddy, const float* __restrict__ x, long ldx,
+// SLAB: dy is not a T matrix but the unfolded f32 slab of the split-K input-gradient GEMM in front (nz slices of rows x C contiguous
+// partials, zstride floats apart): the lane sums its vector from the slices and rounds it to T exactly as fw_slab_reduce ->
+// fw_cast_rows would have, so dx, twin and the column partials are the bits of that three-launch chain without its two passes.
+template <typename T, int G, int NV, int U, int TPB, bool SLAB>
+__global__ __launch_bounds__(TPB) void ln_bwd_kernel(const T* __restrict__ dy, long lddy, const float* __restrict__ slab, int nz, long zstride,
+                                                     const float* __restrict__ x, long ldx,
                                                      const float* __restrict__ gamma, const float* __restrict__ mean,
                                                      const float* __restrict__ rstd, const float* __restrict__ dres, long lddres,
                                                      float* __restrict__ dx, long lddx, float* __restrict__ partial,
                                                      long pstride, int rows, int C, T* __restrict__ twin, long ldtw,
                                                      const float* __restrict__ twscale, int tw_rows_per_scale) {
-    constexpr int RPB = 256 / G;
+    constexpr int RPB = TPB / G;
     const int gl = threadIdx.x % G, gr = threadIdx.x / G;
     const int nv = C >> 2;
     const float invc = 1.0f / C;
@@ -161,8 +201,20 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const T* __restrict__ dy, l
             for (int t = 0; t < NV; ++t) {
                 const int cc = (cok[t] ? gl + G * t : nv - 1) * 4;
                 xv[u][t] = *reinterpret_cast<const f32x4*>(x + rc * ldx + cc);
-                dr[u][t].load(dy + rc * lddy + cc);
+                if (!SLAB) dr[u][t].load(dy + rc * lddy + cc);
                 if (dres) rr[u][t] = *reinterpret_cast<const f32x4*>(dres + rc * lddres + cc);
+            }
+        }
+        if (SLAB) {
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                const long row = r0 + u * RPB + gr;
+                const long rc = row < rows ? row : rows - 1;
+#pragma unroll
+                for (int t = 0; t < NV; ++t) {
+                    const int cc = (cok[t] ? gl + G * t : nv - 1) * 4;
+                    raw_from_sum<T>(dr[u][t], slab_dy_sum(slab + rc * C + cc, nz, zstride));
+                }
             }
         }
         // ---- then row by row ----
@@ -209,29 +261,31 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const T* __restrict__ dy, l
             }
         }
     }
-    // block reduction of the column partials over the RPB row-groups, then one plain store per column
-    __shared__ float red[2][1024];
-    for (int i = threadIdx.x; i < 2048; i += 256) (&red[0][0])[i] = 0.f;
-    __syncthreads();
+    // block reduction of the column partials over the RPB row groups in a FIXED order: every row group stores its registers to its own
+    // LDS row (16-byte stores, no zero-fill, no atomics), then each column is summed over the row groups 0, 1, ... by one thread --
+    // the same (rows, C) gives the same dgamma / dbeta bits on every call.
+    constexpr int COLS = NV * 4 * G;
+    __shared__ float red[RPB][2][COLS];
 #pragma unroll
     for (int t = 0; t < NV; ++t) {
         const int c4 = gl + G * t;
-        if (c4 < nv) {
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                atomicAdd(&red[0][c4 * 4 + e], dg[t][e]);
-                atomicAdd(&red[1][c4 * 4 + e], db[t][e]);
-            }
-        }
+        *reinterpret_cast<f32x4*>(&red[gr][0][c4 * 4]) = dg[t];
+        *reinterpret_cast<f32x4*>(&red[gr][1][c4 * 4]) = db[t];
     }
     __syncthreads();
     // block partials [block][dgamma(Cp) | dbeta(Cp)]: plain stores; fw_slab_reduce folds them (thousands of blocks adding
     // atomically into the same C words serialise in L2 and cost more than the whole LayerNorm pass)
     float* pp = partial + (long)blockIdx.x * pstride;
     const int Cp = (int)(pstride >> 1);
-    for (int c = threadIdx.x; c < Cp; c += 256) {
-        pp[c] = c < C ? red[0][c] : 0.f;
-        pp[Cp + c] = c < C ? red[1][c] : 0.f;
+    for (int c = threadIdx.x; c < Cp; c += TPB) {
+        float a = 0.f, b = 0.f;
+        if (c < C) {
+            a = red[0][0][c]; b = red[0][1][c];
+#pragma unroll
+            for (int k = 1; k < RPB; ++k) { a += red[k][0][c]; b += red[k][1][c]; }
+        }
+        pp[c] = a;
+        pp[Cp + c] = b;
     }
 }
 
@@ -254,21 +308,53 @@ int ln_mod_fwd_launch(const float* x, long ldx, const float* g, const float* b, 
 }
 static inline int ln_group(int C) { return C <= 32 ? 8 : (C <= 64 ? 16 : (C <= 128 ? 32 : 64)); }
 static inline int ln_rows_per_step(int C) { return C <= 256 ? 4 : (C <= 512 ? 2 : 1); }
-// Blocks of the backward pass: every block ends in a fold of its column partials (2 C LDS atomics per lane group, 2 C floats written
-// for fw_slab_reduce to re-read), so wide rows want FEW blocks that walk many rows -- rocprofv3 averages at caps 1024 / 512 / 256:
-// C = 896: 36.2 / 26.7 / 22.1 us, C = 448: 25.6 / 23.4 / 22.3 us, C = 224: 25.7 / 24.4 / 27.9 us, C <= 112: 46.5 / 47.4 / 57.8 us.
+// Blocks of the backward pass (the one source of the number of `partial` rows).  Every block ends in a fold of its column partials and
+// writes 2 C floats for fw_slab_reduce to re-read.  While that fold was a zero-fill of 2048 LDS words plus 2 C LDS float atomics per
+// row group it cost ~9 us a block -- more than the rows of a deep-stage launch -- and the caps below 1024 existed to buy it back with
+// few blocks that walk many rows (averages then at caps 1024 / 512 / 256, C = 896: 36.2 / 26.7 / 22.1 us, C = 448: 25.6 / 23.4 /
+// 22.3 us, C = 224: 25.7 / 24.4 / 27.9 us, C <= 112: 46.5 / 47.4 / 57.8 us).  With the ordered store-then-sum fold the same grids
+// run (rows x C, us on cold operands, bf16 dy, before -> after at 256 threads): 1024 x 896 16.7 -> 7.5, 4096 x 896 27.1 -> 17.8,
+// 4096 x 448 15.5 -> 10.6, 16384 x 448 34.9 -> 30.2, 16384 x 224 21.7 -> 18.9.  What is left for the cap to decide is small;
+// measured again per workgroup size (threads / cap):
+//   4096 x 896  : 256/256 17.8, 256/512 17.2, 512/256 16.6, 512/512 18.6, 1024/256 17.1     (1024 x 896: 7.4 at 256 and 512, 10.2 at 1024)
+//   16384 x 448 : 256/256 30.2, 256/512 27.7, 512/256 27.4, 512/512 25.7, 1024/256 26.5     (4096 x 448: 10.6 / 10.0 / 9.8 / 9.9 / 10.4)
+//   65536 x 224 : 256/512 48.7, 256/1024 47.1, 512/256 49.1, 512/512 47.3, 512/1024 48.0    (16384 x 224: 17.1 / 16.2 / 17.1 / 16.2 / 16.3)
+// 512 threads (8 waves a CU behind one partial row; 1024 threads leave the slab form 128 registers and it spills) with cap 256 above
+// C = 512 and 512 above C = 128.  The C <= 128 forms keep 256 threads and cap 1024.
+constexpr int LN_BWD_WIDE_TPB = 512;     // threads of a backward workgroup at C > 128 (G = 64: 8 row groups); 256 below
 static inline int ln_bwd_grid(int rows, int C) {
-    const int cap = C > 256 ? 256 : (C > 128 ? 512 : 1024);
-    return min(fw_cdiv(rows, 256 / ln_group(C) * ln_rows_per_step(C)), cap);
+    const int tpb = C > 128 ? LN_BWD_WIDE_TPB : 256;
+    const int cap = C > 512 ? 256 : (C > 128 ? 512 : 1024);
+    return min(fw_cdiv(rows, tpb / ln_group(C) * ln_rows_per_step(C)), cap);
 }
 
-template <typename T, int G, int NV, int U>
-int ln_bwd_launch(const void* dy, long lddy, const float* x, long ldx, const float* g, const float* mean,
-                  const float* rstd, const float* dres, long lddres, float* dx, long lddx, float* partial, long pstride,
-                  int rows, int C, void* twin, long ldtw, const float* twscale, int twrps, hipStream_t st) {
-    hipLaunchKernelGGL((ln_bwd_kernel<T, G, NV, U>), dim3(ln_bwd_grid(rows, C)), dim3(256), 0, st, (const T*)dy, lddy, x, ldx, g, mean, rstd,
-                       dres, lddres, dx, lddx, partial, pstride, rows, C, (T*)twin, ldtw, twscale, twrps);
+// dy / lddy: T [rows][lddy], or -- slab != null -- the unfolded split-K slab (slab, nz, zstride) of rows x C contiguous partials
+struct LnBwdArgs {
+    const void* dy; long lddy; const float* slab; int nz; long zstride;
+    const float* x; long ldx; const float* g; const float* mean; const float* rstd; const float* dres; long lddres;
+    float* dx; long lddx; float* partial; long pstride; int rows, C; void* twin; long ldtw; const float* twscale; int twrps;
+};
+template <typename T, int G, int NV, int U, int TPB>
+int ln_bwd_launch(const LnBwdArgs& a, hipStream_t st) {
+    const dim3 grid(ln_bwd_grid(a.rows, a.C)), block(TPB);
+#define LN_BK(SLAB)                                                                                                                  \
+    hipLaunchKernelGGL((ln_bwd_kernel<T, G, NV, U, TPB, SLAB>), grid, block, 0, st, (const T*)a.dy, a.lddy, a.slab, a.nz, a.zstride, a.x, \
+                       a.ldx, a.g, a.mean, a.rstd, a.dres, a.lddres, a.dx, a.lddx, a.partial, a.pstride, a.rows, a.C, (T*)a.twin, a.ldtw, \
+                       a.twscale, a.twrps)
+    if (a.slab) LN_BK(true);
+    else LN_BK(false);
+#undef LN_BK
     FW_LAUNCH_RET();
+}
+template <typename T>
+int ln_bwd_dispatch(const LnBwdArgs& a, hipStream_t st) {
+    const int C = a.C;                             // (G, NV, U) as LN_DISPATCH; the workgroup size as ln_bwd_grid counts it
+    return C <= 32    ? ln_bwd_launch<T, 8, 1, 4, 256>(a, st)
+           : C <= 64  ? ln_bwd_launch<T, 16, 1, 4, 256>(a, st)
+           : C <= 128 ? ln_bwd_launch<T, 32, 1, 4, 256>(a, st)
+           : C <= 256 ? ln_bwd_launch<T, 64, 1, 4, LN_BWD_WIDE_TPB>(a, st)
+           : C <= 512 ? ln_bwd_launch<T, 64, 2, 2, LN_BWD_WIDE_TPB>(a, st)
+                      : ln_bwd_launch<T, 64, 4, 1, LN_BWD_WIDE_TPB>(a, st);
 }
 
 // ---- gradient of the window modulator: dmod[p][c] = sum over the rows r with p(r) = p of dy[r][c] -----------------------------------
@@ -398,22 +484,33 @@ extern "C" int fw_layernorm_bwd_blocks(int rows, int C) { return ln_bwd_grid(row
 // are folded into dgamma / dbeta (accumulated) by fw_slab_reduce, launched here on the same stream -- unless both are null.
 extern "C" int fw_slab_reduce(const float* slab, int nz, long n, long zstride, float* dst, int accumulate, float* dst2, long off2, long n2,
                               void* stream);
+// dy_slab != null: dy is the unfolded slab of the split-K input-gradient GEMM in front -- nz slices, zstride floats apart, each rows x C
+// contiguous f32 partials -- and the kernel sums and rounds it as fw_slab_reduce -> fw_cast_rows would have (dy / lddy are not read).
+extern "C" int fw_layernorm_bwd_slab(int dtype, const void* dy, long lddy, const float* dy_slab, int nz, long zstride, const float* x, long ldx,
+                                     const float* gamma, const float* mean, const float* rstd, const float* dres, long lddres, float* dx,
+                                     long lddx, float* dgamma, float* dbeta, float* partial, int rows, int C, void* twin, long ldtw,
+                                     const float* twscale, int tw_rows_per_scale, void* stream) {
+    FW_CHECK_ARG(rows > 0 && C > 0 && C % 4 == 0 && C <= 1024 && ldx % 4 == 0 && lddx % 4 == 0);
+    FW_CHECK_ARG(x && gamma && mean && rstd && dx && partial && ((dgamma && dbeta) || (!dgamma && !dbeta)));
+    FW_CHECK_ARG(!twin || (ldtw % 4 == 0 && (!twscale || tw_rows_per_scale > 0)));
+    if (dy_slab) FW_CHECK_ARG(nz > 0 && zstride % 4 == 0 && zstride >= (long)rows * C && ((uintptr_t)dy_slab & 15) == 0);
+    else FW_CHECK_ARG(dy && lddy % 4 == 0);
+    hipStream_t st = (hipStream_t)stream;
+    const long pstride = 2L * C;
+    const LnBwdArgs a{dy, lddy, dy_slab, nz, zstride, x, ldx, gamma, mean, rstd, dres, lddres, dx, lddx, partial, pstride, rows, C,
+                      twin, ldtw, twscale, tw_rows_per_scale};
+    const int rc = dtype == FW_DT_BF16 ? ln_bwd_dispatch<bf16raw>(a, st) : ln_bwd_dispatch<float>(a, st);
+    if (rc || !dgamma) return rc;                  // dgamma == dbeta == null: the caller folds the partials later (fw_slab_reduce_multi)
+    return fw_slab_reduce(partial, ln_bwd_grid(rows, C), C, pstride, dgamma, 1, dbeta, C, C, stream);
+}
+
 extern "C" int fw_layernorm_bwd2(int dtype, const void* dy, long lddy, const float* x, long ldx, const float* gamma,
                                  const float* mean, const float* rstd, const float* dres, long lddres, float* dx,
                                  long lddx, float* dgamma, float* dbeta, float* partial, int rows, int C, void* twin, long ldtw,
                                  const float* twscale, int tw_rows_per_scale, void* stream) {
-    FW_CHECK_ARG(rows > 0 && C > 0 && C % 4 == 0 && C <= 1024 && ldx % 4 == 0 && lddy % 4 == 0 && lddx % 4 == 0);
-    FW_CHECK_ARG(dy && x && gamma && mean && rstd && dx && partial && ((dgamma && dbeta) || (!dgamma && !dbeta)));
-    FW_CHECK_ARG(!twin || (ldtw % 4 == 0 && (!twscale || tw_rows_per_scale > 0)));
-    hipStream_t st = (hipStream_t)stream;
-    const long pstride = 2L * C;
-#define LN_B(T)                                                                                                          \
-    LN_DISPATCH(ln_bwd_launch, T, dy, lddy, x, ldx, gamma, mean, rstd, dres, lddres, dx, lddx, partial, pstride, rows, C, twin, \
-                ldtw, twscale, tw_rows_per_scale, st)
-    const int rc = dtype == FW_DT_BF16 ? LN_B(bf16raw) : LN_B(float);
-#undef LN_B
-    if (rc || !dgamma) return rc;                  // dgamma == dbeta == null: the caller folds the partials later (fw_slab_reduce_multi)
-    return fw_slab_reduce(partial, ln_bwd_grid(rows, C), C, pstride, dgamma, 1, dbeta, C, C, stream);
+    FW_CHECK_ARG(dy);
+    return fw_layernorm_bwd_slab(dtype, dy, lddy, nullptr, 0, 0, x, ldx, gamma, mean, rstd, dres, lddres, dx, lddx, dgamma, dbeta, partial,
+                                 rows, C, twin, ldtw, twscale, tw_rows_per_scale, stream);
 }
 
 extern "C" int fw_layernorm_bwd(int dtype, const void* dy, long lddy, const float* x, long ldx, const float* gamma,

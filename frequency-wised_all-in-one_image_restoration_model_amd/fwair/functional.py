@@ -17,6 +17,7 @@ class config:
     compute_dtype = torch.float32       # torch.float32 | torch.bfloat16
     shadow_epoch = 0                    # bumped by the engine after a fused optimizer step
     direct_grads = False                # engine mode: kernels accumulate straight into the (pre-zeroed) flat .grad views
+    lazy_dgrad = True                   # a split-K input gradient whose only reader is a LayerNorm backward stays an unfolded slab
 
 
 def act_empty(rows, cols, dtype, device):
@@ -244,6 +245,40 @@ def _bgrad(g, bias):
 # ---------------------------------------------------------------------------------------------------------------
 # LayerNorm : f32 stream -> T
 # ---------------------------------------------------------------------------------------------------------------
+# Hand-over of an unfolded split-K input gradient (ops.dgrad(lazy=True)) from a Linear's backward to the LayerNorm backward behind it.
+# The LayerNorm forward hangs a cell [consumers, lazy] on its output; every LinearFn / QKVFn that takes that output as a
+# differentiable x counts itself in at forward time.  At backward time a producer may leave its result to the slab only if it is the
+# one consumer counted -- its gradient then reaches the LayerNorm as it is, not summed with another -- and says so in the cell.  The
+# LayerNorm backward reads dy._fw_slab; if a producer went lazy and that attribute did not arrive (the tensor was copied or summed on
+# the way: a consumer the cell cannot see), the buffer it holds was never written and it raises instead of reading it.
+def _ln_publish(ctx, y):
+    ctx.ln_cell = y._fw_ln = [0, False]
+
+
+def _ln_consume(ctx, x):
+    cell = getattr(x, '_fw_ln', None) if ctx.needs_input_grad[0] else None
+    if cell is not None:
+        cell[0] += 1
+    ctx.ln_cell = cell
+
+
+def _ln_may_be_lazy(ctx):
+    return config.lazy_dgrad and ctx.ln_cell is not None and ctx.ln_cell[0] == 1
+
+
+def _ln_take(ctx, dy):
+    """dy as the LayerNorm kernel may read it.  Raises when a producer left its result in a slab that is not attached to dy."""
+    cell = ctx.ln_cell
+    went, cell[1] = cell[1], False
+    if dy is not None and getattr(dy, '_fw_slab', None) is not None:
+        return dy                                   # act_empty rows: aligned already, and nothing may copy the unwritten buffer
+    if went:
+        raise RuntimeError('fwair: a Linear left its input gradient in a split-K slab for this LayerNorm, but the gradient that arrived '
+                           'does not carry it (the LayerNorm output has a consumer that is not a LinearFn / QKVFn, or the gradient was '
+                           'copied on the way); set functional.config.lazy_dgrad = False for such a graph')
+    return aligned(dy) if dy is not None else None
+
+
 class LayerNormFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, gamma, beta):
@@ -254,12 +289,13 @@ class LayerNormFn(torch.autograd.Function):
         call('fw_layernorm_fwd', dt(y.dtype), x, x.stride(0), gamma, beta, y, y.stride(0), mean, rstd, rows, C, 1e-5)
         ctx.save_for_backward(x, gamma, mean, rstd)
         ctx.beta = beta
+        _ln_publish(ctx, y)
         return y
 
     @staticmethod
     def backward(ctx, dy):
         x, gamma, mean, rstd = ctx.saved_tensors
-        dy = aligned(dy)
+        dy = _ln_take(ctx, dy)
         beta = ctx.beta
         dg, rg = _grad_target(gamma)
         db, rb = _grad_target(beta)
@@ -297,6 +333,7 @@ class LinearFn(torch.autograd.Function):
         ctx.save_for_backward(x, weight, rowscale, x_pre)
         ctx.bias = bias
         ctx.cfg = (rows_per_scale, residual is not None)
+        _ln_consume(ctx, x)
         if gelu_out:
             ctx.mark_non_differentiable(g)
             return y, g
@@ -324,7 +361,9 @@ class LinearFn(torch.autograd.Function):
         dx = dpre = None
         if ctx.needs_input_grad[0] or (x_pre is not None and ctx.needs_input_grad[6]):
             d = act_empty(M, K, x.dtype, x.device)
-            ops.dgrad(g, shadow(weight), M, K, N, d, act=2 if x_pre is not None else 0, aux=x_pre)
+            if ops.dgrad(g, shadow(weight), M, K, N, d, act=2 if x_pre is not None else 0, aux=x_pre,
+                         lazy=x_pre is None and _ln_may_be_lazy(ctx)):
+                ctx.ln_cell[1] = True                        # d is unwritten: the LayerNorm backward sums d._fw_slab (see _ln_take)
             if x_pre is not None:
                 dpre = d
             else:
@@ -364,6 +403,7 @@ class LnResFn(torch.autograd.Function):
         call('fw_layernorm_fwd', dt(y.dtype), x, x.stride(0), gamma, beta, y, y.stride(0), mean, rstd, rows, C, 1e-5)
         ctx.save_for_backward(x, gamma, mean, rstd)
         ctx.beta = beta
+        _ln_publish(ctx, y)
         return x.view_as(x), y
 
     @staticmethod
@@ -371,9 +411,9 @@ class LnResFn(torch.autograd.Function):
         x, gamma, mean, rstd = ctx.saved_tensors
         dg, rg = _grad_target(gamma)
         db, rb = _grad_target(ctx.beta)
+        dy = _ln_take(ctx, dy)
         if dy is None:
             return dres, None, None
-        dy = aligned(dy)
         twin = None
         if ctx.rs_hint is not None:
             # the gradient returned here is the dy of the Linear that produced x; its backward wants T(dy * DropPath scale) as the
@@ -459,6 +499,7 @@ class QKVFn(torch.autograd.Function):
             ops.gemm(x, shadow(wkv), M, 2 * C, K, out=buf[:, Cp:], bias=bkv)
         ctx.save_for_backward(x, wq, wkv)
         ctx.bq, ctx.bkv = bq, bkv
+        _ln_consume(ctx, x)
         ctx.fused = (fused, w3)
         return buf
 
@@ -473,7 +514,9 @@ class QKVFn(torch.autograd.Function):
         dx = act_empty(M, K, x.dtype, x.device)
         if w3 is not None and config.direct_grads and 'gw' in fused:
             ops.wgrad(dbuf[:, :3 * C], x, 3 * C, K, M, fused['gw'], fused['gb'], defer=True)
-            ops.dgrad(dbuf[:, :3 * C], w3, M, K, 3 * C, dx)          # split over the 3C reduction when the output has few tiles
+            # split over the 3C reduction when the output has few tiles; the slab goes unfolded to the LayerNorm in front if it can
+            if ops.dgrad(dbuf[:, :3 * C], w3, M, K, 3 * C, dx, lazy=_ln_may_be_lazy(ctx)):
+                ctx.ln_cell[1] = True
             return dx, None, None, None, None, None
         dq, dkv = dbuf[:, :C], dbuf[:, Cp:]
         dwq, dbq = _wgrad(dq, x, C, K, M, wq, ctx.bq)

@@ -393,24 +393,31 @@ def wgrad(g, x, n, k, m, dw, db=None, defer=False):
     slab_reduce(slab, sk, n * k, S, dw, db, nk, n, defer=defer)
 
 
-def dgrad(g, w, M, K, N, out, act=0, aux=None):
+def dgrad(g, w, M, K, N, out, act=0, aux=None, lazy=False):
     """out[M,K] = epi(g[M,N] W[N,K])  (input gradient of a Linear).  A long reduction into a small output -- the 65536-wide
-    mlp_head of the encoder: 32 output tiles, 1024 K-steps each -- is split over N into a slab of partial tiles."""
+    mlp_head of the encoder: 32 output tiles, 1024 K-steps each -- is split over N into a slab of partial tiles.
+    lazy: the caller knows that the only reader of `out` is a LayerNorm backward (layernorm_bwd), which sums the slab while it loads
+    its rows.  A split product then stops after the GEMM: `out` is returned UNWRITTEN, carrying out._fw_slab = (slab, sk, S); an
+    unsplit product writes `out` as always.  -> True when `out` was left to the slab."""
     tiles = ((M + 127) // 128) * ((K + 127) // 128)
     # fewer than 200 output tiles leave the chip to a handful of long K loops (1024 x 896 x 3584: 56 tiles, 56 steps each, 63 us):
     # split the reduction so that one round of the chip is busy, at >= _DGRAD_SPLIT_ROWS reduction rows per slice
     sk = min(512 // max(tiles, 1), N // _DGRAD_SPLIT_ROWS) if (act == 0 and tiles < 200) else 1
     if sk <= 1:
         gemm(g, w, M, K, N, w_trans=True, out=out, act=act, aux=aux)
-        return
+        return False
     S = (M * K + 3) // 4 * 4
     slab = torch.empty((sk, S), dtype=torch.float32, device=g.device)
     gemm(g, w, M, K, N, w_trans=True, out=slab[0, :M * K].view(M, K), splitk=sk, c_zstride=S)
+    if lazy:
+        out._fw_slab = (slab, sk, S)
+        return True
     direct = out.dtype == torch.float32 and out.is_contiguous()
     tmp = out if direct else torch.empty((M, K), dtype=torch.float32, device=g.device)
     call('fw_slab_reduce', slab, sk, M * K, S, tmp, 0, None, 0, 0)
     if not direct:
         call('fw_cast_rows', dt(out.dtype), tmp, K, out, _ld(out), M, K, None, 1)
+    return False
 
 
 # ------------------------------------------------------------------------------------------------ LayerNorm
@@ -424,12 +431,16 @@ def layernorm_fwd(x, gamma, beta, out_dtype, eps=1e-5):
 
 
 def layernorm_bwd(dy, x, gamma, mean, rstd, dgamma, dbeta, dres=None, defer=False, twin=None, twscale=None, tw_rows_per_scale=1):
-    """twin: optional T [rows, C] buffer that also receives dx * twscale[row // tw_rows_per_scale] (see fw_layernorm_bwd2)."""
+    """twin: optional T [rows, C] buffer that also receives dx * twscale[row // tw_rows_per_scale] (see fw_layernorm_bwd2).
+    A dy that carries _fw_slab (dgrad(lazy=True) left it unwritten) is read from that slab (fw_layernorm_bwd_slab)."""
     rows, C = x.shape
     dx = torch.empty((rows, C), dtype=torch.float32, device=x.device)
     nblk = lib().fw_layernorm_bwd_blocks(rows, C)
     partial = torch.empty((nblk, 2 * C), dtype=torch.float32, device=x.device)
-    call('fw_layernorm_bwd2', dt(dy.dtype), dy, _ld(dy), x, _ld(x), gamma, mean, rstd, dres,
+    slab, sk, S = getattr(dy, '_fw_slab', None) or (None, 0, 0)
+    if slab is not None and tuple(dy.shape) != (rows, C):
+        raise RuntimeError(f'fwair: layernorm_bwd: slab gradient of shape {tuple(dy.shape)} for rows of shape {(rows, C)}')
+    call('fw_layernorm_bwd_slab', dt(dy.dtype), None if slab is not None else dy, _ld(dy), slab, sk, S, x, _ld(x), gamma, mean, rstd, dres,
          _ld(dres) if dres is not None else 0, dx, _ld(dx), None, None, partial, rows, C,
          twin, _ld(twin) if twin is not None else 0, twscale, tw_rows_per_scale)
     slab_reduce(partial, nblk, C, 2 * C, dgamma, dbeta, C, C, defer=defer)

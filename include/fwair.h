@@ -75,6 +75,19 @@ int fw_layernorm_bwd2(int dtype, const void* dy, long lddy, const float* x, long
                       const float* rstd, const float* dres, long lddres, float* dx, long lddx, float* dgamma, float* dbeta,
                       float* partial, int rows, int C, void* twin, long ldtw, const float* twscale, int tw_rows_per_scale,
                       void* stream);
+/* Same, with dy taken either as T [rows][lddy] (dy_slab == NULL: exactly fw_layernorm_bwd2) or straight from the unfolded slab of the
+ * split-K input-gradient GEMM in front: dy_slab f32, 16-byte aligned, nz slices zstride floats apart (zstride >= rows * C, a multiple
+ * of 4), each rows x C contiguous partials; dy / lddy are then not read.  A lane sums its vector over the slices in the association
+ * fw_slab_reduce uses with its whole z range in one block -- partial sums of slices j, j + 4, ... for j = 0..3, total
+ * s0 + ((s1 + s2) + s3) -- and rounds it to T as fw_cast_rows does (no rounding for T = f32), so dx and twin are bit for bit those of
+ * fw_slab_reduce(accumulate 0) -> fw_cast_rows -> fw_layernorm_bwd2, and dgamma / dbeta see the same dy, without the two launches and
+ * the f32 and T round trips between them.
+ * All three entries fold a workgroup's column partials through LDS in a fixed order: one (rows, C) gives the same `partial` bits on
+ * every call. */
+int fw_layernorm_bwd_slab(int dtype, const void* dy, long lddy, const float* dy_slab, int nz, long zstride, const float* x, long ldx,
+                          const float* gamma, const float* mean, const float* rstd, const float* dres, long lddres, float* dx,
+                          long lddx, float* dgamma, float* dbeta, float* partial, int rows, int C, void* twin, long ldtw,
+                          const float* twscale, int tw_rows_per_scale, void* stream);
 
 /* ---- learnable window modulator of the decoder blocks (--learnable_modulator; decoder_Uformer.py:536-539,687-691) ----------
  * The reference adds an nn.Embedding(64, C) table to the 64 tokens of every 8x8 window after norm1, the cyclic shift and the window
