@@ -17,16 +17,25 @@ import torch.distributed as dist
 from . import functional as Fn
 from . import ops
 from .lib import call, gc_quiet, graph_capture
+from .losses import ssim11_launch
 
 
 # ---------------------------------------------------------------------------------------------------------------
-# loss  (train.py:88-92):  l1(restored, clean) + w * mean_i CE(logits_i, 0)
+# loss  (train.py:88-92):  l1(restored, clean) + w * mean_i CE(logits_i, 0)  [+ w_s * (1 - SSIM(restored, clean)), --ssim_loss_weight]
 # ---------------------------------------------------------------------------------------------------------------
+def _ssim_term(restored, clean, dres, gscale, ssim):
+    """The optional structural-similarity term w_s * (1 - SSIM) (utils/pytorch_ssim/__init__.py:19-43), ssim = (w_s, value): the kernel
+    adds -w_s * gscale * dSSIM/d restored into the gradient fw_l1_loss just stored (same stream, after it) and leaves SSIM in value[0]."""
+    ws, value = ssim
+    value.zero_()
+    ssim11_launch(restored, clean, dres, -float(ws) * float(gscale), True, value)
+
+
 class TrainLossFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, restored, clean, logits, w, gscale):
+    def forward(ctx, restored, clean, logits, w, gscale, ssim=None):
         """logits: f32 [L, B, 1+K].  Returns f32 [3] = (unused, l1, contrast).  Gradients are pre-multiplied by
-        gscale (1 / world size: a SUM all-reduce then yields the data-parallel mean)."""
+        gscale (1 / world size: a SUM all-reduce then yields the data-parallel mean).  ssim: None or (weight, f32 [1] value buffer)."""
         dev = restored.device
         restored, clean, logits = restored.contiguous(), clean.contiguous(), logits.contiguous()
         out = torch.zeros(3, dtype=torch.float32, device=dev)
@@ -34,6 +43,8 @@ class TrainLossFn(torch.autograd.Function):
         dlog = torch.empty_like(logits)
         L, B, N = logits.shape
         call('fw_l1_loss', restored, clean, dres, restored.numel(), float(gscale), out[1:2])
+        if ssim is not None:
+            _ssim_term(restored, clean, dres, gscale, ssim)
         call('fw_ce0_loss', logits, dlog, L * B, N, float(w) * float(gscale), out[2:3])
         ctx.save_for_backward(dres, dlog)
         ctx.w = float(w)
@@ -43,24 +54,27 @@ class TrainLossFn(torch.autograd.Function):
     def backward(ctx, dout):
         dres, dlog = ctx.saved_tensors
         # d(total) = d(l1) + w d(contrast); the kernels already folded w into dlog.  dout is (1, 0, 0) for total.
-        return dres, None, dlog, None, None
+        return dres, None, dlog, None, None, None
 
 
 class L1LossFn(torch.autograd.Function):
-    """mean |restored - clean| alone (train.py:89), gradient pre-scaled by gscale."""
+    """mean |restored - clean| alone (train.py:89), gradient pre-scaled by gscale.  ssim: None or (weight, f32 [1] value buffer) -- the
+    gradient of weight * (1 - SSIM) then rides in the same buffer (the value returned stays the L1 alone)."""
 
     @staticmethod
-    def forward(ctx, restored, clean, gscale):
+    def forward(ctx, restored, clean, gscale, ssim=None):
         restored, clean = restored.contiguous(), clean.contiguous()
         out = torch.zeros(1, dtype=torch.float32, device=restored.device)
         dres = torch.empty_like(restored)
         call('fw_l1_loss', restored, clean, dres, restored.numel(), float(gscale), out)
+        if ssim is not None:
+            _ssim_term(restored, clean, dres, gscale, ssim)
         ctx.save_for_backward(dres)
         return out
 
     @staticmethod
     def backward(ctx, dout):
-        return ctx.saved_tensors[0], None, None
+        return ctx.saved_tensors[0], None, None, None
 
 
 class ContrastLossFn(torch.autograd.Function):
@@ -81,10 +95,15 @@ class ContrastLossFn(torch.autograd.Function):
         return ctx.saved_tensors[0], None
 
 
-def train_loss(restored, clean, logits, w, gscale=1.0):
-    """-> (total [scalar tensor], l1, contrast); total is differentiable (its backward seeds the kernels' gradients)."""
-    v = TrainLossFn.apply(restored, clean, logits, w, gscale)
-    total = v[1] + w * v[2]
+def train_loss(restored, clean, logits, w, gscale=1.0, ssim=None):
+    """-> (total [scalar tensor], l1, contrast); total is differentiable (its backward seeds the kernels' gradients).
+    ssim = (weight, f32 [1] buffer): total also carries weight * (1 - SSIM), whose gradient the loss kernels already hold."""
+    if ssim is None:
+        v = TrainLossFn.apply(restored, clean, logits, w, gscale)
+        total = v[1] + w * v[2]
+        return total, v[1].detach(), v[2].detach()
+    v = TrainLossFn.apply(restored, clean, logits, w, gscale, ssim)
+    total = v[1] + w * v[2] + ssim[0] * (1.0 - ssim[1][0])
     return total, v[1].detach(), v[2].detach()
 
 
@@ -211,8 +230,10 @@ class GradAllReducer:
 # ---------------------------------------------------------------------------------------------------------------
 class TrainEngine:
     def __init__(self, net, lr=2e-4, contrast_loss_weight=0.6, betas=(0.9, 0.999), eps=1e-8, use_graph=True,
-                 grad_wire_dtype=torch.float32, split_backward=False, freq_l1=None):
+                 grad_wire_dtype=torch.float32, split_backward=False, freq_l1=None, ssim_loss_weight=0.0):
         self.net = net
+        self.ws = float(ssim_loss_weight)                  # weight of the optional term w_s * (1 - SSIM(restored, clean)); 0: the term does not exist
+        self.ssim = None                                   # f32 [1], the step's SSIM: static across graph replays, read by the driver per epoch
         self.freq_l1 = freq_l1                             # (FrequencyDecompose(inverse=False), weight): the optional frequency L1 term of train.py:69-70,90-91
         self.split_backward = split_backward               # force the two-stage backward on a single GPU too (tests)
         self._split = self._gsplit = None
@@ -262,6 +283,8 @@ class TrainEngine:
         self._fuse_tables(net)
         moco._ema_hook = self._ema
         self.allreduce = GradAllReducer(self.flat_g, wire_dtype=grad_wire_dtype)
+        if self.ws > 0:
+            self.ssim = torch.zeros(1, dtype=torch.float32, device=dev)
         Fn.config.shadow_epoch += 1
         Fn.config.direct_grads = True                     # kernels add into the flat .grad views; autograd sees None
         self._graph = None
@@ -345,11 +368,14 @@ class TrainEngine:
         d = (dec(restored.float()) - dec(clean)).abs().mean()
         return d * wgt
 
+    def _ssim_arg(self):
+        return (self.ws, self.ssim) if self.ws > 0 else None
+
     def _fwd_bwd(self, xq, xk, clean):
         self.flat_g.zero_()
         ops.mark_zeroed(self.flat_g)                         # grouped weight gradients may store into it (ops.wgrad)
         restored, logits, labels = self.net(x_query=xq, x_key=xk)
-        total, l1, contrast = train_loss(restored, clean, torch.stack(logits, 0), self.w, 1.0 / self.allreduce.world)
+        total, l1, contrast = train_loss(restored, clean, torch.stack(logits, 0), self.w, 1.0 / self.allreduce.world, self._ssim_arg())
         if self.freq_l1 is not None:
             f = self._freq_term(restored, clean)
             (total + f / self.allreduce.world).backward()
@@ -373,7 +399,7 @@ class TrainEngine:
         inter_d[0]._fw_stack = cut
         restored = self.net.R(xq, inter_d)
         gs = 1.0 / self.allreduce.world
-        l1 = L1LossFn.apply(restored, clean, gs)
+        l1 = L1LossFn.apply(restored, clean, gs, self._ssim_arg()) if self.ws > 0 else L1LossFn.apply(restored, clean, gs)
         if self.freq_l1 is not None:
             f = self._freq_term(restored, clean)
             (l1 + f * gs).backward()
@@ -389,6 +415,8 @@ class TrainEngine:
         torch.autograd.backward([stack, c], [dstack, torch.ones_like(c)])
         self._split = None
         cd = c.detach()
+        if self.ws > 0:                                      # _split_a's loss kernels left the step's SSIM in self.ssim
+            return torch.cat([l1 + self.w * cd + self.ws * (1.0 - self.ssim), l1, cd])
         return torch.cat([l1 + self.w * cd, l1, cd])
 
     def step_split_eager(self, xq, xk, clean):

@@ -4,7 +4,7 @@ derived fields (batch_size, ckpt_path, encoder_dim, lr) follow the reference so 
 plot_*.py drive this package unchanged.  Quirks kept on purpose: `type=bool` flags are truthy
 for any non-empty string; `contrast_loss_weight` stays None unless passed (the reference computes a default into
 a local variable it never uses, option.py:59-64) -- `default_contrast_loss_weight` exposes that intended value.
-Additions (reference-preserving defaults): --compute_dtype, --grad_allreduce_dtype.
+Additions (reference-preserving defaults): --compute_dtype, --grad_allreduce_dtype, --ssim_loss_weight.
 """
 import argparse
 
@@ -53,6 +53,9 @@ _FLAGS = [
                                   'tokens x tokens (the size of the attention map: 64, 256, 576 or 1024).')),
     ('--grad_allreduce_dtype', dict(type=str, default='fp32', choices=['fp32', 'bf16'],
                                     help='wire type of the data-parallel gradient all-reduce.')),
+    ('--ssim_loss_weight', dict(type=float, default=0.0,
+                                help='weight of the term w * (1 - SSIM(restored, clean)) in the phase-2 objective (Gaussian 11x11 window, '
+                                     'utils/pytorch_ssim); 0: the term does not exist.')),
 ]
 
 _TASKS = {

@@ -213,7 +213,8 @@ def main():
         freq = (FrequencyDecompose('frequency_decompose', 1. / opt.num_frequency_bands_l1, opt.patch_size, opt.patch_size, inverse=False),
                 opt.frequency_l1_loss_weight)
     eng = E.TrainEngine(net, lr=opt.lr, contrast_loss_weight=w, use_graph=not _ARGS.no_graph, freq_l1=freq,
-                        grad_wire_dtype=torch.bfloat16 if opt.grad_allreduce_dtype == 'bf16' else torch.float32)
+                        grad_wire_dtype=torch.bfloat16 if opt.grad_allreduce_dtype == 'bf16' else torch.float32,
+                        ssim_loss_weight=opt.ssim_loss_weight)
     start = 0
     if _ARGS.resume:
         net.load_state_dict(torch.load(_ARGS.resume, map_location=dev, weights_only=True))
@@ -244,6 +245,8 @@ def main():
                 line = 'Epoch (%d)  Loss: contrast_loss:%0.4f\n' % (epoch, v[0])
             else:                                                         # train.py:107-117
                 line = 'Epoch (%d)  Loss: l1_loss:%0.4f contrast_loss:%0.4f\n' % (epoch, v[1], v[2])
+                if opt.ssim_loss_weight > 0:                              # --ssim_loss_weight: one trailing field, 1 - SSIM of the epoch's last step
+                    line = line[:-1] + ' ssim_loss:%0.4f\n' % (1.0 - float(eng.ssim))
             dt = time.time() - t0
             print(line.rstrip('\n') + f'   [{n * B * world / max(dt, 1e-9):.1f} images/s]', flush=True)
             log.write(line)

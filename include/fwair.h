@@ -199,6 +199,13 @@ int fw_lrelu_bwd(int dtype, const void* dy, const float* x, float* dx, long n, f
 /* ---- losses (train.py:88-92): loss accumulated into *loss; gradient scaled by gscale ----------------- */
 int fw_l1_loss(const float* a, const float* b, float* da, long n, float gscale, float* loss, void* stream);
 int fw_ce0_loss(const float* logits, float* dlogits, int R, int N, float gscale, float* loss, void* stream);
+/* Structural similarity of the restoration a and the clean image b, both f32 [n][C][H][W] contiguous, 8 <= H, W <= 1024
+ * (utils/pytorch_ssim/__init__.py:19-43: Gaussian 11x11 window, sigma 1.5, zero padding, C1 = 0.01^2, C2 = 0.03^2, mean over the map):
+ * *loss += mean S(a, b); with da != NULL, da (+)= gscale * d mean(S) / d a -- `+=` when accumulate is set, `=` otherwise -- so the term
+ * -w (1 - SSIM) joins the gradient fw_l1_loss stored, stream-ordered after it.  One launch; every da element is written by one thread
+ * (bit-reproducible), the value takes one float atomic per workgroup. */
+int fw_ssim11_loss(const float* a, const float* b, float* da, int n, int C, int H, int W, float gscale, int accumulate, float* loss,
+                   void* stream);
 
 /* ---- Adam (train.py:63,96; torch.optim.Adam defaults) and MoCo EMA (net/utils/moco.py:44-50) ----------
  * hyper: device f32[4] = {lr, beta1^t, beta2^t, t}; fw_adam_tick advances t so graphs replay correctly. */
