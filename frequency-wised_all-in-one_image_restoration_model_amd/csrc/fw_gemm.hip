@@ -19,6 +19,7 @@
 #include <stdio.h>
 #include <string.h>
 #include <stdlib.h>
+#include <type_traits>
 
 namespace {
 // name of the kernel the last fw_gemm call of this thread launched, spelt like rocprofv3's demangled kernel names with spaces
@@ -61,6 +62,36 @@ constexpr int BM = 128;
 FW_DEV unsigned xcd_contiguous(unsigned lin, unsigned total) {
     const unsigned xcd = lin & 7, q = total >> 3, r = total & 7;
     return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (lin >> 3);
+}
+
+// Output tile (bx, by) and K slice bz of this workgroup.  SLICED = false: a kernel that is never launched with K slices (grid z = 1).
+struct TileIdx { int bx, by, bz; };
+template <bool SLICED = true> FW_DEV TileIdx tile_walk() {
+    // Workgroups are dealt round-robin to the 8 XCDs (8 private L2s).  With split-K the tiles of one K slice read the same token
+    // rows: give every XCD one CONTIGUOUS eighth of the (slice, n tile, m tile) order, so that a slice's operands are fetched into
+    // one or two L2s instead of all eight (PMC: 1.9x the algorithmic bytes crossed the fabric with round-robin placement).
+    // (Without split-K, tiles sharing X rows are gridDim.x apart and already meet when gridDim.x % 8 == 0.)
+    int bx = blockIdx.x, by = blockIdx.y, bz = SLICED ? blockIdx.z : 0;
+    const unsigned slices = SLICED ? gridDim.z : 1u, total = gridDim.x * gridDim.y * slices;
+    if (slices > 1) {
+        const unsigned lin = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
+        const unsigned w = xcd_contiguous(lin, total);
+        bx = (int)(w % gridDim.x);
+        by = (int)((w / gridDim.x) % gridDim.y);
+        bz = (int)(w / (gridDim.x * gridDim.y));
+    } else if (slices == 1 && gridDim.y > 1) {
+        // no split-K: every XCD takes a contiguous eighth of a GROUPED tile order (bands of 8 m tiles, n tiles swept inside a
+        // band), so the ~64 tiles an XCD has in flight touch 8 x 8 operand panels that fit its 4 MB L2 instead of re-fetching
+        // X once per n tile (PMC: 2.5x the algorithmic bytes crossed the fabric in plain row-major order)
+        const unsigned lin = blockIdx.x + gridDim.x * blockIdx.y;
+        const unsigned w = xcd_contiguous(lin, total);
+        const unsigned per_band = 8 * gridDim.y;
+        const unsigned band = w / per_band, first = band * 8;
+        const unsigned gsz = min(gridDim.x - first, 8u);
+        bx = (int)(first + (w % per_band) % gsz);
+        by = (int)((w % per_band) / gsz);
+    }
+    return TileIdx{bx, by, bz};
 }
 
 template <typename T> FW_DEV uint4 apply_gelu16(const uint4& v) {
@@ -296,32 +327,8 @@ __global__ __launch_bounds__(256) void gemm_kernel(GemmArgs a) {
     auto ws = [&](int i) -> char* { return smem + i * (XBYTES + WBYTES) + XBYTES; };
 
     const int wave = threadIdx.x >> 6;
-    // Workgroups are dealt round-robin to the 8 XCDs (8 private L2s).  With split-K the tiles of one K slice read the same token
-    // rows: give every XCD one CONTIGUOUS eighth of the (slice, n tile, m tile) order, so that a slice's operands are fetched into
-    // one or two L2s instead of all eight (PMC: 1.9x the algorithmic bytes crossed the fabric with round-robin placement).
-    // (Without split-K, tiles sharing X rows are gridDim.x apart and already meet when gridDim.x % 8 == 0.)
-    int bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
-    {
-        const unsigned total = gridDim.x * gridDim.y * gridDim.z;
-        if (gridDim.z > 1) {
-            const unsigned lin = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
-            const unsigned w = xcd_contiguous(lin, total);
-            bx = (int)(w % gridDim.x);
-            by = (int)((w / gridDim.x) % gridDim.y);
-            bz = (int)(w / (gridDim.x * gridDim.y));
-        } else if (gridDim.z == 1 && gridDim.y > 1) {
-            // no split-K: every XCD takes a contiguous eighth of a GROUPED tile order (bands of 8 m tiles, n tiles swept inside a
-            // band), so the ~64 tiles an XCD has in flight touch 8 x 8 operand panels that fit its 4 MB L2 instead of re-fetching
-            // X once per n tile (PMC: 2.5x the algorithmic bytes crossed the fabric in plain row-major order)
-            const unsigned lin = blockIdx.x + gridDim.x * blockIdx.y;
-            const unsigned w = xcd_contiguous(lin, total);
-            const unsigned per_band = 8 * gridDim.y;
-            const unsigned band = w / per_band, first = band * 8;
-            const unsigned gsz = min(gridDim.x - first, 8u);
-            bx = (int)(first + (w % per_band) % gsz);
-            by = (int)((w % per_band) / gsz);
-        }
-    }
+    const TileIdx t = tile_walk();
+    const int bx = t.bx, by = t.by, bz = t.bz;
     const int m_blk = bx * BM, n_blk = by * BN;
     const int wm0 = (BN == 128) ? (wave & 1) * 64 : wave * 32;
     const int wn0 = (BN == 128) ? (wave >> 1) * 64 : 0;
@@ -616,6 +623,21 @@ FW_DEV void tile_epilogue(const GemmArgs& a, const f32x4 (&acc)[4][WM], int m_bl
 static inline bool plain_epilogue(const GemmArgs& a) {
     return a.act == 0 && !a.rowscale && !a.residual && !a.C2 && a.alpha == 1.0f && !(a.accumulate && a.c_zstride == 0);
 }
+// Launch the PLAIN = true (KP) or the general (KG) instantiation of a kernel, as plain_epilogue decides.  name_fmt: the kernel's name
+// with a trailing %s for PLAIN, name_args: its other template arguments.
+template <void (*KP)(GemmArgs), void (*KG)(GemmArgs), typename... A>
+int launch_pg(const GemmArgs& a, dim3 grid, dim3 block, size_t lds, hipStream_t st, const char* name_fmt, A... name_args) {
+    const bool pl = plain_epilogue(a);
+    FW_KNAME(name_fmt, name_args..., FW_B(pl));
+    if (pl) {
+        FW_SET_LDS_ONCE(KP, lds);
+        hipLaunchKernelGGL(KP, grid, block, lds, st, a);
+    } else {
+        FW_SET_LDS_ONCE(KG, lds);
+        hipLaunchKernelGGL(KG, grid, block, lds, st, a);
+    }
+    FW_LAUNCH_RET();
+}
 
 // ---- that product with a DEEP global -> LDS pipeline ----------------------------------------------------------------
 // XT = true : X token-major as well (dW = dY^T x; bias gradient by ones-MFMA).
@@ -643,23 +665,26 @@ FW_DEV void glds16_asm(const char* gsrc, char* lds_dst) {
 
 // Source pointers of a thread's LDS-DMA instructions for stage 0, computed ONCE (row * ld + swizzled column: 64-bit multiplies);
 // a later stage only adds its K offset.  (Recomputed per stage, the address arithmetic was ~15 VALU instructions per 1 KB moved.)
-// Token-major operand: one [KT tokens][128 cols] tile, a wave-instruction fills 4 token rows (1 KB, lane-linear).
-template <int KT> struct GldsKm {
-    static constexpr int NI = KT / 16;
+// Token-major operand: IMGS [KT tokens][128 cols] images side by side (image h = columns col0 + 128 h ..), WAVES / IMGS waves fill
+// one image each, a wave-instruction fills 4 token rows (1 KB, lane-linear).
+template <int KT, int IMGS = 1, int WAVES = 4> struct GldsKm {
+    static constexpr int WPI = WAVES / IMGS;             // waves per image
+    static constexpr int NI = KT / (4 * WPI);
     const char* src[NI];
     long kstride;                                        // bytes per token row
     int loff[NI];                                        // LDS byte offset of the instruction's 1 KB inside the tile
     FW_MEM void init(const char* base, long ld, int col0, int cols_total, int k0) {
         const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+        const int half = IMGS == 1 ? 0 : wave / WPI, wq = IMGS == 1 ? wave : wave % WPI;
         kstride = ld * 2;
 #pragma unroll
         for (int it = 0; it < NI; ++it) {
-            const int R0 = wave * (KT / 4) + it * 4;
+            const int R0 = wq * (KT / WPI) + it * 4;
             const int r = R0 + (lane >> 4), p = lane & 15;
-            int col = col0 + ((p ^ swz256(r)) << 3);
+            int col = col0 + half * 128 + ((p ^ swz256(r)) << 3);
             if (col >= cols_total) col = 0;                // columns past the matrix only feed masked outputs; stay inside the row
             src[it] = base + ((long)(k0 + r) * ld + col) * 2;
-            loff[it] = R0 * 256;
+            loff[it] = half * KT * 256 + R0 * 256;
         }
     }
     FW_MEM void issue(int step, char* tile) const {
@@ -668,56 +693,43 @@ template <int KT> struct GldsKm {
         for (int it = 0; it < NI; ++it) glds16_asm(src[it] + off, tile + loff[it]);
     }
 };
-// k-contiguous operand: the [ROWS][128 B] image of gemm_kernel (slot swizzle on the source address)
-template <typename T, int ROWS> struct GldsKc {
-    static constexpr int NI = ROWS / 32;
-    const char* src[NI];
-    int loff[NI];
-    FW_MEM void init(const char* base, long ld, int row0, int rows_total, int kbyte0) {
-        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-        for (int it = 0; it < NI; ++it) {
-            const int R0 = (wave * NI + it) * 8;
-            const int r = R0 + (lane >> 3), p = lane & 7;
-            int gr = row0 + r;
-            if (gr >= rows_total) gr = rows_total - 1;     // rows past the end only feed masked outputs
-            src[it] = base + (long)gr * ld * TT<T>::SZ + kbyte0 + ((p ^ (swz(r) >> 4)) << 4);
-            loff[it] = R0 * LDS_ROW;
-        }
-    }
-    FW_MEM void issue(int step, char* tile) const {
-#pragma unroll
-        for (int it = 0; it < NI; ++it) glds16_asm(src[it] + (long)step * 128, tile + loff[it]);
-    }
-};
-
+// k-contiguous operand: [ROWS][ROWB bytes of K] filled by WAVES waves, slot swizzle on the source address.  ROWB = 128: the image of
+// gemm_kernel (slot p of row r holds chunk p ^ swz(r) >> 4; a wave instruction fills 8 rows).  ROWB = 64: slot p of row r holds
+// chunk p ^ swz64(r) (16 consecutive rows x one slot = 64 distinct banks for the fragment's ds_read_b128; 16 rows per instruction).
 constexpr int ROW64 = 64;
 FW_DEV int swz64(int r) { return (r >> 2) & 3; }
-template <typename T, int ROWS> struct GldsKc64 {
-    static constexpr int NI = ROWS / 64;                     // wave instructions per thread and stage (4 waves x 16 rows each)
+template <typename T, int ROWS, int ROWB = LDS_ROW, int WAVES = 4> struct GldsKc {
+    static_assert(ROWB == LDS_ROW || ROWB == ROW64, "row bytes");
+    static constexpr int SLOTS = ROWB / 16, RPI = 64 / SLOTS;  // 16-byte slots per row; rows per wave instruction (1 KB)
+    static constexpr int NI = ROWS / (WAVES * RPI);          // wave instructions per thread and stage
     const char* src[NI];
     int loff[NI];
     FW_MEM void init(const char* base, long ld, int row0, int rows_total, int kbyte0) {
         const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
         for (int it = 0; it < NI; ++it) {
-            const int R0 = (wave * NI + it) * 16;
-            const int r = R0 + (lane >> 2), p = lane & 3;
+            const int R0 = (wave * NI + it) * RPI;
+            const int r = R0 + lane / SLOTS, p = lane % SLOTS;
             int gr = row0 + r;
             if (gr >= rows_total) gr = rows_total - 1;     // rows past the end only feed masked outputs
-            src[it] = base + (long)gr * ld * TT<T>::SZ + kbyte0 + ((p ^ swz64(r)) << 4);
-            loff[it] = R0 * ROW64;
+            src[it] = base + (long)gr * ld * TT<T>::SZ + kbyte0 + ((p ^ (ROWB == LDS_ROW ? swz(r) >> 4 : swz64(r))) << 4);
+            loff[it] = R0 * ROWB;
         }
     }
     FW_MEM void issue(int step, char* tile) const {
 #pragma unroll
-        for (int it = 0; it < NI; ++it) glds16_asm(src[it] + (long)step * ROW64, tile + loff[it]);
+        for (int it = 0; it < NI; ++it) glds16_asm(src[it] + (long)step * ROWB, tile + loff[it]);
     }
 };
 FW_DEV uint4 frag_sw64(const char* tile, int row0) {
     const int l = lane_id();
     const int row = row0 + (l & 15);
     return *reinterpret_cast<const uint4*>(tile + row * ROW64 + (((l >> 4) ^ swz64(row)) << 4));
+}
+// MFMA fragment of rows row0 .. row0+15, K chunk c (64 B), of a k-contiguous tile with ROWB-byte rows (a 64-byte row is one chunk)
+template <int ROWB> FW_DEV uint4 frag(const char* tile, int row0, int chunk) {
+    if constexpr (ROWB == ROW64) return frag_sw64(tile, row0);
+    else return frag_sw(tile, row0, chunk);
 }
 
 // ---- bf16 epilogue through LDS: full 128-byte row segments instead of 8-byte pieces ---------------------------------------------------
@@ -808,7 +820,7 @@ FW_DEV void tr_ring_tile(const GemmArgs& a, int bx, int by, int bz, char* smem) 
     using T = bf16raw;
     static_assert(NS == 2 || NS == 3, "ring depth");
     constexpr int WM = 4;
-    constexpr bool X64 = !XT && KT == 32;                      // k-contiguous X in 64-byte rows (GldsKc64): 32-deep steps, e.g. K = 224
+    constexpr bool X64 = !XT && KT == 32;                      // k-contiguous X in 64-byte rows (GldsKc<.., ROW64>): 32-deep steps, e.g. K = 224
     constexpr int XB = XT ? KT * 256 : 128 * (X64 ? ROW64 : LDS_ROW), WB = KT * 256, STAGE = XB + WB;
     constexpr int LPS = (XT ? KT / 16 : (X64 ? 2 : 4)) + KT / 16;          // global_load_lds instructions per thread and stage
     auto xs = [&](int i) -> char* { return smem + i * STAGE; };
@@ -831,7 +843,7 @@ FW_DEV void tr_ring_tile(const GemmArgs& a, int bx, int by, int bz, char* smem) 
     gw.init(a.W, a.ldw, n_blk, a.N, k_begin);
     GldsKm<XT ? KT : 16> gxm;
     GldsKc<T, BM> gxc;
-    GldsKc64<T, BM> gxc64;
+    GldsKc<T, BM, ROW64> gxc64;
     if constexpr (XT) gxm.init(a.X, a.ldx, m_blk, a.M, k_begin);
     else if constexpr (X64) gxc64.init(a.X, a.ldx, m_blk, a.M, k_begin * 2);
     else gxc.init(a.X, a.ldx, m_blk, a.M, k_begin * 2);
@@ -893,26 +905,8 @@ FW_DEV void tr_ring_tile(const GemmArgs& a, int bx, int by, int bz, char* smem) 
 template <bool XT, int KT, int NS, bool PLAIN>
 __global__ __launch_bounds__(256, KT == 32 ? 3 : 2) void gemm_tr_ring_kernel(GemmArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    int bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
-    {                                                     // contiguous eighths of the (slice, n tile, m tile) order per XCD, see gemm_kernel
-        const unsigned total = gridDim.x * gridDim.y * gridDim.z;
-        if (gridDim.z > 1) {
-            const unsigned lin = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
-            const unsigned w = xcd_contiguous(lin, total);
-            bx = (int)(w % gridDim.x);
-            by = (int)((w / gridDim.x) % gridDim.y);
-            bz = (int)(w / (gridDim.x * gridDim.y));
-        } else if (gridDim.z == 1 && gridDim.y > 1) {
-            const unsigned lin = blockIdx.x + gridDim.x * blockIdx.y;
-            const unsigned w = xcd_contiguous(lin, total);
-            const unsigned per_band = 8 * gridDim.y;
-            const unsigned band = w / per_band, first = band * 8;
-            const unsigned gsz = min(gridDim.x - first, 8u);
-            bx = (int)(first + (w % per_band) % gsz);
-            by = (int)((w % per_band) / gsz);
-        }
-    }
-    tr_ring_tile<XT, KT, NS, PLAIN>(a, bx, by, bz, smem);
+    const TileIdx t = tile_walk();
+    tr_ring_tile<XT, KT, NS, PLAIN>(a, t.bx, t.by, t.bz, smem);
 }
 
 // ---- every weight gradient of a backward pass in ONE launch ------------------------------------------------------------------------
@@ -1035,63 +1029,57 @@ __global__ __launch_bounds__(512) void gemm_wgrad_group_big_kernel(const GemmArg
     else tr_big_tile<false>(a, it.y, it.z, it.w, smem);
 }
 
-template <bool XT, int KT, int NS, bool PLAIN>
-int launch_tr_ring_p(const GemmArgs& a, hipStream_t st) {
-    const size_t lds = (size_t)NS * ((XT ? KT * 256 : 128 * ((KT == 32) ? ROW64 : LDS_ROW)) + KT * 256);
-    FW_SET_LDS_ONCE((gemm_tr_ring_kernel<XT, KT, NS, PLAIN>), lds);
-    FW_KNAME("gemm_tr_ring_kernel<%s,%d,%d,%s>", FW_B(XT), KT, NS, FW_B(PLAIN));
-    hipLaunchKernelGGL((gemm_tr_ring_kernel<XT, KT, NS, PLAIN>), dim3(fw_cdiv(a.M, 128), fw_cdiv(a.N, 128), a.splitk), dim3(256), lds, st, a);
-    FW_LAUNCH_RET();
-}
 template <bool XT, int KT, int NS>
 int launch_tr_ring(const GemmArgs& a, hipStream_t st) {
-    return plain_epilogue(a) ? launch_tr_ring_p<XT, KT, NS, true>(a, st) : launch_tr_ring_p<XT, KT, NS, false>(a, st);
+    const size_t lds = (size_t)NS * ((XT ? KT * 256 : 128 * ((KT == 32) ? ROW64 : LDS_ROW)) + KT * 256);
+    return launch_pg<gemm_tr_ring_kernel<XT, KT, NS, true>, gemm_tr_ring_kernel<XT, KT, NS, false>>(
+        a, dim3(fw_cdiv(a.M, 128), fw_cdiv(a.N, 128), a.splitk), dim3(256), lds, st, "gemm_tr_ring_kernel<%s,%d,%d,%s>", FW_B(XT), KT, NS);
 }
 
-// ---- gemm_kernel's NT product (both operands k-contiguous, whole 128-byte K steps) on the same ring ---------------------
-// Forward Linears of the C >= 224 stages, im2col / pixel-shuffle convolutions: y = x W^T.  Stage = [128 + BN rows][128 B].
-// Two stages (BN = 128: 2 x 32 KB, two workgroups per CU), or three of 24 KB at BN = 64 (still two workgroups per CU).  Deeper
-// rings at BN = 128 (3 or 4 stages, one resident workgroup) measured slower and were removed; git history has them.
-template <typename T, int BN, int NS, bool PLAIN>
-__global__ __launch_bounds__(256) void gemm_ring_kernel(GemmArgs a) {
-    constexpr int KT = 128 / TT<T>::SZ;
-    constexpr int WM = (BN == 128) ? 4 : 2;
-    constexpr int XBYTES = BM * LDS_ROW, WBYTES = BN * LDS_ROW, STAGE = XBYTES + WBYTES;
-    constexpr int LPS = BM / 32 + BN / 32;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    auto xs = [&](int i) -> char* { return smem + i * STAGE; };
-    auto ws = [&](int i) -> char* { return smem + i * STAGE + XBYTES; };
+// ---- the ring core: X k-contiguous, both operands by LDS-DMA, one TM x TN output tile per workgroup -------------------------------
+// The ring discipline of tr_ring_tile (NS stages, counted vmcnt, one raw barrier per stage) for the products whose X is [M][K]:
+// gemm_ring_kernel and gemm_ring64_kernel below are instantiations of ring_tile and differ only in the geometry RingGeom derives;
+// gemm_big_kernel and gemm_wide_kernel are the same loop written out in the kernel (see there).  A wave owns 64 columns (4 MFMA tiles
+// along n) and WM tiles along m.  A K step is one LDS row of ROWB bytes (128 or 64).  WT (the 256-wide kernels only): W stored [K][N]
+// (bf16): its tile is TN / 128 token-major [KT][128] images (GldsKm, frag_tr256).
+template <typename T, int TM, int TN, int WAVES, int ROWB, int NS, bool WT> struct RingGeom {
+    static constexpr int KT = ROWB / TT<T>::SZ;                        // k elements per step
+    static constexpr int MW = WAVES / (TN / 64);                       // waves along m
+    static constexpr int WM = TM / (16 * MW);                          // m tiles (16) per wave
+    static constexpr int XB = TM * ROWB, WB = WT ? (TN / 128) * KT * 256 : TN * ROWB, STAGE = XB + WB;
+    static constexpr size_t EPI = (size_t)WAVES * 16 * WM * EPI_LD;    // the staged epilogue's regions, one per wave
+    static constexpr size_t LDS = (size_t)NS * STAGE > EPI ? (size_t)NS * STAGE : EPI;   // dynamic LDS of a launch
+};
+// Wait until at most the loads of the stages that may stay in flight are outstanding: `younger` stages were issued after the one about
+// to be consumed (NS - 2 in the steady state, fewer near the tail), LPS loads per thread and stage, loads complete in issue order.
+template <int NS, int LPS, int Y = NS - 2> FW_DEV void ring_wait(int younger) {
+    if constexpr (Y <= 0) wait_vmcnt<0>();
+    else if (younger >= Y) wait_vmcnt<Y * LPS>();
+    else ring_wait<NS, LPS, Y - 1>(younger);
+}
+template <typename T, int TM, int TN, int WAVES, int ROWB, int NS, bool PLAIN>
+FW_DEV void ring_tile(const GemmArgs& a, char* smem) {
+    using G = RingGeom<T, TM, TN, WAVES, ROWB, NS, false>;
+    constexpr int KT = G::KT, WM = G::WM;
+    static_assert((size_t)NS * G::STAGE >= G::EPI, "the staged epilogue's regions must fit the ring's LDS");
+    using GldsX = GldsKc<T, TM, ROWB, WAVES>;
+    using GldsW = GldsKc<T, TN, ROWB, WAVES>;
+    constexpr int LPS = GldsX::NI + GldsW::NI;                         // global_load_lds instructions per thread and stage
+    auto xs = [&](int i) -> char* { return smem + i * G::STAGE; };
+    auto ws = [&](int i) -> char* { return smem + i * G::STAGE + G::XB; };
     const int wave = threadIdx.x >> 6;
-    int bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
-    {
-        const unsigned total = gridDim.x * gridDim.y * gridDim.z;
-        if (gridDim.z > 1) {
-            const unsigned lin = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
-            const unsigned w = xcd_contiguous(lin, total);
-            bx = (int)(w % gridDim.x);
-            by = (int)((w / gridDim.x) % gridDim.y);
-            bz = (int)(w / (gridDim.x * gridDim.y));
-        } else if (gridDim.z == 1 && gridDim.y > 1) {
-            const unsigned lin = blockIdx.x + gridDim.x * blockIdx.y;
-            const unsigned w = xcd_contiguous(lin, total);
-            const unsigned per_band = 8 * gridDim.y;
-            const unsigned band = w / per_band, first = band * 8;
-            const unsigned gsz = min(gridDim.x - first, 8u);
-            bx = (int)(first + (w % per_band) % gsz);
-            by = (int)((w % per_band) / gsz);
-        }
-    }
-    const int m_blk = bx * BM, n_blk = by * BN;
-    const int wm0 = (BN == 128) ? (wave & 1) * 64 : wave * 32;
-    const int wn0 = (BN == 128) ? (wave >> 1) * 64 : 0;
-    const int k_begin = bz * a.kper;
+    const TileIdx t = tile_walk();
+    const int m_blk = t.bx * TM, n_blk = t.by * TN;
+    // (MW == WAVES, the 64-wide tile: written out, since the compiler does not fold wave % WAVES and wave / WAVES -- 4 VGPRs)
+    const int wm0 = (G::MW == WAVES ? wave : wave % G::MW) * (16 * WM), wn0 = (G::MW == WAVES ? 0 : wave / G::MW) * 64;
+    const int k_begin = t.bz * a.kper;
     const int k_end = min(a.K, k_begin + a.kper);
-    const int nsteps = (k_end - k_begin) / KT;           // whole steps (host: K % KT == 0)
+    const int nsteps = (k_end - k_begin) / KT;           // whole steps (host: K and kper are multiples of KT)
 
     f32x4 acc[4][WM];
     zero_acc(acc);
-    GldsKc<T, BM> gx;
-    GldsKc<T, BN> gw;
+    GldsX gx;
+    GldsW gw;
     gx.init(a.X, a.ldx, m_blk, a.M, k_begin * TT<T>::SZ);
     gw.init(a.W, a.ldw, n_blk, a.N, k_begin * TT<T>::SZ);
     auto issue = [&](int step, int buf) {
@@ -1103,19 +1091,18 @@ __global__ __launch_bounds__(256) void gemm_ring_kernel(GemmArgs a) {
         if (p < nsteps) issue(p, p);
     int buf = 0;
     for (int s = 0; s < nsteps; ++s) {
-        const int younger = min(NS - 2, nsteps - 1 - s);
-        if (younger >= NS - 2) wait_vmcnt<(NS - 2) * LPS>();
-        else wait_vmcnt<0>();
+        ring_wait<NS, LPS>(nsteps - 1 - s);
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
-        if (s + NS - 1 < nsteps) issue(s + NS - 1, buf == 0 ? NS - 1 : buf - 1);
+        if (s + NS - 1 < nsteps) issue(s + NS - 1, buf == 0 ? NS - 1 : buf - 1);   // the buffer step s-1 has just released
+        const char* xt = xs(buf); const char* wt = ws(buf);
 #pragma unroll
-        for (int c = 0; c < 2; ++c) {
+        for (int c = 0; c < ROWB / 64; ++c) {
             uint4 af[4], bfr[WM];
 #pragma unroll
-            for (int m = 0; m < 4; ++m) af[m] = frag_sw(ws(buf), wn0 + 16 * m, c);
+            for (int m = 0; m < 4; ++m) af[m] = frag<ROWB>(wt, wn0 + 16 * m, c);
 #pragma unroll
-            for (int n = 0; n < WM; ++n) bfr[n] = frag_sw(xs(buf), wm0 + 16 * n, c);
+            for (int n = 0; n < WM; ++n) bfr[n] = frag<ROWB>(xt, wm0 + 16 * n, c);
 #pragma unroll
             for (int m = 0; m < 4; ++m)
 #pragma unroll
@@ -1124,27 +1111,29 @@ __global__ __launch_bounds__(256) void gemm_ring_kernel(GemmArgs a) {
         buf = buf + 1 == NS ? 0 : buf + 1;
     }
     if constexpr (sizeof(T) == 2) {
-        if (a.staged >= 0 && (size_t)NS * STAGE >= (size_t)4 * 16 * WM * EPI_LD) {
-            __syncthreads();
+        if (a.staged >= 0) {
+            __syncthreads();                               // every wave has left the ring: its space stages the output rows
             tile_epilogue_staged<WM>(a, acc, m_blk, n_blk, wm0, wn0, smem, a.staged);
             return;
         }
     }
-    tile_epilogue<T, WM, PLAIN>(a, acc, m_blk, n_blk, wm0, wn0, bz);
+    tile_epilogue<T, WM, PLAIN>(a, acc, m_blk, n_blk, wm0, wn0, t.bz);
 }
 
+// ---- gemm_kernel's NT product (both operands k-contiguous, whole 128-byte K steps) on the same ring ---------------------
+// Forward Linears of the C >= 224 stages, im2col / pixel-shuffle convolutions: y = x W^T.  Stage = [128 + BN rows][128 B].
+// Two stages (BN = 128: 2 x 32 KB, two workgroups per CU), or three of 24 KB at BN = 64 (still two workgroups per CU).  Deeper
+// rings at BN = 128 (3 or 4 stages, one resident workgroup) measured slower and were removed; git history has them.
 template <typename T, int BN, int NS, bool PLAIN>
-int launch_ring_p(const GemmArgs& a, hipStream_t st) {
-    const size_t lds = (size_t)NS * (BM + BN) * LDS_ROW;
-    FW_SET_LDS_ONCE((gemm_ring_kernel<T, BN, NS, PLAIN>), lds);
-    dim3 grid(fw_cdiv(a.M, BM), fw_cdiv(a.N, BN), a.splitk);
-    FW_KNAME("gemm_ring_kernel<%s,%d,%d,%s>", tname<T>(), BN, NS, FW_B(PLAIN));
-    hipLaunchKernelGGL((gemm_ring_kernel<T, BN, NS, PLAIN>), grid, dim3(256), lds, st, a);
-    FW_LAUNCH_RET();
+__global__ __launch_bounds__(256) void gemm_ring_kernel(GemmArgs a) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    ring_tile<T, BM, BN, 4, LDS_ROW, NS, PLAIN>(a, smem);
 }
 template <typename T, int BN, int NS>
 int launch_ring(const GemmArgs& a, hipStream_t st) {
-    return plain_epilogue(a) ? launch_ring_p<T, BN, NS, true>(a, st) : launch_ring_p<T, BN, NS, false>(a, st);
+    return launch_pg<gemm_ring_kernel<T, BN, NS, true>, gemm_ring_kernel<T, BN, NS, false>>(
+        a, dim3(fw_cdiv(a.M, BM), fw_cdiv(a.N, BN), a.splitk), dim3(256), RingGeom<T, BM, BN, 4, LDS_ROW, NS, false>::LDS, st,
+        "gemm_ring_kernel<%s,%d,%d,%s>", tname<T>(), BN, NS);
 }
 
 // ---- the NT product on 64-BYTE K steps: three 16 KB stages (BN = 128), two loads in flight, three workgroups per CU ----------
@@ -1156,96 +1145,15 @@ int launch_ring(const GemmArgs& a, hipStream_t st) {
 // Also takes K that is a multiple of 64 bytes but not of 128 (K = 224, 672 in bf16).
 template <typename T, int BN, int NS, bool PLAIN>
 __global__ __launch_bounds__(256) void gemm_ring64_kernel(GemmArgs a) {
-    constexpr int KT = ROW64 / TT<T>::SZ;
-    constexpr int WM = (BN == 128) ? 4 : 2;
-    constexpr int XBYTES = BM * ROW64, WBYTES = BN * ROW64, STAGE = XBYTES + WBYTES;
-    constexpr int LPS = BM / 64 + BN / 64;
     static_assert(NS >= 3, "ring depth");
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    auto xs = [&](int i) -> char* { return smem + i * STAGE; };
-    auto ws = [&](int i) -> char* { return smem + i * STAGE + XBYTES; };
-    const int wave = threadIdx.x >> 6;
-    int bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
-    {
-        const unsigned total = gridDim.x * gridDim.y * gridDim.z;
-        if (gridDim.z > 1) {
-            const unsigned lin = blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z);
-            const unsigned w = xcd_contiguous(lin, total);
-            bx = (int)(w % gridDim.x);
-            by = (int)((w / gridDim.x) % gridDim.y);
-            bz = (int)(w / (gridDim.x * gridDim.y));
-        } else if (gridDim.z == 1 && gridDim.y > 1) {
-            const unsigned lin = blockIdx.x + gridDim.x * blockIdx.y;
-            const unsigned w = xcd_contiguous(lin, total);
-            const unsigned per_band = 8 * gridDim.y;
-            const unsigned band = w / per_band, first = band * 8;
-            const unsigned gsz = min(gridDim.x - first, 8u);
-            bx = (int)(first + (w % per_band) % gsz);
-            by = (int)((w % per_band) / gsz);
-        }
-    }
-    const int m_blk = bx * BM, n_blk = by * BN;
-    const int wm0 = (BN == 128) ? (wave & 1) * 64 : wave * 32;
-    const int wn0 = (BN == 128) ? (wave >> 1) * 64 : 0;
-    const int k_begin = bz * a.kper;
-    const int k_end = min(a.K, k_begin + a.kper);
-    const int nsteps = (k_end - k_begin) / KT;           // whole steps (host: K and kper are multiples of KT)
-
-    f32x4 acc[4][WM];
-    zero_acc(acc);
-    GldsKc64<T, BM> gx;
-    GldsKc64<T, BN> gw;
-    gx.init(a.X, a.ldx, m_blk, a.M, k_begin * TT<T>::SZ);
-    gw.init(a.W, a.ldw, n_blk, a.N, k_begin * TT<T>::SZ);
-    auto issue = [&](int step, int buf) {
-        gx.issue(step, xs(buf));
-        gw.issue(step, ws(buf));
-    };
-#pragma unroll
-    for (int p = 0; p < NS - 1; ++p)
-        if (p < nsteps) issue(p, p);
-    int buf = 0;
-    for (int s = 0; s < nsteps; ++s) {
-        const int younger = min(NS - 2, nsteps - 1 - s);
-        if (younger >= NS - 2) wait_vmcnt<(NS - 2) * LPS>();
-        else if (younger == NS - 3) wait_vmcnt<(NS - 3) * LPS>();
-        else wait_vmcnt<0>();
-        __builtin_amdgcn_s_barrier();
-        asm volatile("" ::: "memory");
-        if (s + NS - 1 < nsteps) issue(s + NS - 1, buf == 0 ? NS - 1 : buf - 1);
-        uint4 af[4], bfr[WM];
-#pragma unroll
-        for (int m = 0; m < 4; ++m) af[m] = frag_sw64(ws(buf), wn0 + 16 * m);
-#pragma unroll
-        for (int n = 0; n < WM; ++n) bfr[n] = frag_sw64(xs(buf), wm0 + 16 * n);
-#pragma unroll
-        for (int m = 0; m < 4; ++m)
-#pragma unroll
-            for (int n = 0; n < WM; ++n) mma_chunk<T>(acc[m][n], af[m], bfr[n]);
-        buf = buf + 1 == NS ? 0 : buf + 1;
-    }
-    if constexpr (sizeof(T) == 2) {
-        if (a.staged >= 0 && (size_t)NS * STAGE >= (size_t)4 * 16 * WM * EPI_LD) {
-            __syncthreads();
-            tile_epilogue_staged<WM>(a, acc, m_blk, n_blk, wm0, wn0, smem, a.staged);
-            return;
-        }
-    }
-    tile_epilogue<T, WM, PLAIN>(a, acc, m_blk, n_blk, wm0, wn0, bz);
-}
-
-template <typename T, int BN, int NS, bool PLAIN>
-int launch_ring64_p(const GemmArgs& a, hipStream_t st) {
-    const size_t lds = (size_t)NS * (BM + BN) * ROW64;
-    FW_SET_LDS_ONCE((gemm_ring64_kernel<T, BN, NS, PLAIN>), lds);
-    dim3 grid(fw_cdiv(a.M, BM), fw_cdiv(a.N, BN), a.splitk);
-    FW_KNAME("gemm_ring64_kernel<%s,%d,%d,%s>", tname<T>(), BN, NS, FW_B(PLAIN));
-    hipLaunchKernelGGL((gemm_ring64_kernel<T, BN, NS, PLAIN>), grid, dim3(256), lds, st, a);
-    FW_LAUNCH_RET();
+    ring_tile<T, BM, BN, 4, ROW64, NS, PLAIN>(a, smem);
 }
 template <typename T, int BN, int NS>
 int launch_ring64(const GemmArgs& a, hipStream_t st) {
-    return plain_epilogue(a) ? launch_ring64_p<T, BN, NS, true>(a, st) : launch_ring64_p<T, BN, NS, false>(a, st);
+    return launch_pg<gemm_ring64_kernel<T, BN, NS, true>, gemm_ring64_kernel<T, BN, NS, false>>(
+        a, dim3(fw_cdiv(a.M, BM), fw_cdiv(a.N, BN), a.splitk), dim3(256), RingGeom<T, BM, BN, 4, ROW64, NS, false>::LDS, st,
+        "gemm_ring64_kernel<%s,%d,%d,%s>", tname<T>(), BN, NS);
 }
 
 // ---- 256 x 256 tiles, 8 waves: the compute-bound products (C = 448 / 896 stages, the 65 536-wide encoder heads) --------------------
@@ -1256,69 +1164,33 @@ int launch_ring64(const GemmArgs& a, hipStream_t st) {
 // (16 for 32 before).  Same ring discipline as gemm_ring_kernel (LDS-DMA from inline asm, counted vmcnt, one raw barrier per stage):
 // 64-deep steps, 2 stages x 64 KB (128-byte rows).  (32-deep steps in 3 or 4 stages of 32 KB lost to it and were removed.)
 // WT: W stored [K][N] (input gradients dX = dY W): its tile is two [KT][128] token-major images read with ds_read_b64_tr_b16.
+// This kernel and gemm_wide_kernel keep the ring loop written out IN the kernel, with the ring core's parts (keep the three loops in
+// step).  Once the body is a function called with the argument block the compiler loads that block differently, and with 128
+// accumulator registers per wave that is enough to change the result: as an instantiation of ring_tile the WT forms here spill 64 / 192
+// bytes of scratch instead of 32 / 160, and gemm_wide_kernel<*, true> loses the order of its K loop (all 12 fragment reads first, the
+// last two W fragments behind lgkmcnt(1)) and 1 - 2 % of its speed.  Neither is ever launched with K slices: tile_walk<false>.
+// The a.dbg measurement switches live here only.
 template <bool WT, bool PLAIN>
 __global__ __launch_bounds__(512) void gemm_big_kernel(GemmArgs a) {
     using T = bf16raw;
-    constexpr int KT = 64, NS = 2, WM = 8, BIG = 256;
-    constexpr int XB = BIG * LDS_ROW, WB = WT ? 2 * KT * 256 : XB, STAGE = XB + WB;
-    constexpr int NIX = 4, NIW = 4, LPS = NIX + NIW;
+    using G = RingGeom<T, 256, 256, 8, LDS_ROW, 2, WT>;
+    constexpr int KT = G::KT, NS = 2, WM = G::WM;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    auto xs = [&](int i) -> char* { return smem + i * STAGE; };
-    auto ws = [&](int i) -> char* { return smem + i * STAGE + XB; };
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int bx = blockIdx.x, by = blockIdx.y;
-    if (gridDim.y > 1) {                                   // XCD-contiguous, banded tile order (see gemm_kernel)
-        const unsigned total = gridDim.x * gridDim.y;
-        const unsigned lin = blockIdx.x + gridDim.x * blockIdx.y;
-        const unsigned w = xcd_contiguous(lin, total);
-        const unsigned per_band = 8 * gridDim.y;
-        const unsigned band = w / per_band, first = band * 8;
-        const unsigned gsz = min(gridDim.x - first, 8u);
-        bx = (int)(first + (w % per_band) % gsz);
-        by = (int)((w % per_band) / gsz);
-    }
-    const int m_blk = bx * BIG, n_blk = by * BIG;
+    auto xs = [&](int i) -> char* { return smem + i * G::STAGE; };
+    auto ws = [&](int i) -> char* { return smem + i * G::STAGE + G::XB; };
+    const int wave = threadIdx.x >> 6;
+    const TileIdx t = tile_walk<false>();
+    const int m_blk = t.bx * 256, n_blk = t.by * 256;
     const int wm0 = (wave & 1) * 128, wn0 = (wave >> 1) * 64;
     const int nsteps = a.K / KT;
-
-    // per-thread LDS-DMA sources of stage 0 (a later stage adds its K offset) and destinations inside a stage
-    const char* xsrc[NIX]; int xoff[NIX];
-    const char* wsrc[NIW]; int woff[NIW];
-    long wkstride = 0;
-#pragma unroll
-    for (int it = 0; it < NIX; ++it) {
-        const int R0 = (wave * NIX + it) * 8, r = R0 + (lane >> 3), p = lane & 7;
-        int gr = m_blk + r; if (gr >= a.M) gr = a.M - 1;
-        xsrc[it] = a.X + (long)gr * a.ldx * 2 + ((p ^ (swz(r) >> 4)) << 4);
-        xoff[it] = R0 * LDS_ROW;
-    }
-    if constexpr (!WT) {
-#pragma unroll
-        for (int it = 0; it < NIW; ++it) {
-            const int R0 = (wave * NIW + it) * 8, r = R0 + (lane >> 3), p = lane & 7;
-            int gr = n_blk + r; if (gr >= a.N) gr = a.N - 1;
-            wsrc[it] = a.W + (long)gr * a.ldw * 2 + ((p ^ (swz(r) >> 4)) << 4);
-            woff[it] = R0 * LDS_ROW;
-        }
-    } else {
-        // waves 0-3 fill the [KT][128] image of columns n_blk .. +127, waves 4-7 that of n_blk + 128 .. +255 (4 token rows per instruction)
-        const int half = wave >> 2, wq = wave & 3;
-        wkstride = a.ldw * 2;
-#pragma unroll
-        for (int it = 0; it < NIW; ++it) {
-            const int R0 = wq * (KT / 4) + it * 4, r = R0 + (lane >> 4), p = lane & 15;
-            int col = n_blk + half * 128 + ((p ^ swz256(r)) << 3);
-            if (col >= a.N) col = 0;
-            wsrc[it] = a.W + ((long)r * a.ldw + col) * 2;
-            woff[it] = half * KT * 256 + R0 * 256;
-        }
-    }
+    GldsKc<T, 256, LDS_ROW, 8> gx;
+    std::conditional_t<WT, GldsKm<KT, 2, 8>, GldsKc<T, 256, LDS_ROW, 8>> gw;
+    constexpr int LPS = decltype(gx)::NI + decltype(gw)::NI;
+    gx.init(a.X, a.ldx, m_blk, a.M, 0);
+    gw.init(a.W, a.ldw, n_blk, a.N, 0);
     auto issue = [&](int step, int buf) {
-        char* xt = xs(buf); char* wt = ws(buf);
-#pragma unroll
-        for (int it = 0; it < NIX; ++it) glds16_asm(xsrc[it] + (long)step * KT * 2, xt + xoff[it]);
-#pragma unroll
-        for (int it = 0; it < NIW; ++it) glds16_asm(wsrc[it] + (WT ? (long)step * KT * wkstride : (long)step * KT * 2), wt + woff[it]);
+        gx.issue(step, xs(buf));
+        gw.issue(step, ws(buf));
     };
     f32x4 acc[4][WM];
     zero_acc(acc);
@@ -1328,9 +1200,7 @@ __global__ __launch_bounds__(512) void gemm_big_kernel(GemmArgs a) {
         if (p < nsteps && !noload) issue(p, p);
     int buf = 0;
     for (int s = 0; s < nsteps; ++s) {
-        const int younger = min(NS - 2, nsteps - 1 - s);
-        if (younger >= NS - 2) wait_vmcnt<(NS - 2) * LPS>();
-        else wait_vmcnt<0>();
+        ring_wait<NS, LPS>(nsteps - 1 - s);
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
         if (s + NS - 1 < nsteps && !noload) issue(s + NS - 1, buf == 0 ? NS - 1 : buf - 1);
@@ -1341,10 +1211,10 @@ __global__ __launch_bounds__(512) void gemm_big_kernel(GemmArgs a) {
 #pragma unroll
             for (int m = 0; m < 4; ++m) {
                 if constexpr (WT) af[m] = frag_tr256(wt + (wn0 >> 7) * KT * 256, (wn0 & 127) + 16 * m, c);
-                else af[m] = frag_sw(wt, wn0 + 16 * m, c);
+                else af[m] = frag<LDS_ROW>(wt, wn0 + 16 * m, c);
             }
 #pragma unroll
-            for (int n = 0; n < WM; ++n) bfr[n] = frag_sw(xt, wm0 + 16 * n, c);
+            for (int n = 0; n < WM; ++n) bfr[n] = frag<LDS_ROW>(xt, wm0 + 16 * n, c);
 #pragma unroll
             for (int m = 0; m < 4; ++m)
 #pragma unroll
@@ -1370,63 +1240,24 @@ __global__ __launch_bounds__(512) void gemm_big_kernel(GemmArgs a) {
 template <bool WT, bool PLAIN>
 __global__ __launch_bounds__(256, 2) void gemm_wide_kernel(GemmArgs a) {
     using T = bf16raw;
-    constexpr int KT = 32, NS = 3, WM = 8, TM = 128, TN = 256;
-    constexpr int XB = TM * ROW64, WB = WT ? 2 * KT * 256 : TN * ROW64, STAGE = XB + WB;
-    constexpr int NIX = 2, NIW = 4, LPS = NIX + NIW;
+    using G = RingGeom<T, 128, 256, 4, ROW64, 3, WT>;
+    constexpr int KT = G::KT, NS = 3, WM = G::WM;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    auto xs = [&](int i) -> char* { return smem + i * STAGE; };
-    auto ws = [&](int i) -> char* { return smem + i * STAGE + XB; };
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int bx = blockIdx.x, by = blockIdx.y;
-    if (gridDim.y > 1) {
-        const unsigned total = gridDim.x * gridDim.y;
-        const unsigned lin = blockIdx.x + gridDim.x * blockIdx.y;
-        const unsigned w = xcd_contiguous(lin, total);
-        const unsigned per_band = 8 * gridDim.y;
-        const unsigned band = w / per_band, first = band * 8;
-        const unsigned gsz = min(gridDim.x - first, 8u);
-        bx = (int)(first + (w % per_band) % gsz);
-        by = (int)((w % per_band) / gsz);
-    }
-    const int m_blk = bx * TM, n_blk = by * TN;
+    auto xs = [&](int i) -> char* { return smem + i * G::STAGE; };
+    auto ws = [&](int i) -> char* { return smem + i * G::STAGE + G::XB; };
+    const int wave = threadIdx.x >> 6;
+    const TileIdx t = tile_walk<false>();
+    const int m_blk = t.bx * 128, n_blk = t.by * 256;
     const int wm0 = 0, wn0 = wave * 64;
     const int nsteps = a.K / KT;
-    const char* xsrc[NIX]; int xoff[NIX];
-    const char* wsrc[NIW]; int woff[NIW];
-    long wkstride = 0;
-#pragma unroll
-    for (int it = 0; it < NIX; ++it) {
-        const int R0 = (wave * NIX + it) * 16, r = R0 + (lane >> 2), p = lane & 3;
-        int gr = m_blk + r; if (gr >= a.M) gr = a.M - 1;
-        xsrc[it] = a.X + (long)gr * a.ldx * 2 + ((p ^ swz64(r)) << 4);
-        xoff[it] = R0 * ROW64;
-    }
-    if constexpr (!WT) {
-#pragma unroll
-        for (int it = 0; it < NIW; ++it) {
-            const int R0 = (wave * NIW + it) * 16, r = R0 + (lane >> 2), p = lane & 3;
-            int gr = n_blk + r; if (gr >= a.N) gr = a.N - 1;
-            wsrc[it] = a.W + (long)gr * a.ldw * 2 + ((p ^ swz64(r)) << 4);
-            woff[it] = R0 * ROW64;
-        }
-    } else {
-        const int half = wave >> 1, wq = wave & 1;          // waves 0-1: columns n_blk .. +127, waves 2-3: the next 128; 16 token rows each
-        wkstride = a.ldw * 2;
-#pragma unroll
-        for (int it = 0; it < NIW; ++it) {
-            const int R0 = wq * 16 + it * 4, r = R0 + (lane >> 4), p = lane & 15;
-            int col = n_blk + half * 128 + ((p ^ swz256(r)) << 3);
-            if (col >= a.N) col = 0;
-            wsrc[it] = a.W + ((long)r * a.ldw + col) * 2;
-            woff[it] = half * KT * 256 + R0 * 256;
-        }
-    }
+    GldsKc<T, 128, ROW64, 4> gx;
+    std::conditional_t<WT, GldsKm<KT, 2, 4>, GldsKc<T, 256, ROW64, 4>> gw;
+    constexpr int LPS = decltype(gx)::NI + decltype(gw)::NI;
+    gx.init(a.X, a.ldx, m_blk, a.M, 0);
+    gw.init(a.W, a.ldw, n_blk, a.N, 0);
     auto issue = [&](int step, int buf) {
-        char* xt = xs(buf); char* wt = ws(buf);
-#pragma unroll
-        for (int it = 0; it < NIX; ++it) glds16_asm(xsrc[it] + (long)step * KT * 2, xt + xoff[it]);
-#pragma unroll
-        for (int it = 0; it < NIW; ++it) glds16_asm(wsrc[it] + (WT ? (long)step * KT * wkstride : (long)step * KT * 2), wt + woff[it]);
+        gx.issue(step, xs(buf));
+        gw.issue(step, ws(buf));
     };
     f32x4 acc[4][WM];
     zero_acc(acc);
@@ -1435,9 +1266,7 @@ __global__ __launch_bounds__(256, 2) void gemm_wide_kernel(GemmArgs a) {
         if (p < nsteps) issue(p, p);
     int buf = 0;
     for (int s = 0; s < nsteps; ++s) {
-        const int younger = min(NS - 2, nsteps - 1 - s);
-        if (younger >= NS - 2) wait_vmcnt<(NS - 2) * LPS>();
-        else wait_vmcnt<0>();
+        ring_wait<NS, LPS>(nsteps - 1 - s);
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
         if (s + NS - 1 < nsteps) issue(s + NS - 1, buf == 0 ? NS - 1 : buf - 1);
@@ -1446,10 +1275,10 @@ __global__ __launch_bounds__(256, 2) void gemm_wide_kernel(GemmArgs a) {
 #pragma unroll
         for (int m = 0; m < 4; ++m) {
             if constexpr (WT) af[m] = frag_tr256(wt + (wn0 >> 7) * KT * 256, (wn0 & 127) + 16 * m, 0);
-            else af[m] = frag_sw64(wt, wn0 + 16 * m);
+            else af[m] = frag<ROW64>(wt, wn0 + 16 * m, 0);
         }
 #pragma unroll
-        for (int n = 0; n < WM; ++n) bfr[n] = frag_sw64(xt, wm0 + 16 * n);
+        for (int n = 0; n < WM; ++n) bfr[n] = frag<ROW64>(xt, wm0 + 16 * n, 0);
 #pragma unroll
         for (int m = 0; m < 4; ++m)
 #pragma unroll
@@ -1463,33 +1292,18 @@ __global__ __launch_bounds__(256, 2) void gemm_wide_kernel(GemmArgs a) {
     }
     tile_epilogue<T, WM, PLAIN>(a, acc, m_blk, n_blk, wm0, wn0, 0);
 }
-template <bool WT, bool PLAIN>
-int launch_wide_p(const GemmArgs& a, hipStream_t st) {
-    size_t lds = (size_t)3 * (128 * ROW64 + (WT ? 2 * 32 * 256 : 256 * ROW64));
-    if (lds < (size_t)4 * 128 * EPI_LD) lds = (size_t)4 * 128 * EPI_LD;
-    FW_SET_LDS_ONCE((gemm_wide_kernel<WT, PLAIN>), lds);
-    FW_KNAME("gemm_wide_kernel<%s,%s>", FW_B(WT), FW_B(PLAIN));
-    hipLaunchKernelGGL((gemm_wide_kernel<WT, PLAIN>), dim3(fw_cdiv(a.M, 128), fw_cdiv(a.N, 256), 1), dim3(256), lds, st, a);
-    FW_LAUNCH_RET();
-}
-
-template <bool WT, bool PLAIN>
-int launch_big_p(const GemmArgs& a, hipStream_t st) {
-    size_t lds = (size_t)2 * (256 * LDS_ROW + (WT ? 2 * 64 * 256 : 256 * LDS_ROW));
-    if (lds < (size_t)8 * 128 * EPI_LD) lds = (size_t)8 * 128 * EPI_LD;       // the staged epilogue's 8 x [128][136 B] regions
-    FW_SET_LDS_ONCE((gemm_big_kernel<WT, PLAIN>), lds);
-    FW_KNAME("gemm_big_kernel<%s,%s>", FW_B(WT), FW_B(PLAIN));
-    hipLaunchKernelGGL((gemm_big_kernel<WT, PLAIN>), dim3(fw_cdiv(a.M, 256), fw_cdiv(a.N, 256), 1), dim3(512), lds, st, a);
-    FW_LAUNCH_RET();
-}
 template <bool WT>
 int launch_big(const GemmArgs& a, hipStream_t st) {
     // 128 x 256 tiles at two workgroups per CU, except the 65 536-wide encoder heads: 1 024 tiles of 256 x 256 -- 95 us against 106 us
     // (measured per shape with tools/big_gemm_bench.py)
     constexpr int BIG_MIN_N = 16384;
-    const bool pl = plain_epilogue(a);
-    if (a.N >= BIG_MIN_N) return pl ? launch_big_p<WT, true>(a, st) : launch_big_p<WT, false>(a, st);
-    return pl ? launch_wide_p<WT, true>(a, st) : launch_wide_p<WT, false>(a, st);
+    if (a.N >= BIG_MIN_N)
+        return launch_pg<gemm_big_kernel<WT, true>, gemm_big_kernel<WT, false>>(
+            a, dim3(fw_cdiv(a.M, 256), fw_cdiv(a.N, 256), 1), dim3(512), RingGeom<bf16raw, 256, 256, 8, LDS_ROW, 2, WT>::LDS, st,
+            "gemm_big_kernel<%s,%s>", FW_B(WT));
+    return launch_pg<gemm_wide_kernel<WT, true>, gemm_wide_kernel<WT, false>>(
+        a, dim3(fw_cdiv(a.M, 128), fw_cdiv(a.N, 256), 1), dim3(256), RingGeom<bf16raw, 128, 256, 4, ROW64, 3, WT>::LDS, st,
+        "gemm_wide_kernel<%s,%s>", FW_B(WT));
 }
 
 // =====================================================================================================

@@ -300,6 +300,23 @@ def test_dgrad_slices_on_the_tile_kernel(dtype, kernel):
     o.assert_sentinel('dgrad')
 
 
+def test_k_slices_on_the_ring_kernel():
+    """Two slices of the reduction on the LDS-DMA ring (the split-K order of the tile walk, 3 x 4 x 2 workgroups: an x extent that is
+    no multiple of 8), each a partial tile stored into its own f32 slab at c_zstride.  fw_gemm cuts K = 1856 = 29 steps of 64 into
+    slices of ceil(29 / 2) = 15 steps: k < 960 and k >= 960; 15 steps are below the 28 that select the three-stage ring."""
+    M, N, K, split = 300, 200, 1856, 2
+    kper = 15 * 64
+    p = Product(BF16, 'NT', M, N, K, seed=22)
+    slabs = torch.full((split, M, N + 16), SENTINEL, dtype=F32, device=DEV)
+    p.gemm(out=slabs[0, :, 8:8 + N], splitk=split, c_zstride=M * (N + 16))
+    assert_kernel('gemm_ring_kernel<bf16,64,2,true>', 'K slices')
+    for z in range(split):
+        part = GemmRef(p.ref.x[:, z * kper:(z + 1) * kper], p.ref.w[:, z * kper:(z + 1) * kper])
+        check_gemm(part, BF16, {'out': slabs[z, :, 8:8 + N]}, f'K slice {z}')
+        outside = torch.cat([slabs[z, :, :8], slabs[z, :, 8 + N:]], 1)
+        assert bool((outside == SENTINEL).all()), f'K slice {z}: columns outside the output slice were written'
+
+
 # gemm_stream_kernel<T, NCH, WT, EXT>: NCH from K (128, 256, 512 bytes), EXT 1 = GELU' input, 2 = f32 residual
 @pytest.mark.parametrize('K,nch', [(56, 2), (120, 4), (248, 8)])
 def test_stream_forms(K, nch):
